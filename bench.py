@@ -1,6 +1,6 @@
 """Headline benchmark: activations/sec of the TopK-SAE train step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1]): d_in = 1024, 32x expansion (d_sae = 32768), k = 32,
 batch 16384 activations per GPU, fp32, synthetic N(mu, 1) activations held in a device-resident pool
@@ -37,7 +37,9 @@ import json
 import math
 import os
 import pathlib
+import shutil
 import sys
+import tempfile
 import time
 
 import torch
@@ -324,10 +326,11 @@ def train_e2e_record(dev, *, steps=400, pool_batches=32):
     from saev_amd.nn import modeling, objectives
 
     pool = synthetic_pool(dev, "mean", pool_batches * BATCH, D_MODEL)
+    runs_root = tempfile.mkdtemp(prefix="saev_bench_runs_")  # (this run's own: the checkpoint train() writes is removed below)
     dcfg = data.ShuffledConfig(batch_size=BATCH, seed=17)
     cfg = T.Config(train_data=dcfg, val_data=dcfg, n_train=steps * BATCH, n_val=BATCH,
                    sae=nn.SparseAutoencoderConfig(d_model=D_MODEL, d_sae=D_SAE, reinit_blend=0.0, activation=modeling.TopK(top_k=TOP_K)),
-                   objective=objectives.Matryoshka(n_prefixes=1), log_every=10**9, track=False, runs_root=pathlib.Path("/tmp/saev_bench_runs"))
+                   objective=objectives.Matryoshka(n_prefixes=1), log_every=10**9, track=False, runs_root=pathlib.Path(runs_root))
     t_loop = {}
     orig_iter = sched.BatchLimiter.__iter__
 
@@ -343,6 +346,7 @@ def train_e2e_record(dev, *, steps=400, pool_batches=32):
         sched.BatchLimiter.__iter__ = orig_iter
     torch.cuda.synchronize()
     dt_train = time.perf_counter() - t_loop["t0"]
+    shutil.rmtree(runs_root, ignore_errors=True)
     del saes, objs
     torch.cuda.empty_cache()
     # the bare loop: same shapes, same lr ramp, same pool
@@ -370,6 +374,31 @@ def train_e2e_record(dev, *, steps=400, pool_batches=32):
             "feed": "resident pool of 32 batches, seeded permutation per epoch (data.ShuffledDataLoader), batch drawn inside the step",
             "note": "framework.train.train() end to end (first steps from random init, no log step in the window) against the bare "
                     "SaeEngine.train_step_gather loop on the same pool; tools/bench_train_e2e.py has the streaming feed from a shard directory"}
+
+
+def dump_outputs(eng, n_rows, stats, out_dir, n_latents=2048, n_sample_rows=1024):
+    """What the last timed step hands its caller, as .npy files: the step's statistics, the updated parameters (W_enc / W_dec
+    on a fixed sample of latents), its codes and its reconstruction (on a fixed sample of rows).  The samples come from a
+    fixed seed, so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(0)
+    lat = torch.from_numpy(np.sort(rng.choice(D_SAE, min(n_latents, D_SAE), replace=False))).to(eng.device)
+    rows = torch.from_numpy(np.sort(rng.choice(n_rows, min(n_sample_rows, n_rows), replace=False))).to(eng.device)
+    idx, val, x_hat = eng.last_codes(n_rows)
+    idx, order = idx.sort(dim=1)  # the order of a row's k codes is the kernel's business: ascending latents
+    out = {f"stat_{f}": np.float64(getattr(stats, f)) for f in ("mse", "aux", "l0", "l1", "grad_norm", "n_dead")}
+    out.update(b_enc=eng.view("b_enc"), b_dec=eng.view("b_dec"), W_enc_sampled=eng.view("W_enc")[:, lat],
+               W_dec_sampled=eng.view("W_dec")[lat], sampled_latents=lat.double(),
+               codes_idx=idx.double(), codes_val=val.gather(1, order), x_hat_sampled=x_hat[rows], sampled_rows=rows.double())
+    out = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+    total = sum(np.asarray(v).nbytes for v in out.values())
+    assert total <= 64 << 20, total
+    for name, a in out.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def main():
@@ -419,6 +448,10 @@ def main():
     ap.add_argument("--n-saes", type=int, default=1,
                     help="train this many SAEs on every batch (the reference's parallel groups); the extra ones differ in "
                          "parameters only and share the first one's x statistics / operand images.  value still counts each batch once")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float32 / float64, "
+                         "< 64 MB): the step's loss statistics, b_enc and b_dec, the W_enc columns / W_dec rows of a fixed sample "
+                         "of latents, the codes of every row (latents ascending per row) and x_hat of a fixed sample of rows")
     ap.add_argument("--shape", default=None,
                     help="d_model,d_sae,top_k of a TOY run (rehearsals of the multi-rank code path on one device, e.g. "
                          "--shape 256,2048,16 --batch 256 --backend gloo --same-device): the line then says so in config.workload "
@@ -567,6 +600,8 @@ def main():
     stats = eng.read_stats()
     aux_route_timed = eng.aux_route()
     eng.enable_kernel_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, B, stats, pathlib.Path(args.dump_outputs))
 
     # ---- steady state: a long segment well past the dead-latent threshold -----------------------------------------
     sustained = None

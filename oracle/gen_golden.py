@@ -28,6 +28,8 @@ Fixture index:
   G16 legacy_ckpt      headers in every older checkpoint layout the reference's nn.load still reads (pre-schema, schema 1 in
                        both of its forms, schemas 2-4) and the config the reference's loader makes of each
   G17 batch_entropy    the reference's loader-coverage metrics of the log block (utils/statistics.py) on seeded index batches
+  G18 ckpt_interop     a checkpoint written by this repo's nn.dump, the config and parameters the reference's nn.load made of
+                       it, and the file the reference's nn.dump then wrote of what it loaded
   G14 inference        the reference's framework/inference.worker_fn over a small protocol-2.1 cache (with and
                        without labels.bin / ignore_labels): CSR token_acts, mean_values, sparsity, distributions,
                        metrics.json; plus Metadata.hash and IndexMap known answers for the same cache
@@ -473,6 +475,40 @@ def g16_legacy_checkpoints(ref):
     npz("g16_legacy_checkpoints", **out)
 
 
+def g18_checkpoint_interop(ref):
+    """This repo's ``nn.dump`` -> the reference's ``nn.load`` -> the reference's ``nn.dump``: the fixture keeps the bytes the
+    reference read, what its loader made of them (config as the reference's own dump would write it, parameters) and the
+    file it wrote back, so the round trip is checked without the reference present."""
+    import tempfile
+
+    sys.path.insert(0, str(HERE.parent))
+    from saev_amd.nn import modeling as my_modeling
+
+    torch.manual_seed(180)
+    sae = my_modeling.SparseAutoencoder(my_modeling.SparseAutoencoderConfig(d_model=16, d_sae=48, activation=my_modeling.TopK(top_k=4)))
+    with torch.no_grad():
+        sae.b_enc.copy_(0.05 * torch.randn(48))
+        sae.b_dec.copy_(0.1 * torch.randn(16))
+        sae.W_enc.add_(0.02 * torch.randn(16, 48))
+    with tempfile.TemporaryDirectory(prefix="g18_") as tmp:
+        tmp = pathlib.Path(tmp)
+        my_modeling.dump(tmp / "ours.pt", sae)
+        ours = (tmp / "ours.pt").read_bytes()
+        theirs = ref.modeling.load(tmp / "ours.pt")
+        cfg = dataclasses.asdict(theirs.cfg)
+        cfg["activation"] = ref.modeling._serialize_dataclass(theirs.cfg.activation)
+        ref.modeling.dump(tmp / "theirs.pt", theirs)
+        header, _, rest = (tmp / "theirs.pt").read_bytes().partition(b"\n")
+    hdr = json.loads(header)
+    hdr["commit"] = "unknown"  # container-specific
+    written = json.dumps(hdr).encode() + b"\n" + rest
+    npz("g18_checkpoint_interop", ours=np.frombuffer(ours, dtype=np.uint8),
+        their_cfg=np.frombuffer(json.dumps(cfg, sort_keys=True).encode(), dtype=np.uint8),
+        theirs=np.frombuffer(written, dtype=np.uint8),
+        **{"sd_" + k: v.detach() for k, v in sae.state_dict().items()},
+        **{"loaded_" + k: v.detach() for k, v in theirs.state_dict().items()})
+
+
 def g14_inference(ref, tag, with_labels):
     """Runs the reference's inference pass (its own OrderedDataLoader, manager process included) on a cache written
     by this repo's protocol-2.1 writer and a checkpoint written by the reference's nn.dump."""
@@ -557,6 +593,9 @@ def main():
         g16_legacy_checkpoints(ref)
         g17_batch_entropy(ref)
         return
+    if "--only-g18" in sys.argv:
+        g18_checkpoint_interop(ref)
+        return
     if "--only-g14" in sys.argv:
         g14_inference(ref, "plain", False)
         g14_inference(ref, "labels", True)
@@ -581,6 +620,7 @@ def main():
     g12_checkpoint(ref)
     g16_legacy_checkpoints(ref)
     g17_batch_entropy(ref)
+    g18_checkpoint_interop(ref)
     g13_matryoshka(ref)
     g14_inference(ref, "plain", False)
     g14_inference(ref, "labels", True)

@@ -964,7 +964,7 @@ def test_teacher_forced_matryoshka_steps_match_oracle(tag):
     assert flips <= 3 and dead_max > 0 and routes & {1, 2, 3}, (flips, dead_max, routes)
 
 
-def test_32x32_first_pass_kernel_still_selectable():
+def test_32x32_first_pass_kernel_still_selectable(tmp_path):
     """SAEV_AMD_ENC_MFMA=32 brings the 32x32x16 first-pass kernel back (the A/B switch of the 16x16x32 one; read once per
     process, hence the subprocess): same codes as the default kernel on the same input."""
     import os
@@ -984,9 +984,9 @@ def test_32x32_first_pass_kernel_still_selectable():
         "torch.save((idx.cpu(), val.cpu()), sys.argv[1])\n")
     outs = []
     for shape in ("16", "32"):
-        path = f"/tmp/saev_amd_mfma{shape}.pt"
+        path = tmp_path / f"mfma{shape}.pt"
         env = dict(os.environ, SAEV_AMD_ENC_MFMA=shape, PYTHONPATH=os.pathsep.join(sys.path))
-        subprocess.run([sys.executable, "-c", code, path], check=True, env=env, timeout=600)
+        subprocess.run([sys.executable, "-c", code, str(path)], check=True, env=env, timeout=600)
         outs.append(torch.load(path))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 

@@ -218,20 +218,39 @@ def test_load_legacy_edge_cases(tmp_path):
 
 
 def test_reference_loader_reads_our_checkpoint(tmp_path):
-    import _refshim
+    """Fixture G18: the reference's nn.load read a checkpoint this repo's dump wrote and made our config and parameters of
+    it; the file its nn.dump then wrote loads back here to the same SAE.  Our dump still writes what the reference read."""
+    import io
 
-    if not _refshim.available():
-        pytest.skip("reference checkout not present (GPU box)")
     from saev_amd.nn import modeling as M
 
-    ref = _refshim.install()
-    sae = M.SparseAutoencoder(M.SparseAutoencoderConfig(d_model=16, d_sae=48, activation=M.TopK(top_k=4)))
+    g = load_golden("g18_checkpoint_interop")
+    sd = {k: g["sd_" + k] for k in R.PARAM_ORDER}
+    ours = bytes(g["ours"].numpy().tolist())
+    read_header, _, read_rest = ours.partition(b"\n")
+    read_header = json.loads(read_header)
+    (tmp_path / "read.pt").write_bytes(ours)
+    sae = M.load(tmp_path / "read.pt")
+    assert sae.cfg == M.SparseAutoencoderConfig(d_model=16, d_sae=48, activation=M.TopK(top_k=4))
+    for k in R.PARAM_ORDER:
+        assert torch.equal(getattr(sae, k), sd[k]), k
     M.dump(tmp_path / "ours.pt", sae)
-    theirs = ref.modeling.load(tmp_path / "ours.pt")
-    assert torch.equal(theirs.W_enc, sae.W_enc) and theirs.cfg.activation.top_k == 4
-    ref.modeling.dump(tmp_path / "theirs.pt", theirs)
+    header, _, rest = (tmp_path / "ours.pt").read_bytes().partition(b"\n")
+    header = json.loads(header)
+    assert set(header) == set(read_header) and header["schema"] == read_header["schema"] == 5
+    assert header["cfg"] == read_header["cfg"], "the header the reference's loader read"
+    assert list(torch.load(io.BytesIO(rest), weights_only=True)) == list(torch.load(io.BytesIO(read_rest), weights_only=True))
+    their_cfg = json.loads(bytes(g["their_cfg"].numpy().tolist()).decode())
+    got = dataclasses.asdict(sae.cfg)
+    got["activation"] = M._ser(sae.cfg.activation)
+    assert got == their_cfg, "the config the reference's loader made of our file"
+    for k in R.PARAM_ORDER:
+        assert torch.equal(g["loaded_" + k], sd[k]), k
+    (tmp_path / "theirs.pt").write_bytes(bytes(g["theirs"].numpy().tolist()))
     again = M.load(tmp_path / "theirs.pt")
-    assert again.cfg == sae.cfg and torch.equal(again.b_dec, sae.b_dec)
+    assert again.cfg == sae.cfg
+    for k in R.PARAM_ORDER:
+        assert torch.equal(getattr(again, k), sd[k]), k
 
 
 def test_module_surface_matches_reference_shapes():
