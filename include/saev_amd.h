@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SAEV_AMD_ABI_VERSION 10
+#define SAEV_AMD_ABI_VERSION 11
 
 typedef enum {
     SAEV_OK = 0,
@@ -75,7 +75,15 @@ typedef struct {
                                       the rows of ALL data-parallel ranks); sizes only the backward's pair order, slice-major
                                       copies and partial rows -- the forward's buffers (candidate lists, dense fallback,
                                       AuxK, ...) stay at max_batch, which is then the LOCAL batch.                      */
+    int32_t activation;            /* SAEV_ACT_TOPK (0) or SAEV_ACT_RELU.  A ReLU context (nn/modeling.py:111-113 Relu, :150-156
+                                      ReluActivation) ignores top_k and needs k_aux = 0; it runs the forward entries only:
+                                      saev_encode_relu, saev_decode_rows, saev_scatter_rows and the single ops, while the
+                                      step entries and saev_encode_topk return SAEV_UNSUPPORTED (training a ReLU SAE is not
+                                      on this path).                                                                 */
 } saev_cfg;
+
+#define SAEV_ACT_TOPK 0
+#define SAEV_ACT_RELU 1
 
 /* Element offsets of the four tensors inside each flat buffer, its total length, and the per-rank chunk lengths of the
  * two halves (all in floats) for this configuration.  Without shard_world: off_W_dec 0, off_b_dec S*D, off_W_enc
@@ -231,6 +239,28 @@ int saev_scatter_dense(saev_ctx* ctx, const int32_t* idx, const float* val, int3
  * `prefixes_host` has n_prefixes ascending cut points ending at d_sae (NULL => one prefix). */
 int saev_decode_sparse(saev_ctx* ctx, const int32_t* idx, const float* val, int32_t n_rows, int32_t k,
                        const int64_t* prefixes_host, int32_t n_prefixes, float* x_hats_out, void* stream);
+/* ---- ReLU SAE forward (variable-length rows) ------------------------------------------------
+ * A ReLU code row has no fixed length.  Rows are PADDED: idx (n_rows x row_cap) int32 and val (n_rows x row_cap) fp32 hold
+ * row b's entries in their first row_nnz[b] slots, in ascending latent order (the CSR-block order framework/inference.py
+ * relies on); slots past row_nnz[b] are unspecified. */
+/* modeling.py:343-347 encode + :150-156 ReluActivation: f = relu(x @ W_enc + b_enc) without a dense h.  row_nnz_out[b] is the
+ * EXACT number of positives of row b, also when it exceeds row_cap; only the first row_cap entries of such a row are stored and
+ * *overflow_out (a device int32) receives the largest count: 0 when every row fit, else > row_cap -- the caller reads it back
+ * and repeats the call with row_cap >= that count (a row is never silently truncated).  Arithmetic: exact fp32 products and
+ * sums in every fp32-accurate encoder mode (F32, F16X3, F16R); BF16 returns SAEV_UNSUPPORTED.  The entries past row_nnz of
+ * a padded row are not touched.  Needs a context with activation = SAEV_ACT_RELU. */
+int saev_encode_relu(saev_ctx* ctx, const float* x, int32_t n_rows, int32_t row_cap, int32_t* row_nnz_out, int32_t* idx_out,
+                     float* val_out, int32_t* overflow_out, void* stream);
+/* modeling.py:351-409 on padded rows: x_hat[b, p, :] = b_dec + sum_{j < row_nnz[b], idx < prefixes[p]} val * W_dec[idx]; the
+ * cost grows with row_nnz, not with row_cap (a row_nnz above row_cap reads as row_cap).  With n_prefixes > 1 (at most 16,
+ * ascending, ending at d_sae) the entries of each row must be in ascending latent order, as saev_encode_relu writes them.
+ * x_hats_out is (n_rows, n_prefixes, d_model).  Any activation. */
+int saev_decode_rows(saev_ctx* ctx, const int32_t* idx, const float* val, const int32_t* row_nnz, int32_t row_cap,
+                     int32_t n_rows, const int64_t* prefixes_host, int32_t n_prefixes, float* x_hats_out, void* stream);
+/* saev_scatter_dense for padded rows: f_out[b, idx] = val for the first min(row_nnz[b], row_cap) entries of each row, into a
+ * zero-initialised (n_rows x d_sae) matrix (dense f_x for API compatibility). */
+int saev_scatter_rows(saev_ctx* ctx, const int32_t* idx, const float* val, const int32_t* row_nnz, int32_t row_cap,
+                      int32_t n_rows, float* f_out, void* stream);
 /* modeling.py:419-445 on the bound grad buffer. */
 int saev_remove_parallel_grads(saev_ctx* ctx, void* stream);
 /* Row gather out of a device-resident activation pool (replaces ReservoirBuffer.get,

@@ -13,7 +13,7 @@ import pathlib
 _HERE = pathlib.Path(__file__).resolve().parent
 LIB_PATH = pathlib.Path(os.environ.get("SAEV_AMD_LIB", _HERE / "libsaev_amd.so"))
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class SaevCfg(C.Structure):
@@ -23,6 +23,7 @@ class SaevCfg(C.Structure):
         ("normalize_w_dec", C.c_int32), ("remove_parallel_grads", C.c_int32),
         ("max_batch", C.c_int32), ("encoder_mode", C.c_int32), ("aux_dead_cap", C.c_int32),
         ("shard_world", C.c_int32), ("bound_mode", C.c_int32), ("max_backward_rows", C.c_int32),
+        ("activation", C.c_int32),
     ]
 
 
@@ -72,6 +73,9 @@ _SIGNATURES = {
     "saev_encode_topk": (C.c_int, [P, P, C.c_int32, P, P, P]),
     "saev_scatter_dense": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, P]),
     "saev_decode_sparse": (C.c_int, [P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, P]),
+    "saev_encode_relu": (C.c_int, [P, P, C.c_int32, C.c_int32, P, P, P, P, P]),
+    "saev_decode_rows": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, P, C.c_int32, P, P]),
+    "saev_scatter_rows": (C.c_int, [P, P, P, P, C.c_int32, C.c_int32, P, P]),
     "saev_remove_parallel_grads": (C.c_int, [P, P]),
     "saev_gather_rows": (C.c_int, [P, P, P, C.c_int32, P, P]),
     "saev_step_forward": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, P]),

@@ -353,6 +353,15 @@ int saev_create(const saev_cfg* cfg, int device, saev_ctx** out) { return saev_c
 int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, saev_ctx** out) {
     if (!cfg || !out) return SAEV_INVALID_ARG;
     *out = nullptr;
+    if (cfg->activation != SAEV_ACT_TOPK && cfg->activation != SAEV_ACT_RELU) return SAEV_INVALID_ARG;
+    // a ReLU context (forward entries only) has no k: its TopK-sized scratch is sized for k = 1
+    saev_cfg relu_cfg;
+    if (cfg->activation == SAEV_ACT_RELU) {
+        if (cfg->k_aux != 0) return SAEV_UNSUPPORTED;
+        relu_cfg = *cfg;
+        relu_cfg.top_k = 1;
+        cfg = &relu_cfg;
+    }
     if (cfg->d_model <= 0 || cfg->d_sae <= 0 || cfg->top_k <= 0 || cfg->max_batch <= 0) return SAEV_INVALID_ARG;
     // candidate lists are addressed with 32-bit byte offsets (max_batch <= 246 723 rows per call)
     if ((uint64_t)cfg->max_batch * CAND_STRIDE * 4ull >= (1ull << 32)) return SAEV_INVALID_ARG;
@@ -1081,6 +1090,7 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
 
 int saev_encode_topk(saev_ctx* c, const float* x, int32_t n, int32_t* idx_out, float* val_out, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_encode_topk: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params, SAEV_NOT_BOUND, "parameters not bound");
     REQUIRE(c, x && idx_out && val_out && n > 0 && n <= c->cfg.max_batch, SAEV_INVALID_ARG,
             "saev_encode_topk: bad arguments (n_rows must be in 1..max_batch)");
@@ -1136,6 +1146,60 @@ int saev_decode_sparse(saev_ctx* c, const int32_t* idx, const float* val, int32_
     return SAEV_OK;
 }
 
+// ---- ReLU SAE forward (relu.hip) --------------------------------------------------------------
+
+int saev_encode_relu(saev_ctx* c, const float* x, int32_t n, int32_t row_cap, int32_t* row_nnz_out, int32_t* idx_out,
+                     float* val_out, int32_t* overflow_out, void* stream) {
+    if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->params, SAEV_NOT_BOUND, "parameters not bound");
+    REQUIRE(c, c->cfg.activation == SAEV_ACT_RELU, SAEV_UNSUPPORTED, "saev_encode_relu: the context is not a ReLU context");
+    REQUIRE(c, c->cfg.encoder_mode != SAEV_ENCODER_BF16, SAEV_UNSUPPORTED,
+            "saev_encode_relu: the bf16 encoder is not available for ReLU (use f32, f16x3 or f16r)");
+    REQUIRE(c, x && row_nnz_out && idx_out && val_out && overflow_out && n > 0 && row_cap > 0, SAEV_INVALID_ARG,
+            "saev_encode_relu: bad arguments");
+    REQUIRE(c, ((uintptr_t)x % 16) == 0, SAEV_INVALID_ARG, "x must be 16-byte aligned");
+    REQUIRE(c, c->off_W_enc % 4 == 0, SAEV_UNSUPPORTED, "saev_encode_relu: W_enc is not 16-byte aligned in this layout");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipMemsetAsync(overflow_out, 0, sizeof(int32_t), s));
+    ReluEncodeArgs a{};
+    a.x = x; a.W_enc = c->params + c->off_W_enc; a.b_enc = c->params + c->off_b_enc;
+    a.n_rows = n; a.D = c->cfg.d_model; a.S = c->cfg.d_sae; a.row_cap = row_cap;
+    a.idx_out = idx_out; a.val_out = val_out; a.row_nnz_out = row_nnz_out; a.max_nnz_out = overflow_out;
+    HIPCHK(c, launch_relu_encode(a, s));
+    return SAEV_OK;
+}
+
+int saev_decode_rows(saev_ctx* c, const int32_t* idx, const float* val, const int32_t* row_nnz, int32_t row_cap, int32_t n,
+                     const int64_t* prefixes_host, int32_t n_prefixes, float* x_hats_out, void* stream) {
+    if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->params, SAEV_NOT_BOUND, "parameters not bound");
+    REQUIRE(c, idx && val && row_nnz && x_hats_out && n > 0 && row_cap > 0, SAEV_INVALID_ARG, "saev_decode_rows: bad arguments");
+    const int S = c->cfg.d_sae;
+    int64_t single = S;
+    if (!prefixes_host) { prefixes_host = &single; n_prefixes = 1; }
+    REQUIRE(c, n_prefixes >= 1 && n_prefixes <= 16, SAEV_INVALID_ARG, "saev_decode_rows: 1 to 16 prefixes");
+    REQUIRE(c, prefixes_host[n_prefixes - 1] == S && prefixes_host[0] >= 1, SAEV_INVALID_ARG,
+            "prefixes must end at d_sae and start at >= 1");
+    for (int p = 1; p < n_prefixes; ++p)
+        REQUIRE(c, prefixes_host[p] > prefixes_host[p - 1], SAEV_INVALID_ARG, "prefixes must be strictly increasing");
+    ReluDecodeArgs a{};
+    a.idx = idx; a.val = val; a.row_nnz = row_nnz; a.row_cap = row_cap; a.n_rows = n; a.D = c->cfg.d_model;
+    a.W_dec = c->params + c->off_W_dec; a.b_dec = c->params + c->off_b_dec;
+    a.n_prefixes = n_prefixes;
+    for (int p = 0; p < n_prefixes; ++p) a.prefixes[p] = prefixes_host[p];
+    a.x_hats = x_hats_out;
+    HIPCHK(c, launch_relu_decode(a, (hipStream_t)stream));
+    return SAEV_OK;
+}
+
+int saev_scatter_rows(saev_ctx* c, const int32_t* idx, const float* val, const int32_t* row_nnz, int32_t row_cap, int32_t n,
+                      float* f_out, void* stream) {
+    if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, idx && val && row_nnz && f_out && n > 0 && row_cap > 0, SAEV_INVALID_ARG, "saev_scatter_rows: bad arguments");
+    HIPCHK(c, launch_relu_scatter(idx, val, row_nnz, row_cap, n, c->cfg.d_sae, f_out, (hipStream_t)stream));
+    return SAEV_OK;
+}
+
 int saev_remove_parallel_grads(saev_ctx* c, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
     REQUIRE(c, c->params && c->grads, SAEV_NOT_BOUND, "parameters/grads not bound");
@@ -1159,6 +1223,7 @@ int saev_gather_rows(saev_ctx* c, const float* pool, const int64_t* rows, int32_
 int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_global, int32_t training,
                       void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_step_forward: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params, SAEV_NOT_BOUND, "parameters not bound");
     REQUIRE(c, x && n > 0 && n <= c->cfg.max_batch, SAEV_INVALID_ARG,
             "saev_step_forward: n_rows must be in 1..max_batch");
@@ -2014,6 +2079,7 @@ int saev_wdec_ready_event(saev_ctx* c, void* event) {
 
 int saev_tail_prepare(saev_ctx* c, int32_t shard_rank, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_tail_prepare: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params && c->grads, SAEV_NOT_BOUND, "saev_tail_prepare: params/grads not bound");
     TailRanges r;
     int rc = tail_ranges(c, shard_rank, &r);
@@ -2065,6 +2131,7 @@ int saev_tail_prepare(saev_ctx* c, int32_t shard_rank, void* stream) {
 int saev_tail_apply(saev_ctx* c, float lr, float max_norm, float grad_scale, int64_t adam_step, int32_t shard_rank,
                     void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_tail_apply: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params && c->grads && c->adam_m && c->adam_v, SAEV_NOT_BOUND,
             "saev_tail_apply: params/grads/adam state not bound");
     REQUIRE(c, adam_step >= 1, SAEV_INVALID_ARG, "adam_step is 1-based");
@@ -2294,6 +2361,7 @@ int saev_comm_destroy(saev_ctx* c) {
 
 int saev_train_step_dp(saev_ctx* c, const float* x_local, int32_t n_local, float lr, float max_norm, int64_t adam_step, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_train_step_dp: a ReLU context runs the forward entries only");
     REQUIRE(c, c->comm != nullptr, SAEV_INVALID_ARG, "saev_train_step_dp: no communicator (saev_comm_init)");
     REQUIRE(c, c->grads != nullptr, SAEV_NOT_BOUND, "saev_train_step_dp: no gradient buffer bound");
     hipStream_t s = (hipStream_t)stream;

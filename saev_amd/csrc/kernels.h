@@ -685,3 +685,32 @@ hipError_t launch_scatter_add_dead(const int32_t* dl, int nd, int D, const float
                                    // part already, unless the latent was cut by run boundaries (starts: the CSC offsets):
                                    // the statistics left here are then those of the row as it is now MINUS that part
                                    const int32_t* starts = nullptr);
+
+// ---- ReLU SAE forward (relu.hip) -------------------------------------------------------------
+struct ReluEncodeArgs {
+    const float* x;       // (n_rows, D)
+    const float* W_enc;   // (D, S)
+    const float* b_enc;   // (S)
+    int n_rows, D, S;
+    int row_cap;          // capacity of a padded output row
+    int32_t* idx_out;     // (n_rows, row_cap) ascending latents with f > 0
+    float* val_out;       // (n_rows, row_cap)
+    int32_t* row_nnz_out; // (n_rows) exact count of positives (may exceed row_cap)
+    int32_t* max_nnz_out; // init 0: atomicMax of the counts that exceed row_cap
+};
+hipError_t launch_relu_encode(const ReluEncodeArgs& a, hipStream_t stream);
+
+struct ReluDecodeArgs {
+    const int32_t* idx;     // (n_rows, row_cap) ascending per row
+    const float* val;
+    const int32_t* row_nnz; // (n_rows); entries past min(row_nnz, row_cap) are ignored
+    int row_cap, n_rows, D;
+    const float* W_dec;     // (S, D)
+    const float* b_dec;     // (D)
+    int n_prefixes;         // <= 16
+    int64_t prefixes[16];   // ascending cut points, the last = S
+    float* x_hats;          // (n_rows, n_prefixes, D)
+};
+hipError_t launch_relu_decode(const ReluDecodeArgs& a, hipStream_t stream);
+hipError_t launch_relu_scatter(const int32_t* idx, const float* val, const int32_t* row_nnz, int row_cap, int n_rows, int S,
+                               float* f_out, hipStream_t stream);

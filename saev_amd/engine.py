@@ -86,6 +86,9 @@ class EngineConfig:
     group_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_GROUP", "0")))
     aux_split_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_SPLIT", "0")))
     aux_wide_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_WIDE", "0")))
+    # "topk" (default), or "relu": a forward-only context for a ReLU SAE (top_k is ignored, k_aux must be 0): encode_relu,
+    # decode_rows, scatter_rows and the single ops run; the step entries raise NotImplementedError
+    activation: str = "topk"
 
 
 @dataclasses.dataclass
@@ -146,6 +149,10 @@ class SaeEngine:
             raise ValueError(f"EngineConfig.bounds (SAEV_AMD_BOUNDS) must be 'guaranteed' or 'predicted', got {cfg.bounds!r}")
         if cfg.encoder not in ("f32", "f16x3", "bf16", "f16r"):
             raise ValueError(f"EngineConfig.encoder (SAEV_AMD_ENCODER) must be one of f32, f16x3, bf16, f16r, got {cfg.encoder!r}")
+        if cfg.activation not in ("topk", "relu"):
+            raise ValueError(f"EngineConfig.activation must be 'topk' or 'relu', got {cfg.activation!r}")
+        if cfg.activation == "relu" and cfg.k_aux != 0:
+            raise ValueError("a ReLU engine has no auxiliary loss: k_aux must be 0")
         with torch.cuda.device(self.device):
             self.params = torch.zeros(self.n_params, device=self.device, dtype=torch.float32)
             self.grads = torch.zeros_like(self.params) if with_optim else None
@@ -160,6 +167,7 @@ class SaeEngine:
                 max_batch=cfg.max_batch, encoder_mode={"f32": 0, "f16x3": 1, "bf16": 2, "f16r": 3}[cfg.encoder],
                 aux_dead_cap=cfg.aux_dead_cap, shard_world=cfg.shard_world,
                 bound_mode={"guaranteed": 0, "predicted": 1}[cfg.bounds], max_backward_rows=cfg.max_backward_rows,
+                activation={"topk": 0, "relu": 1}[cfg.activation],
             )
             if cfg.dw_route not in ("slices", "rows", "slices_a", "slices_s") or cfg.fwd_route not in ("default", "rows", "sum_pass"):
                 raise ValueError(f"EngineConfig.dw_route must be 'slices', 'slices_a', 'slices_s' or 'rows' and fwd_route 'default', 'rows' or 'sum_pass', got {cfg.dw_route!r} / {cfg.fwd_route!r}")
@@ -183,10 +191,18 @@ class SaeEngine:
         self.adam_steps = 0
         self._x_keepalive = None
         self._w_enc_t = None
+        # ReLU rows: capacity of the next encode_relu (grows to the largest count seen) and how many calls needed a second launch
+        self.relu_row_cap = min(cfg.d_sae, 512)
+        self.relu_second_launches = 0
 
     # ---- plumbing -------------------------------------------------------------------------
     def _chk(self, rc, what):
         _lib.check(self.lib, self.ctx, rc, what)
+
+    def _topk_only(self, what: str):
+        if self.cfg.activation != "topk":
+            raise NotImplementedError(f"{what}: training and the TopK forward are not on the HIP path for a {self.cfg.activation} SAE "
+                                      "(only its forward is: encode_relu / decode_rows)")
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -311,6 +327,7 @@ class SaeEngine:
         return idx, val
 
     def encode_topk(self, x: torch.Tensor):
+        self._topk_only("encode_topk")
         x = self._check_x(x)
         self._note_param_writes()
         n, k = x.shape[0], min(self.cfg.top_k, self.cfg.d_sae)
@@ -336,6 +353,55 @@ class SaeEngine:
         self._chk(self.lib.saev_decode_sparse(self.ctx, _ptr(idx.contiguous()), _ptr(val.contiguous()), n, k, arr, len(pre), _ptr(out), _stream()), "saev_decode_sparse")
         return out
 
+    # ---- ReLU SAE forward: padded variable-length rows (include/saev_amd.h, saev_encode_relu) ---------------------------
+    def encode_relu(self, x: torch.Tensor, row_cap: int | None = None):
+        """f = relu(x W_enc + b_enc) as padded rows: ``(idx, val, row_nnz)``, idx / val (n, cap), row b's entries in its first
+        row_nnz[b] slots in ascending latent order (slots past it are unspecified).  ``cap`` starts at ``row_cap`` (default: the
+        engine's ``relu_row_cap``); when a row has more positives the call reads the largest count back and runs the encoder
+        once more with that capacity, so no row is truncated.  Without ``row_cap`` the engine's capacity then grows to it."""
+        if self.cfg.activation != "relu":
+            raise _lib.SaevError("encode_relu needs an engine created with activation='relu'")
+        if self.cfg.encoder == "bf16":
+            raise NotImplementedError("the bf16 encoder is not available for ReLU SAEs: use f32, f16x3 or f16r")
+        x = self._check_x(x)
+        self._note_param_writes()
+        n, S = x.shape[0], self.cfg.d_sae
+        cap = max(1, min(S, row_cap if row_cap is not None else self.relu_row_cap))
+        over = torch.empty(1, device=self.device, dtype=torch.int32)
+        row_nnz = torch.empty(n, device=self.device, dtype=torch.int32)
+        for attempt in range(2):
+            idx = torch.empty(n, cap, device=self.device, dtype=torch.int32)
+            val = torch.empty(n, cap, device=self.device, dtype=torch.float32)
+            self._chk(self.lib.saev_encode_relu(self.ctx, _ptr(x), n, cap, _ptr(row_nnz), _ptr(idx), _ptr(val), _ptr(over), _stream()),
+                      "saev_encode_relu")
+            need = int(over.item())  # the call's one read-back: 0, or the largest row count when a row overflowed
+            if need == 0:
+                return idx, val, row_nnz
+            if attempt == 1:
+                raise _lib.SaevError(f"saev_encode_relu overflowed a capacity of {cap} sized from its own count {need}")
+            cap = need
+            self.relu_second_launches += 1
+            if row_cap is None:
+                self.relu_row_cap = max(self.relu_row_cap, min(S, (need + 63) // 64 * 64))
+
+    def decode_rows(self, idx: torch.Tensor, val: torch.Tensor, row_nnz: torch.Tensor, prefixes=None) -> torch.Tensor:
+        """(n, n_prefixes, d_model) reconstructions of padded rows (ascending latents per row); the cost grows with row_nnz."""
+        n, cap = idx.shape
+        pre = [self.cfg.d_sae] if prefixes is None else [int(p) for p in prefixes]
+        arr = (C.c_int64 * len(pre))(*pre)
+        out = torch.empty(n, len(pre), self.cfg.d_model, device=self.device, dtype=torch.float32)
+        self._chk(self.lib.saev_decode_rows(self.ctx, _ptr(idx.contiguous()), _ptr(val.contiguous()), _ptr(row_nnz.contiguous()), cap, n,
+                                            arr, len(pre), _ptr(out), _stream()), "saev_decode_rows")
+        return out
+
+    def scatter_rows(self, idx: torch.Tensor, val: torch.Tensor, row_nnz: torch.Tensor) -> torch.Tensor:
+        """Dense (n, d_sae) f_x of padded rows (API compatibility)."""
+        n, cap = idx.shape
+        f = torch.zeros(n, self.cfg.d_sae, device=self.device, dtype=torch.float32)
+        self._chk(self.lib.saev_scatter_rows(self.ctx, _ptr(idx.contiguous()), _ptr(val.contiguous()), _ptr(row_nnz.contiguous()), cap, n,
+                                             _ptr(f), _stream()), "saev_scatter_rows")
+        return f
+
     def remove_parallel_grads(self):
         self._chk(self.lib.saev_remove_parallel_grads(self.ctx, _stream()), "saev_remove_parallel_grads")
 
@@ -348,6 +414,7 @@ class SaeEngine:
 
     # ---- the step -------------------------------------------------------------------------
     def step_forward(self, x: torch.Tensor, *, training: bool = True, n_rows_global: int | None = None):
+        self._topk_only("step_forward")
         x = self._check_x(x)
         self._x_keepalive = x
         self._note_param_writes()
@@ -355,9 +422,11 @@ class SaeEngine:
         self._chk(self.lib.saev_step_forward(self.ctx, _ptr(x), n, n_rows_global or n, int(training), _stream()), "saev_step_forward")
 
     def step_dead(self, n_rows_global: int):
+        self._topk_only("step_dead")
         self._chk(self.lib.saev_step_dead(self.ctx, n_rows_global, _stream()), "saev_step_dead")
 
     def step_backward(self):
+        self._topk_only("step_backward")
         self._chk(self.lib.saev_step_backward(self.ctx, _stream()), "saev_step_backward")
 
     # backward in pieces (data-parallel overlap, see framework/ddp.py)
@@ -370,6 +439,7 @@ class SaeEngine:
         return self._w_enc_t
 
     def backward_begin(self):
+        self._topk_only("backward_begin")
         self._chk(self.lib.saev_backward_begin(self.ctx, _stream()), "saev_backward_begin")
 
     def backward_rows(self, lo: int, hi: int, part: int = 0):
@@ -383,6 +453,7 @@ class SaeEngine:
     def step_tail(self, lr: float, max_norm: float = 1.0, grad_scale: float = 1.0, *, trusted: bool = False):
         """``trusted``: nothing wrote the gradient buffer since ``backward_end`` -- the tail may use the row statistics the
         backward left behind (projection inside Adam, no rpg pass), as ``train_step`` does."""
+        self._topk_only("step_tail")
         self.adam_steps += 1
         if trusted:
             self._chk(self.lib.saev_trust_gradients(self.ctx, 1), "saev_trust_gradients")
@@ -441,9 +512,11 @@ class SaeEngine:
 
 
     def tail_prepare(self, shard_rank: int = -1):
+        self._topk_only("tail_prepare")
         self._chk(self.lib.saev_tail_prepare(self.ctx, shard_rank, _stream()), "saev_tail_prepare")
 
     def tail_apply(self, lr: float, max_norm: float = 1.0, grad_scale: float = 1.0, shard_rank: int = -1):
+        self._topk_only("tail_apply")
         self.adam_steps += 1
         self._chk(self.lib.saev_tail_apply(self.ctx, lr, max_norm, grad_scale, self.adam_steps, shard_rank, _stream()), "saev_tail_apply")
 
@@ -465,6 +538,7 @@ class SaeEngine:
         ``grad_views()`` is NOT a valid gradient afterwards: the W_enc gradient stays in the transposed scratch and the
         dW_dec rows are stored un-projected (the fused Adam projects them as it reads).  To look at gradients run the phases
         (``step_forward`` / ``step_dead`` / ``step_backward`` / ``step_tail``), as the log steps of ``train()`` do."""
+        self._topk_only("train_step")
         x = self._check_x(x)
         self._x_keepalive = x
         self._note_param_writes()
@@ -487,6 +561,7 @@ class SaeEngine:
         return int(self.lib.saev_comm_world(self.ctx))
 
     def train_step_dp(self, x_local: torch.Tensor, lr: float, max_norm: float = 1.0):
+        self._topk_only("train_step_dp")
         """One optimizer step on the global batch of which ``x_local`` is this rank's share (equal shares on all ranks): forward,
         all-reduce of the fired flags, AuxK + backward, all-reduce of the flat gradient, tail with the gradient averaged --
         all enqueued by ONE call into the library (saev_train_step_dp), RCCL on torch's current stream."""
@@ -499,6 +574,7 @@ class SaeEngine:
     def train_step_gather(self, pool: torch.Tensor, rows: torch.Tensor, lr: float, max_norm: float = 1.0, out: torch.Tensor | None = None) -> torch.Tensor:
         """``train_step`` on the batch ``pool[rows]``, drawn inside the step (saev_train_step_gather): the step's first kernel reads
         the pool rows and leaves the batch as a contiguous matrix -- returned -- on its way."""
+        self._topk_only("train_step_gather")
         n = rows.shape[0]
         if pool.device != self.device or pool.dtype != torch.float32 or pool.ndim != 2 or pool.shape[1] != self.cfg.d_model or not pool.is_contiguous():
             raise _lib.SaevError(f"the pool must be a contiguous float32 (rows, {self.cfg.d_model}) matrix on {self.device}")

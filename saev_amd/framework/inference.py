@@ -12,7 +12,9 @@ Writes under ``<run>/inference/<metadata hash>/``:
 
 The reference materialises the dense (B, d_sae) ``f_x`` per batch, copies it to the host and lets scipy compress it
 (inference.py:189-246).  Here the codes never leave their sparse form: the HIP encoder returns (idx, val) with
-ascending latent indices per row, which *is* a CSR block; per-latent sums are index-adds over the B*k codes.
+ascending latent indices per row, which *is* a CSR block; per-latent sums are index-adds over the B*k codes.  A ReLU SAE
+takes the same route with padded variable-length rows (SaeEngine.encode_relu: the first row_nnz entries of each row, also in
+ascending latent order) and their decode (SaeEngine.decode_rows); its SSE is summed in fp64 from x_hat.
 """
 
 from __future__ import annotations
@@ -123,6 +125,7 @@ def worker_fn(cfg: Config):
     batch_size = cfg.data.batch_size // T * T  # whole examples per batch (inference.py:158-165)
     loader = OrderedDataLoader(dataclasses.replace(cfg.data, batch_size=batch_size), device=device)
     eng = sae._eng(batch_size)
+    relu = isinstance(sae.cfg.activation, nn.modeling.Relu)
 
     if cfg.save:
         value_sum = torch.zeros(S, device=device)
@@ -142,8 +145,12 @@ def worker_fn(cfg: Config):
     for batch in loader:
         x = batch["act"]
         b = x.shape[0]
-        eng.step_forward(x, training=False)
-        idx, val, x_hat = eng.last_codes(b)
+        if relu:
+            idx, val, row_nnz = eng.encode_relu(x)
+            x_hat = eng.decode_rows(idx, val, row_nnz)[:, 0]
+        else:
+            eng.step_forward(x, training=False)
+            idx, val, x_hat = eng.last_codes(b)
         keep_host = torch.ones(b, dtype=torch.bool)
         if "token_labels" in batch:  # segmentation caches: drop tokens whose label is ignored
             keep_host = torch.isin(batch["token_labels"], ignore, invert=True)
@@ -151,7 +158,7 @@ def worker_fn(cfg: Config):
         n_tokens += n_keep
         keep = keep_host.to(device)
         if n_keep > 0:
-            if n_keep == b:
+            if n_keep == b and not relu:
                 st = eng.read_stats()  # fp64 sums of this batch from the step's own reduction
                 sse += st.sse
                 sum_sq += st.sum_sq
@@ -169,7 +176,10 @@ def worker_fn(cfg: Config):
         assert g[0].item() == prev_i + 1 and bool((g[1:] == g[:-1] + 1).all()), "batches must arrive in global order"
         prev_i = int(g[-1].item())
 
-        live = (val != 0) & keep[:, None]  # what a dense -> CSR conversion of the masked f_x would keep
+        if relu:  # the row's first row_nnz entries, all > 0
+            live = (torch.arange(idx.shape[1], device=device)[None, :] < row_nnz[:, None]) & keep[:, None]
+        else:
+            live = (val != 0) & keep[:, None]  # what a dense -> CSR conversion of the masked f_x would keep
         cols, vals = idx[live].long(), val[live]
         value_sum.index_add_(0, cols, vals)
         n_pos.index_add_(0, cols, (vals > 0).to(torch.float32))

@@ -182,11 +182,22 @@ def _make_loader(cfg_data, device, rank, world, pool=None):
     return saev_data.ShuffledDataLoader(cfg_data, device=device, rank=rank, world_size=world, pool=pool)
 
 
+def _require_topk(cfgs: list[Config], what: str) -> None:
+    """Only TopK SAEs train on the HIP path: a ReLU SAE runs its forward (nn.modeling, framework.inference) only, BatchTopK
+    nothing."""
+    for c in cfgs:
+        act = c.sae.activation
+        if not isinstance(act, modeling.TopK):
+            raise NotImplementedError(f"{what}: {type(act).__name__} SAEs are not trained on the HIP path (TopK only; a Relu SAE's "
+                                      "forward runs through nn.SparseAutoencoder and framework.inference)")
+
+
 def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=None) -> tuple[torch.nn.ModuleList, torch.nn.ModuleList, RunLog, int]:
     """Train all SAEs of one parallel group on the same batches (train.py:238-462).
 
     ``train_pool`` optionally supplies an in-memory (n, d_model) activation pool instead of a shard dir; ``train_feed`` a
     ready loader-shaped object (e.g. data.ExtractionFeed: activations straight out of a transformer's forward hooks)."""
+    _require_topk(cfgs, "train")
     if len(split_cfgs(cfgs)) != 1:
         raise ValueError(f"Configs are not parallelizeable: {cfgs}.")
     cfg = cfgs[0]
@@ -409,6 +420,7 @@ def evaluate(cfgs: list[Config], saes: torch.nn.ModuleList, objs: torch.nn.Modul
              val_pool: Tensor | None = None) -> list[EvalMetrics]:
     """Eval-mode pass over the validation feed (train.py:510-618): fp64 baseline sums, SAE SSE, per-latent
     firing counts (f > 0) and value sums, dead / almost-dead (<1e-7) / dense (>1e-2) counts."""
+    _require_topk(cfgs, "evaluate")
     if len(split_cfgs(cfgs)) != 1:
         raise ValueError(f"Configs are not parallelizeable: {cfgs}.")
     saes.eval()

@@ -12,9 +12,10 @@ files move between the two unchanged:
 
 What differs: every compute method runs hand-written HIP kernels through libsaev_amd.so on the
 module's parameters, which are views into one flat device buffer owned by ``saev_amd.engine.SaeEngine``.
-There is no CPU implementation: calling a compute method on CPU tensors raises.  Only the TopK
-activation is on the accelerated path (BASELINE.json north_star); ``Relu`` and ``BatchTopK`` configs
-still parse and round-trip through checkpoints but raise ``NotImplementedError`` when run.
+There is no CPU implementation: calling a compute method on CPU tensors raises.  TopK SAEs train and
+run on the accelerated path (BASELINE.json north_star); ``Relu`` SAEs run their forward (``encode /
+decode / forward``, the inference pass) but do not train; ``BatchTopK`` configs still parse and
+round-trip through checkpoints but raise ``NotImplementedError`` when run.
 """
 
 from __future__ import annotations
@@ -136,18 +137,23 @@ class Output:
     """Forward outputs with the reference's field names (modeling.py:299-304).
 
     The HIP path keeps the k-sparse codes ``idx`` / ``val`` (batch, top_k); the dense ``h_x`` / ``f_x``
-    (batch, d_sae) matrices are materialised only when read."""
+    (batch, d_sae) matrices are materialised only when read.  A ReLU SAE's codes are padded rows: ``idx`` /
+    ``val`` (batch, cap) with ``row_nnz`` (batch) valid entries each (``SaeEngine.encode_relu``)."""
 
     def __init__(self, sae: "SparseAutoencoder", x: Tensor, idx: Tensor, val: Tensor, x_hats: Tensor | None,
-                 h_x: Tensor | None = None, prefixes: Tensor | None = None):
+                 h_x: Tensor | None = None, prefixes: Tensor | None = None, row_nnz: Tensor | None = None):
         self._sae, self._x, self.idx, self.val, self._x_hats = sae, x, idx, val, x_hats
         self._h_x, self._f_x, self.prefixes = h_x, None, prefixes
+        self.row_nnz = row_nnz
 
     @property
     def x_hats(self) -> Tensor:
         """(batch, n_prefixes, d_model); with Matryoshka prefixes the nested reconstructions are decoded on demand."""
         if self._x_hats is None:
-            self._x_hats = self._sae._eng().decode_sparse(self.idx, self.val, prefixes=self.prefixes)
+            if self.row_nnz is not None:
+                self._x_hats = self._sae._eng().decode_rows(self.idx, self.val, self.row_nnz, prefixes=self.prefixes)
+            else:
+                self._x_hats = self._sae._eng().decode_sparse(self.idx, self.val, prefixes=self.prefixes)
         return self._x_hats
 
     @property
@@ -159,7 +165,10 @@ class Output:
     @property
     def f_x(self) -> Tensor:
         if self._f_x is None:
-            self._f_x = self._sae._eng().scatter_dense(self.idx, self.val)
+            if self.row_nnz is not None:
+                self._f_x = self._sae._eng().scatter_rows(self.idx, self.val, self.row_nnz)
+            else:
+                self._f_x = self._sae._eng().scatter_dense(self.idx, self.val)
         return self._f_x
 
 
@@ -186,6 +195,21 @@ class TopKActivation(torch.nn.Module):
         return eng.scatter_dense(idx, val)
 
 
+class ReluActivation(torch.nn.Module):
+    """relu of dense pre-activations (modeling.py:150-156).  ``SparseAutoencoder`` itself never goes through this module for a
+    ReLU SAE: its encode / forward run the fused HIP encoder, which produces the positive entries without a dense h
+    (``SaeEngine.encode_relu``).  This module is the reference's standalone activation over a dense matrix the caller already
+    holds, an elementwise clamp."""
+
+    def __init__(self, cfg: Relu, sae: "SparseAutoencoder | None" = None):
+        super().__init__()
+        self.cfg = cfg
+        self.__dict__["_sae"] = sae  # not a submodule
+
+    def forward(self, x: Tensor) -> Tensor:
+        return torch.nn.functional.relu(x)
+
+
 class _Unsupported(torch.nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -193,7 +217,7 @@ class _Unsupported(torch.nn.Module):
 
     def forward(self, x):
         raise NotImplementedError(
-            f"{type(self.cfg).__name__} is outside the MI355X hot path (TopK only); the config is kept so "
+            f"{type(self.cfg).__name__} is outside the MI355X hot path (TopK, and the ReLU forward); the config is kept so "
             "sweeps/checkpoints parse.")
 
 
@@ -217,6 +241,8 @@ class SparseAutoencoder(torch.nn.Module):
         self.b_enc = torch.nn.Parameter(torch.zeros(cfg.d_sae))
         if isinstance(cfg.activation, TopK):
             self.activation = TopKActivation(cfg.activation, self)
+        elif isinstance(cfg.activation, Relu):
+            self.activation = ReluActivation(cfg.activation, self)
         else:
             self.activation = _Unsupported(cfg.activation)
         self.__dict__["_engine"] = None
@@ -225,6 +251,13 @@ class SparseAutoencoder(torch.nn.Module):
     # ---- engine binding ---------------------------------------------------------------------
     def _engine_cfg(self, max_batch: int, objective_cfg=None) -> EngineConfig:
         act = self.cfg.activation
+        if isinstance(act, Relu):
+            # forward only; the L1 coefficient of act.sparsity plays no part in it.  The engine's step entries raise.
+            return EngineConfig(
+                d_model=self.cfg.d_model, d_sae=self.cfg.d_sae, k_aux=0, alpha=0.0,
+                dead_threshold_tokens=getattr(self, "_dead_threshold_tokens", 10_000_000), normalize_w_dec=self.cfg.normalize_w_dec,
+                remove_parallel_grads=self.cfg.remove_parallel_grads, max_batch=max_batch, activation="relu",
+            )
         if not isinstance(act, TopK):
             raise NotImplementedError(f"{type(act).__name__} activation is not on the HIP path (TopK only)")
         if not isinstance(act.sparsity, NoSparsity):
@@ -288,6 +321,9 @@ class SparseAutoencoder(torch.nn.Module):
     # ---- reference API ----------------------------------------------------------------------
     def forward(self, x: Tensor) -> Output:
         eng = self._eng(x.shape[0])
+        if isinstance(self.cfg.activation, Relu):
+            idx, val, row_nnz = eng.encode_relu(x)
+            return Output(self, x, idx, val, eng.decode_rows(idx, val, row_nnz), row_nnz=row_nnz)
         eng.step_forward(x, training=False)
         idx, val, x_hat = eng.last_codes(x.shape[0])
         return Output(self, x, idx, val, x_hat[:, None, :])
@@ -295,12 +331,18 @@ class SparseAutoencoder(torch.nn.Module):
     def encode(self, x: Tensor) -> EncodeOut:
         eng = self._eng(x.shape[0])
         h_x = eng.encode_dense(x.reshape(-1, self.cfg.d_model))
-        f_x = self.activation(h_x)
+        if isinstance(self.cfg.activation, Relu):
+            f_x = eng.scatter_rows(*eng.encode_relu(x.reshape(-1, self.cfg.d_model)))
+        else:
+            f_x = self.activation(h_x)
         shape = (*x.shape[:-1], self.cfg.d_sae)
         return EncodeOut(h_x=h_x.reshape(shape), f_x=f_x.reshape(shape))
 
-    def encode_sparse(self, x: Tensor) -> tuple[Tensor, Tensor]:
-        """(idx, val) codes, (batch, top_k) each, without materialising the dense matrices."""
+    def encode_sparse(self, x: Tensor) -> tuple[Tensor, ...]:
+        """(idx, val) codes, (batch, top_k) each, without materialising the dense matrices.  ReLU: (idx, val, row_nnz), padded
+        rows of ascending latents (``SaeEngine.encode_relu``)."""
+        if isinstance(self.cfg.activation, Relu):
+            return self._eng(x.shape[0]).encode_relu(x)
         return self._eng(x.shape[0]).encode_topk(x)
 
     def decode(self, f_x: Tensor, *, prefixes: Tensor | None = None) -> Tensor:
@@ -467,7 +509,8 @@ def _config_fields(header: dict[str, tp.Any], where: str) -> dict[str, tp.Any]:
 def load(fpath: pathlib.Path | str, *, device="cpu") -> SparseAutoencoder:
     """Read an ``sae.pt``: schema 5 (what ``dump`` here and the reference's ``nn.dump`` write, modeling.py:548-574) and every
     older layout the reference's loader still reads (modeling.py:586-645; table above ``_config_fields``).  Only TopK
-    checkpoints run on the HIP path; ReLU / BatchTopK ones load (parameters and config) and raise when run."""
+    checkpoints train on the HIP path and ReLU ones run their forward; BatchTopK ones load (parameters and config) and raise
+    when run."""
     with open(fpath, "rb") as fd:
         first_line = fd.readline()
         payload = io.BytesIO(fd.read())
