@@ -305,7 +305,8 @@ int saev_step_forward(saev_ctx* ctx, const float* x, int32_t n_rows, int64_t n_r
 int saev_step_dead(saev_ctx* ctx, int64_t n_rows_global, void* stream);
 int saev_last_aux_route(const saev_ctx* ctx);
 /* Device memory the context itself owns, in bytes (the four flat buffers belong to the caller): which = 0 everything,
- * 1 the AuxK dead-set buffers (sized by saev_cfg.aux_dead_cap), 2 the Matryoshka gradient blocks (saev_set_prefixes). */
+ * 1 the AuxK dead-set buffers (sized by saev_cfg.aux_dead_cap), 2 the Matryoshka gradient blocks (saev_set_prefixes),
+ * 3 the Muon workspace (allocated by the first saev_muon_tail, saev_muon_workspace_bytes(d_model, d_sae)). */
 int64_t saev_scratch_bytes(const saev_ctx* ctx, int32_t which);
 int64_t saev_dead_readbacks(const saev_ctx* ctx);
 /* Phase 3: all four parameter gradients into the bound grad buffer (replaces autograd,
@@ -418,6 +419,38 @@ int saev_comm_world(const saev_ctx* ctx);   /* 0: no communicator */
 int saev_comm_destroy(saev_ctx* ctx);
 int saev_train_step_dp(saev_ctx* ctx, const float* x_local, int32_t n_local, float lr, float max_norm, int64_t adam_step,
                        void* stream);
+/* MUON (torch.optim.Muon, torch >= 2.9, with the reference's split: Muon on the two weight matrices, fused Adam on the biases).
+ * saev_muon_tail replaces saev_step_tail after the phases (saev_step_forward / _dead / _backward): remove_parallel_grads, the
+ * global-norm clip, Adam on b_dec / b_enc (adam_step counts the Adam steps, 1-based) and, for W_dec and W_enc:
+ *     m  <- lerp(m, g, 1 - momentum)                      fp32, bit-identical to torch's lerp_
+ *     u  =  lerp(g, m, momentum) (nesterov) or m
+ *     X  =  bf16(u) in the (d_model, d_sae) orientation (W_dec's is transposed), X /= clamp(bf16(||X||), eps) in bf16
+ *     ns_steps x:  G = X X^T;  U = b G + c G G;  X = a X + U X
+ *     p  <- p (1 - lr weight_decay) - adj_lr X (transposed back for W_dec)
+ * with adj_lr = lr sqrt(max(1, rows / cols)) (adjust_lr 0, torch's "original"), lr 0.2 sqrt(max(rows, cols)) (1,
+ * "match_rms_adamw") or lr (2).  The momentum lives in the W_dec / W_enc segments of the bound adam_m (their adam_v segments
+ * are not used).  Rounding of the Newton-Schulz products: fp32 accumulation, fp32 epilogue alpha acc + beta C, one rounding to
+ * bf16 per output element, as the vendor BLAS does for torch's bf16 addmm -- not bit-equal to torch, equal to an emulation
+ * that rounds at the same points within one bf16 ulp per product.  Split-K sums run in a fixed order: two runs, two ranks
+ * holding the same gradient, give identical bits.  Scratch (two bf16 (d_model, d_sae) matrices, two bf16 d_model^2, the
+ * split-K partials) is allocated by the first call.  The operand images of W_enc are invalidated internally, as
+ * saev_params_touched does: a Muon step never ends in SAEV_STALE_PARAMS.  saev_train_step / _gather / _dp run Adam only;
+ * data-parallel Muon goes through the phases with the gradient summed on every rank (grad_scale = 1 / world). */
+typedef struct {
+    float momentum, weight_decay, a, b, c, eps;
+    int32_t nesterov, ns_steps, adjust_lr;
+} saev_muon_cfg;
+/* torch's defaults: momentum 0.95, weight_decay 0.1, (a, b, c) = (3.4445, -4.7750, 2.0315), eps 1e-7, nesterov 1, 5 steps, "original" */
+void saev_muon_default_cfg(saev_muon_cfg* out);
+/* cfg NULL: the defaults */
+int saev_muon_tail(saev_ctx* ctx, float lr, float max_norm, float grad_scale, int64_t adam_step, const saev_muon_cfg* cfg,
+                   void* stream);
+/* Newton-Schulz alone, context-free: x_in / x_out are (rows, cols) bf16 row-major with rows <= cols (transpose a taller matrix
+ * first); normalize != 0 divides by the clamped bf16 norm first, as the tail does.  workspace: saev_muon_workspace_bytes(rows,
+ * cols) bytes of device memory, 256-byte aligned. */
+int64_t saev_muon_workspace_bytes(int64_t rows, int64_t cols);
+int saev_muon_newton_schulz(const void* x_in, int64_t rows, int64_t cols, void* x_out, const saev_muon_cfg* cfg, int32_t normalize,
+                            void* workspace, int64_t workspace_bytes, void* stream);
 /* PARAMETER OWNERSHIP.  With the f16r encoder the context keeps, from one call to the next, what its forward needs of W_enc
  * (fp16 operand images, a slice-major fp32 transpose, bias and norm shares: written by the Adam launch of saev_train_step, or by
  * the last forward that prepared them itself) and uses it for as long as only the library has written the parameter buffer.  A

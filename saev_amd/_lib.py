@@ -46,6 +46,13 @@ class SaevStepStats(C.Structure):
     ]
 
 
+class SaevMuonCfg(C.Structure):
+    """include/saev_amd.h: saev_muon_cfg (adjust_lr 0 = torch's "original", 1 = "match_rms_adamw", 2 = none)."""
+
+    _fields_ = [(n, C.c_float) for n in ("momentum", "weight_decay", "a", "b", "c", "eps")] + \
+               [(n, C.c_int32) for n in ("nesterov", "ns_steps", "adjust_lr")]
+
+
 class SaevError(RuntimeError):
     pass
 
@@ -106,6 +113,10 @@ _SIGNATURES = {
     "saev_train_step": (C.c_int, [P, P, C.c_int32, C.c_float, C.c_float, C.c_int64, P]),
     "saev_train_step_gather": (C.c_int, [P, P, P, P, C.c_int32, C.c_float, C.c_float, C.c_int64, P]),
     "saev_params_touched": (C.c_int, [P]),
+    "saev_muon_default_cfg": (None, [C.POINTER(SaevMuonCfg)]),
+    "saev_muon_tail": (C.c_int, [P, C.c_float, C.c_float, C.c_float, C.c_int64, C.POINTER(SaevMuonCfg), P]),
+    "saev_muon_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "saev_muon_newton_schulz": (C.c_int, [P, C.c_int64, C.c_int64, P, C.POINTER(SaevMuonCfg), C.c_int32, P, C.c_int64, P]),
     "saev_comm_unique_id": (C.c_int, [P]),
     "saev_comm_init": (C.c_int, [P, P, C.c_int32, C.c_int32]),
     "saev_comm_world": (C.c_int, [P]),

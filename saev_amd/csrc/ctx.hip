@@ -52,6 +52,8 @@ struct saev_ctx {
     // scratch
     std::vector<void*> allocs;
     size_t scratch_bytes = 0, aux_bytes = 0;  // device memory the context owns: per-step scratch, AuxK dead-set buffers
+    uint8_t* muon_ws = nullptr;  // Muon workspace (muon.hip: MuonLayout), allocated by the first saev_muon_tail
+    size_t muon_bytes = 0;
     int cuts_last[MAX_PREFIXES] = {0};  // the cut points the forward in flight used (the backward must see the same)
     int32_t *cand_cnt = nullptr, *gmax = nullptr, *cand_idx = nullptr;
     int gmax_stride = 0;
@@ -671,7 +673,8 @@ int saev_last_aux_route(const saev_ctx* c) { return c ? c->aux_route : -1; }
 int64_t saev_scratch_bytes(const saev_ctx* c, int32_t which) {
     if (!c) return -1;
     const size_t matry = (c->G ? (size_t)c->cfg.max_batch * c->P_cap * c->cfg.d_model * sizeof(float) : 0) * (c->GS ? 2 : 1);
-    return (int64_t)(which == 1 ? c->aux_bytes : which == 2 ? matry : c->scratch_bytes + c->aux_bytes + matry);
+    return (int64_t)(which == 1 ? c->aux_bytes : which == 2 ? matry : which == 3 ? c->muon_bytes
+                                                                      : c->scratch_bytes + c->aux_bytes + matry + c->muon_bytes);
 }
 int64_t saev_dead_readbacks(const saev_ctx* c) { return c ? c->n_readbacks : -1; }
 
@@ -2239,6 +2242,128 @@ int saev_params_touched(saev_ctx* c) {
     c->wimg_fresh = false;
     c->wimg_bf16_fresh = false;
     c->wn2_fresh = false;
+    return SAEV_OK;
+}
+
+// ---- Muon (include/saev_amd.h: MUON; kernels in muon.hip) -----------------------------------------------------------------
+void saev_muon_default_cfg(saev_muon_cfg* out) {
+    if (!out) return;
+    *out = saev_muon_cfg{0.95f, 0.1f, 3.4445f, -4.7750f, 2.0315f, 1e-7f, 1, 5, 0};
+}
+
+int64_t saev_muon_workspace_bytes(int64_t rows, int64_t cols) {
+    if (rows <= 0 || cols <= 0 || rows > cols || cols > (int64_t)1 << 30) return -1;
+    return (int64_t)muon_layout((int)rows, (int)cols).bytes;
+}
+
+namespace {
+int muon_cfg_check(const saev_muon_cfg& m, std::string* why) {
+    if (m.ns_steps < 0 || m.ns_steps >= 100) { *why = "ns_steps must be in [0, 100)"; return SAEV_INVALID_ARG; }
+    if (m.adjust_lr < 0 || m.adjust_lr > 2) { *why = "adjust_lr must be 0 (original), 1 (match_rms_adamw) or 2 (none)"; return SAEV_INVALID_ARG; }
+    if (!(m.momentum >= 0.f) || !(m.weight_decay >= 0.f)) { *why = "momentum and weight_decay must be >= 0"; return SAEV_INVALID_ARG; }
+    return SAEV_OK;
+}
+// the shortest decimal that rounds to f, as a double: the value a caller wrote (0.95, 0.1) when it came from a float field, so
+// that 1 - momentum and 1 - lr * weight_decay round as torch's Python-float arithmetic does
+double muon_dec(float f) {
+    char buf[32];
+    for (int p = 1; p <= 9; ++p) {
+        std::snprintf(buf, sizeof buf, "%.*g", p, (double)f);
+        const double d = std::strtod(buf, nullptr);
+        if ((float)d == f) return d;
+    }
+    return (double)f;
+}
+}  // namespace
+
+int saev_muon_newton_schulz(const void* x_in, int64_t rows, int64_t cols, void* x_out, const saev_muon_cfg* cfg, int32_t normalize,
+                            void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!x_in || !x_out || !workspace) return SAEV_INVALID_ARG;
+    const int64_t need = saev_muon_workspace_bytes(rows, cols);
+    if (need < 0 || workspace_bytes < need || ((uintptr_t)workspace & 255) != 0) return SAEV_INVALID_ARG;
+    saev_muon_cfg m;
+    saev_muon_default_cfg(&m);
+    if (cfg) m = *cfg;
+    std::string why;
+    if (muon_cfg_check(m, &why) != SAEV_OK) return SAEV_INVALID_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = (int)rows, S = (int)cols;
+    const MuonLayout L = muon_layout(D, S);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    // (the padding must be zero: the whole X buffer is cleared, then the caller's matrix is copied in)
+    if (hipMemsetAsync(ws + L.off_X[0], 0, (size_t)L.Dp * L.Sp * 2, s) != hipSuccess) return SAEV_HIP_ERROR;
+    if (launch_muon_load(static_cast<const uint16_t*>(x_in), D, S, reinterpret_cast<uint16_t*>(ws + L.off_X[0]), L.Sp,
+                         reinterpret_cast<double*>(ws + L.off_sq), s) != hipSuccess) return SAEV_HIP_ERROR;
+    hipError_t e = hipSuccess;
+    const int cur = muon_newton_schulz(ws, L, D, S, normalize, m.ns_steps, m.a, m.b, m.c, m.eps, s, &e);
+    if (cur < 0) return SAEV_HIP_ERROR;
+    if (hipMemcpy2DAsync(x_out, (size_t)S * 2, ws + L.off_X[cur], (size_t)L.Sp * 2, (size_t)S * 2, (size_t)D, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return SAEV_HIP_ERROR;
+    return SAEV_OK;
+}
+
+int saev_muon_tail(saev_ctx* c, float lr, float max_norm, float grad_scale, int64_t adam_step, const saev_muon_cfg* cfg, void* stream) {
+    if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_muon_tail: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->params && c->grads && c->adam_m && c->adam_v, SAEV_NOT_BOUND, "saev_muon_tail: params/grads/adam state not bound");
+    REQUIRE(c, adam_step >= 1, SAEV_INVALID_ARG, "adam_step is 1-based");
+    REQUIRE(c, !c->wenc_t_pending, SAEV_INVALID_ARG, "saev_muon_tail: runs after the phases, not inside saev_train_step");
+    saev_muon_cfg m;
+    saev_muon_default_cfg(&m);
+    if (cfg) m = *cfg;
+    {
+        std::string why;
+        const int rc = muon_cfg_check(m, &why);
+        REQUIRE(c, rc == SAEV_OK, rc, "saev_muon_tail: " + why);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int S = c->cfg.d_sae, D = c->cfg.d_model;
+    REQUIRE(c, D <= S, SAEV_UNSUPPORTED, "saev_muon_tail: d_model > d_sae");
+    const MuonLayout L = muon_layout(D, S);
+    if (c->muon_ws == nullptr) {
+        void* q = nullptr;
+        HIPCHK(c, hipMalloc(&q, L.bytes));
+        c->allocs.push_back(q);
+        c->muon_ws = static_cast<uint8_t*>(q);
+        c->muon_bytes = L.bytes;
+        // the padding of both X buffers stays zero from here on: the passes write [0, D) x [0, S) only, the products keep zeros
+        HIPCHK(c, hipMemsetAsync(c->muon_ws, 0, L.off_G, s));
+    }
+    // remove_parallel_grads in place and the clip norm's sum of squares (the generic route: Muon reads the projected gradient)
+    c->row_proj_valid = false;
+    int rc = saev_tail_prepare(c, -1, stream);
+    if (rc != SAEV_OK) return rc;
+    c->wn2_fresh = false; c->wimg_fresh = false; c->wimg_bf16_fresh = false; c->wchk_valid = false;  // (W_enc / W_dec move)
+    AdamArgs a{};
+    a.lr = lr; a.beta1 = 0.9f; a.beta2 = 0.999f; a.eps = 1e-8f;
+    a.omb1 = (float)(1.0 - 0.9); a.omb2 = (float)(1.0 - 0.999);
+    a.bc1 = (float)(1.0 - std::pow(0.9, (double)adam_step));
+    a.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(0.999, (double)adam_step));
+    a.grad_scale = grad_scale; a.max_norm = max_norm; a.sumsq = saev_sumsq_device(c); a.stats = c->stats;
+    const long off_b[2] = {c->off_b_dec, c->off_b_enc}, n_b[2] = {D, S};
+    for (int h = 0; h < 2; ++h) {
+        a.p = c->params + off_b[h]; a.g = c->grads + off_b[h]; a.m = c->adam_m + off_b[h]; a.v = c->adam_v + off_b[h]; a.n = n_b[h];
+        HIPCHK(c, launch_adam(a, s));
+    }
+    const double lr_d = muon_dec(lr);
+    const float decay = (float)(1.0 - lr_d * muon_dec(m.weight_decay));
+    for (int h = 0; h < 2; ++h) {  // W_dec (S, D), then W_enc (D, S)
+        const long off = h == 0 ? c->off_W_dec : c->off_W_enc;
+        const int trans = h == 0 ? 1 : 0;
+        const double rows = h == 0 ? S : D, cols = h == 0 ? D : S;
+        const double ratio = m.adjust_lr == 0 ? std::sqrt(std::max(1.0, rows / cols)) : m.adjust_lr == 1 ? 0.2 * std::sqrt(std::max(rows, cols)) : 1.0;
+        MuonMomArgs mo{};
+        mo.g = c->grads + off; mo.m = c->adam_m + off; mo.sumsq = saev_sumsq_device(c); mo.grad_scale = grad_scale; mo.max_norm = max_norm;
+        mo.w_buf = (float)(1.0 - muon_dec(m.momentum)); mo.mu = m.momentum; mo.nesterov = m.nesterov ? 1 : 0; mo.trans = trans;
+        mo.D = D; mo.S = S; mo.ldx = L.Sp; mo.X = reinterpret_cast<uint16_t*>(c->muon_ws + L.off_X[0]);
+        mo.sq_part = reinterpret_cast<double*>(c->muon_ws + L.off_sq);
+        HIPCHK(c, launch_muon_momentum(mo, s));
+        hipError_t e = hipSuccess;
+        const int cur = muon_newton_schulz(c->muon_ws, L, D, S, 1, m.ns_steps, m.a, m.b, m.c, m.eps, s, &e);
+        if (cur < 0) HIPCHK(c, e);
+        HIPCHK(c, launch_muon_apply(c->params + off, reinterpret_cast<const uint16_t*>(c->muon_ws + L.off_X[cur]), L.Sp, D, S, trans,
+                                    decay, (float)(lr_d * ratio), s));
+    }
     return SAEV_OK;
 }
 

@@ -714,3 +714,35 @@ struct ReluDecodeArgs {
 hipError_t launch_relu_decode(const ReluDecodeArgs& a, hipStream_t stream);
 hipError_t launch_relu_scatter(const int32_t* idx, const float* val, const int32_t* row_nnz, int row_cap, int n_rows, int S,
                                float* f_out, hipStream_t stream);
+
+// ---- Muon (muon.hip) ---------------------------------------------------------------------------------------------------
+// Rounding contract of the Newton-Schulz GEMMs: fp32 accumulation of bf16 products, the fp32 epilogue alpha * acc + beta * Cin,
+// one rounding to bf16 (nearest even) of each output element -- as the vendor BLAS does for torch's bf16 addmm.
+constexpr int MUON_MAX_SPLITS = 16;
+struct MuonLayout {      // one workspace for matrices of (D, S) (D <= S), padded to (Dp, Sp)
+    int Dp, Sp, nb;      // nb: per-workgroup squares the momentum / load pass leaves
+    int splits;          // split-K partials the workspace holds (Dp x Dp fp32 each)
+    size_t off_X[2], off_G, off_U, off_P, off_sq, off_nrm, bytes;
+};
+MuonLayout muon_layout(int D, int S);
+struct MuonMomArgs {
+    const float* g; float* m;     // gradient and momentum buffer of the parameter (source orientation)
+    const double* sumsq; float grad_scale, max_norm;  // clip coefficient exactly as the Adam kernels form it
+    float w_buf, mu;              // 1 - momentum (rounded once from double), momentum
+    int nesterov, trans;          // trans: the source is (S, D) row-major
+    int D, S, ldx;
+    uint16_t* X;                  // (Dp, Sp) bf16, written on [0, D) x [0, S)
+    double* sq_part;              // one per workgroup
+};
+hipError_t launch_muon_momentum(const MuonMomArgs& a, hipStream_t stream);
+hipError_t launch_muon_load(const uint16_t* src, int D, int S, uint16_t* X, int ldx, double* sq_part, hipStream_t stream);
+hipError_t launch_muon_apply(float* W, const uint16_t* X, int ldx, int D, int S, int trans, float decay, float adj_lr, hipStream_t stream);
+struct MuonGemmArgs {
+    const uint16_t* A; const uint16_t* B; const uint16_t* Cin; uint16_t* C; float* P;
+    int lda, ldb, ldc, M, N, K, kper, sym;
+    float alpha, beta;
+};
+// `steps` iterations on the normalised (normalize = 0) or raw (1: X /= clamp(bf16(||X||), eps) first, from the squares the
+// momentum / load pass left) X in workspace buffer 0; returns the buffer index that holds the result, -1 on a launch error
+int muon_newton_schulz(uint8_t* ws, const MuonLayout& L, int D, int S, int normalize, int steps, float a, float b, float c, float eps,
+                       hipStream_t stream, hipError_t* err);

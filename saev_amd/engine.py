@@ -91,6 +91,51 @@ class EngineConfig:
     activation: str = "topk"
 
 
+@dataclasses.dataclass(frozen=True)
+class MuonConfig:
+    """torch.optim.Muon's hyper-parameters (same names and defaults; lr is the per-step argument) -- include/saev_amd.h: MUON."""
+
+    weight_decay: float = 0.1
+    momentum: float = 0.95
+    nesterov: bool = True
+    ns_coefficients: tuple[float, float, float] = (3.4445, -4.7750, 2.0315)
+    eps: float = 1e-07
+    ns_steps: int = 5
+    adjust_lr_fn: str | None = None
+
+    def c_struct(self) -> "_lib.SaevMuonCfg":
+        adj = {None: 0, "original": 0, "match_rms_adamw": 1, "none": 2}
+        if self.adjust_lr_fn not in adj:
+            raise ValueError(f"adjust_lr_fn must be None, 'original' or 'match_rms_adamw', got {self.adjust_lr_fn!r}")
+        a, b, c = self.ns_coefficients
+        return _lib.SaevMuonCfg(momentum=self.momentum, weight_decay=self.weight_decay, a=a, b=b, c=c, eps=self.eps,
+                                nesterov=int(self.nesterov), ns_steps=self.ns_steps, adjust_lr=adj[self.adjust_lr_fn])
+
+
+def newton_schulz(x: torch.Tensor, muon: MuonConfig | None = None, *, normalize: bool = True) -> torch.Tensor:
+    """Newton-Schulz orthogonalisation of a 2-D device matrix on the HIP kernels of the Muon tail (torch's
+    ``_zeropower_via_newtonschulz``): bf16 in and out, a taller matrix is transposed as torch does.  ``normalize=False``
+    skips the division by the norm (the input is taken as already normalised)."""
+    if x.ndim != 2 or not x.is_cuda:
+        raise ValueError("newton_schulz takes a 2-D device matrix")
+    lib = _lib.load()
+    muon = muon or MuonConfig()
+    tall = x.shape[0] > x.shape[1]
+    xb = (x.t() if tall else x).to(torch.bfloat16).contiguous()
+    rows, cols = xb.shape
+    nbytes = int(lib.saev_muon_workspace_bytes(rows, cols))
+    if nbytes < 0:
+        raise _lib.SaevError(f"newton_schulz: unsupported shape {tuple(x.shape)}")
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    out = torch.empty_like(xb)
+    cfg = muon.c_struct()
+    with torch.cuda.device(x.device):
+        rc = lib.saev_muon_newton_schulz(_ptr(xb), rows, cols, _ptr(out), C.byref(cfg), int(normalize), _ptr(ws), nbytes, _stream())
+    if rc != 0:
+        raise _lib.SaevError(f"saev_muon_newton_schulz failed (status {rc})")
+    return out.t() if tall else out
+
+
 @dataclasses.dataclass
 class StepStats:
     mse: float
@@ -462,6 +507,22 @@ class SaeEngine:
         finally:
             if trusted:
                 self.lib.saev_trust_gradients(self.ctx, 0)
+
+    def muon_tail(self, lr: float, max_norm: float = 1.0, grad_scale: float = 1.0, muon: MuonConfig | None = None):
+        """The tail of a Muon step after the phases (saev_muon_tail): rpg, clip, Adam on the biases, Muon on W_dec / W_enc.
+        The momentum buffers are the W_dec / W_enc segments of ``adam_m``."""
+        self._topk_only("muon_tail")
+        cfg = (muon or MuonConfig()).c_struct()
+        self.adam_steps += 1
+        self._chk(self.lib.saev_muon_tail(self.ctx, lr, max_norm, grad_scale, self.adam_steps, C.byref(cfg), _stream()), "saev_muon_tail")
+
+    def train_step_muon(self, x: torch.Tensor, lr: float, max_norm: float = 1.0, muon: MuonConfig | None = None):
+        """One optimizer step with Muon on the weight matrices: the phases, then ``muon_tail``."""
+        n = x.shape[0]
+        self.step_forward(x, training=True, n_rows_global=n)
+        self.step_dead(n)
+        self.step_backward()
+        self.muon_tail(lr, max_norm, muon=muon)
 
     # ---- gathered backward (data-parallel runs that exchange the sparse step state instead of the gradient) -------------
     def gather_buffers(self, world: int, n_local: int):

@@ -194,7 +194,7 @@ class _SelfCheck:
 
 
 def choose_exchange(dist, world: int, rank: int, device, local_batch: int, *, tail: str = "auto", exchange: str = "auto",
-                    sparse_max_rows: int = 4096) -> tuple[str, str, dict]:
+                    sparse_max_rows: int = 4096, muon: bool = False) -> tuple[str, str, dict]:
     """Resolve ("auto" | explicit) tail / exchange settings into what a run uses, identically on every rank.
 
       exchange  "auto": the sparse step state when a rank holds at most ``sparse_max_rows`` rows (strong scaling: the
@@ -209,8 +209,14 @@ def choose_exchange(dist, world: int, rank: int, device, local_batch: int, *, ta
     all-reduce of a status flag; (2) step the all-reduce path and the candidate -- errors in here are not caught: a rank that
     fails between two collectives cannot be waited for, the process group's timeout / abort handling ends the job; (3) compare
     -- again a local verdict and one MIN all-reduce.  No rank ever enters a collective its peers may skip.
+    ``muon``: some SAE of the run trains with Muon, whose orthogonalisation needs the whole gradient on every rank -- the tail
+    is the replicated one ("auto" never picks the sharded tail, an explicit "sharded" raises ValueError).
     Returns (tail, exchange, report); the report says what was checked and why a fallback was taken."""
     report: dict = {"requested": {"tail": tail, "exchange": exchange}}
+    if muon:
+        if tail == "sharded":
+            raise ValueError("tail='sharded' cannot run Muon: its Newton-Schulz iteration needs the whole gradient on every rank")
+        tail = "replicated"
     if dist is None:
         return "replicated", "dense", report
     if world <= 1:  # one rank over a real backend (bench.py --force-dist): explicit choices run as they are, "auto" has nothing to check
@@ -309,8 +315,9 @@ def collective_busbw(dist, world: int, device, n_params: int, chunk_a: int, chun
 class DataParallelStepper:
     def __init__(self, engine, dist=None, world_size: int = 1, force: bool = False, overlap: bool | None = None,
                  n_buckets: int = 2, tail: str | None = None, rank: int | None = None, exchange: str | None = None,
-                 timeout_s: float | None = None):
-        """``force`` keeps the collective path even for one rank (exercises RCCL on a single-GPU box)."""
+                 timeout_s: float | None = None, muon=None):
+        """``force`` keeps the collective path even for one rank (exercises RCCL on a single-GPU box).  ``muon`` (an
+        engine.MuonConfig): the step ends in the Muon tail (SaeEngine.muon_tail) instead of Adam; it needs the replicated tail."""
         if exchange is None:
             exchange = os.environ.get("SAEV_AMD_DDP_EXCHANGE", "dense")
         if exchange not in ("dense", "sparse"):
@@ -327,6 +334,9 @@ class DataParallelStepper:
         if tail not in ("replicated", "sharded"):
             raise ValueError(f"tail must be 'replicated' or 'sharded', got {tail!r}")
         self.tail = tail if self.dist is not None else "replicated"
+        self.muon = muon
+        if muon is not None and self.tail == "sharded":
+            raise ValueError("tail='sharded' cannot run Muon: its Newton-Schulz iteration needs the whole gradient on every rank")
         self.rank = rank if rank is not None else (self.dist.get_rank() if self.dist is not None else 0)
         self._side = None
         self.exchange = exchange if self.dist is not None else "dense"
@@ -481,7 +491,13 @@ class DataParallelStepper:
         # The fused tail takes the clip norm and the projection from row statistics the backward left behind: only sound when
         # nothing wrote the gradient since.  A pre_tail hook is caller code (it may project or rescale eng.grads): with one,
         # the generic tail re-reads the gradient buffer as it now stands.
-        eng.step_tail(lr, max_norm, grad_scale=1.0 / w, trusted=pre_tail is None)
+        self._tail(lr, max_norm, 1.0 / w, trusted=pre_tail is None)
+
+    def _tail(self, lr: float, max_norm: float, grad_scale: float = 1.0, trusted: bool = False) -> None:
+        if self.muon is not None:
+            self.engine.muon_tail(lr, max_norm, grad_scale=grad_scale, muon=self.muon)
+        else:
+            self.engine.step_tail(lr, max_norm, grad_scale=grad_scale, trusted=trusted)
 
     def _check_same_route(self) -> None:
         """Debug (SAEV_AMD_DDP_CHECK=1): every rank must have made the same host-side AuxK decision -- route and compact-row
@@ -513,15 +529,16 @@ class DataParallelStepper:
     def _train_step(self, x_local: torch.Tensor, lr: float, max_norm: float, pre_tail) -> None:
         eng = self.engine
         if self.dist is None:
-            if pre_tail is None:
+            if pre_tail is None and self.muon is None:
                 eng.train_step(x_local, lr, max_norm)
                 return
             n = x_local.shape[0]
             eng.step_forward(x_local, training=True, n_rows_global=n)
             eng.step_dead(n)
             eng.step_backward()
-            pre_tail()
-            eng.step_tail(lr, max_norm)
+            if pre_tail is not None:
+                pre_tail()
+            self._tail(lr, max_norm)
             return
         if self.exchange == "sparse":
             self._step_sparse(x_local, lr, max_norm, pre_tail)
@@ -544,4 +561,4 @@ class DataParallelStepper:
             return
         if pre_tail is not None:
             pre_tail()
-        eng.step_tail(lr, max_norm, grad_scale=1.0 / self.world)
+        self._tail(lr, max_norm, 1.0 / self.world)

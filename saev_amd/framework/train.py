@@ -4,7 +4,8 @@ Kept from the reference: ``Config`` (same fields and defaults, train.py:50-105),
 (train.py:108-189), ``train`` (train.py:238-462), ``evaluate`` + ``EvalMetrics`` (train.py:465-618),
 ``split_cfgs`` (train.py:626-695), ``worker_fn`` (train.py:192-235) and the metric key names of the
 log block (train.py:419-432).  Step order is the reference's: renormalise decoder rows -> objective ->
-backward -> remove parallel grads -> clip -> (log) -> Adam with the lr set at the end of the previous
+backward -> remove parallel grads -> clip -> (log) -> Adam (or, optim="muon", Muon on W_dec / W_enc and Adam on the
+biases) with the lr set at the end of the previous
 step (first step lr = 0) -> scheduler step.
 
 Different by design: each SAE's step is ONE call into libsaev_amd.so (``saev_train_step``) instead of
@@ -35,6 +36,7 @@ from .. import nn
 from ..nn import modeling, objectives
 from ..utils import scheduling
 from ..utils.statistics import batch_entropy
+from ..engine import MuonConfig
 from .ddp import DataParallelStepper
 
 logger = logging.getLogger("train")
@@ -204,8 +206,11 @@ def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=No
     if cfg.device != "cuda" or not torch.cuda.is_available():
         raise RuntimeError("saev_amd trains on a HIP device only (Config.device must be 'cuda'); there is no CPU path")
     for c in cfgs:
-        if c.optim != "adam":
-            raise NotImplementedError("optim='muon' is outside the MI355X hot path (Adam only)")
+        if c.optim not in ("adam", "muon"):
+            raise ValueError(f"optim must be 'adam' or 'muon', got {c.optim!r}")
+    # Muon (train.py:284-306 of the reference): torch.optim.Muon's defaults on W_dec / W_enc, fused Adam on the biases, both
+    # groups on the same schedule -- one call into the library per step (SaeEngine.muon_tail) after the phases
+    muons = [MuonConfig() if c.optim == "muon" else None for c in cfgs]
     dist, rank, world = _dist()
     device = torch.device("cuda", torch.cuda.current_device())
 
@@ -233,9 +238,10 @@ def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=No
 
         tail_mode, exchange, report = choose_exchange(dist, world, rank, device, dataloader.local_batch,
                                                       tail=os.environ.get("SAEV_AMD_DDP_TAIL", "auto"),
-                                                      exchange=os.environ.get("SAEV_AMD_DDP_EXCHANGE", "auto"))
+                                                      exchange=os.environ.get("SAEV_AMD_DDP_EXCHANGE", "auto"),
+                                                      muon=any(m is not None for m in muons))
         logger.info("data-parallel exchange: tail=%s exchange=%s (%s)", tail_mode, exchange, report)
-    for sae, obj, c in zip(saes, objs, cfgs):
+    for sae, obj, c, mu in zip(saes, objs, cfgs, muons):
         if tail_mode == "sharded":
             sae._shard_world = world  # the engine lays its flat buffers out in `world` equal chunks per half
         if exchange == "sparse":
@@ -246,13 +252,13 @@ def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=No
             dist.broadcast(eng.params, src=0)
         if steppers:  # one batch feeds every SAE of the group (train.py:334-348): the first engine's x statistics,
             eng.share_x(steppers[0].engine)  # centring and operand images serve the others
-        steppers.append(DataParallelStepper(eng, dist, world, tail=tail_mode, exchange=exchange))
+        steppers.append(DataParallelStepper(eng, dist, world, tail=tail_mode, exchange=exchange, muon=mu))
         scheds.append(scheduling.WarmupCosine(0.0, c.n_lr_warmup, c.lr, len(limiter), 0.0))
         lrs.append(0.0)  # first optimizer step is pure warm-up (train.py:118)
     dataloader.engine = steppers[0].engine
     # One rank, a resident pool: the loader hands over (pool, row indices) and the first SAE's step draws the batch in its own
     # first kernel (SaeEngine.train_step_gather) -- no gather pass, and for a single SAE the streamed preparation of the step.
-    if world == 1 and hasattr(dataloader, "defer_gather"):
+    if world == 1 and hasattr(dataloader, "defer_gather") and muons[0] is None:
         dataloader.defer_gather = True
 
     global_step, n_patches_seen = 0, 0
