@@ -1,6 +1,6 @@
 """Headline benchmark: activations/sec of the TopK-SAE train step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): d_in = 1024, 32x expansion (d_sae = 32768), k = 32,
 batch 16384 activations per GPU, fp32, synthetic N(mu, 1) activations held in a device-resident pool
@@ -14,9 +14,21 @@ Timed region ("steady-state train step"): the loop first trains `-
 reference's dead-latent threshold of 10 M tokens = 611 of these steps, past the 500-step lr warm-up, and past the ~1 000 steps
 over which latent usage spreads and the gather kernels lose their L2 hits -- the step time is flat from there on), then runs the
 contract's W untimed warm-up steps and times exactly K steps.  `value` is therefore the step a training run spends its
-life in -- tracker consulted, AuxK on whatever is dead, latent usage spread over ~27 000 latents.  The first 5 + 20 steps
-from random init (what rounds 1-3 reported; ~18 % faster because 19 000 latents are still unused and AuxK is off) are
-timed on the way and reported as `from_random_init`.
+life in -- tracker consulted, AuxK on whatever is dead, latent usage spread over ~27 000 latents.
+
+A plain run does only that: set up, train the state-preparation steps, warm up, time the K steps, write `--dump-outputs`
+if asked, print the line.  `--full` adds every other measurement: all of them run after the timed steps except
+`from_random_init`, which only times steps a plain run trains as well, so the headline and the dumped arrays are the same
+with and without it:
+  "from_random_init": the first 5 + 20 state-preparation steps from random init (what rounds 1-3 reported; ~18 % faster
+                  because 19 000 latents are still unused and AuxK is off), timed on the way;
+  "sustained":    a 2 000-step segment of the same loop after the headline (`--sustained-steps` sets its length with or
+                  without --full);
+  "auxk_active", "other_configs", "data_regimes", "train_e2e", "sweep_group", "roofline.vendor_gemm": runs of their own;
+  "mse_rel_err_vs_oracle" and "cpu_baseline": the CPU oracle (below);
+  with N > 1:     "collectives": RCCL bus bandwidth of the step's own collectives at their real sizes.
+The --no-* options leave single ones of these out of a --full run.  A --full run takes a minute or two, most of it the CPU
+baseline.
 
 Prints ONE JSON line on rank 0 (contract in the task description), including
   "roofline":     the encoder's first-pass MFMA kernel: achieved TFLOP/s = algorithmic 2*B*D*S flops / mean kernel
@@ -26,10 +38,9 @@ Prints ONE JSON line on rank 0 (contract in the task description), including
                   against the dense f16 MFMA peak (2.5 PFLOP/s); --encoder f16x3 (three products per fp32 product)
                   reports `executed_tflops` = 3x beside it; --encoder f32 is priced against the 157.3 TFLOP/s fp32
                   matrix peak;
-  "cpu_baseline": the CPU oracle (oracle/sae_ref.py, a restatement of the reference's PyTorch-CPU
+  with --full:    "cpu_baseline": the CPU oracle (oracle/sae_ref.py, a restatement of the reference's PyTorch-CPU
                   step) timed on this box's host cores as BASELINE.md section 3 prescribes: all cores and 8 threads,
-                  one warm-up + five timed steps each (~110 s of CPU work together);
-  with N > 1:     "collectives": RCCL bus bandwidth of the step's own collectives at their real sizes.
+                  one warm-up + five timed steps each (~110 s of CPU work together).
 """
 
 import argparse
@@ -406,6 +417,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement of the line (from_random_init, sustained, auxk_active, "
+                         "other_configs, vendor_gemm, data_regimes, train_e2e, sweep_group, the oracle MSE check and cpu_baseline; "
+                         "collectives with N > 1); the --no-* options below leave single ones out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--encoder", choices=["f32", "f16x3", "bf16", "f16r"], default=None, help="encoder arithmetic (default: engine default)")
@@ -432,9 +447,10 @@ def main():
                          "is the steady-state step: past the 10 M-token dead-latent threshold (611 steps), the lr warm-up (500) and "
                          "the ~1 000 steps over which latent usage keeps spreading and the step keeps slowing down "
                          "(tools/experiments/long_run_probe.py: 2.8 ms at step 100, 3.07 at 700, 3.25-3.35 from 1 200 to 8 000); the "
-                         "first 5 + 20 of them are timed as `from_random_init`.  0 = time from random init (rounds 1-3)")
-    ap.add_argument("--sustained-steps", type=int, default=2000,
-                    help="length of a long segment timed after the headline steps (0 = skip): the same loop, continued")
+                         "first 5 + 20 of them are timed as `from_random_init` with --full.  0 = time from random init (rounds 1-3)")
+    ap.add_argument("--sustained-steps", type=int, default=None,
+                    help="length of a long segment timed after the headline steps (0 = skip): the same loop, continued "
+                         "(default: 2000 with --full, else 0)")
     ap.add_argument("--sustained-after", type=int, default=0, help="further untimed steps between the headline and that segment")
     ap.add_argument("--no-auxk-probe", action="store_true", help="skip the AuxK-active sub-records (forced dead sets)")
     ap.add_argument("--no-other-configs", action="store_true",
@@ -462,6 +478,10 @@ def main():
     if toy:
         D_MODEL, D_SAE, TOP_K = (int(v) for v in args.shape.split(","))
         args.no_other_configs = args.no_extras = args.no_auxk_probe = args.no_cpu_baseline = True
+    if args.sustained_steps is None:
+        args.sustained_steps = 2000 if args.full else 0
+    if not args.full:  # a plain run: the headline alone
+        args.no_other_configs = args.no_extras = args.no_auxk_probe = args.no_cpu_baseline = args.no_busbw = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -572,7 +592,7 @@ def main():
     step_i = 0
     early = None
     if args.pretrain_steps > 0:
-        n_w, n_t = min(5, args.pretrain_steps), min(20, max(0, args.pretrain_steps - 5))
+        n_w, n_t = min(5, args.pretrain_steps), min(20, max(0, args.pretrain_steps - 5)) if args.full else 0
         for i in range(n_w):
             one_step(i)
         step_i = n_w
@@ -753,7 +773,7 @@ def main():
                              "n_dead_last": stats.n_dead, "aux_route_last": aux_route_timed,
                              "note": (f"value = {args.steps} steps after {args.warmup} warm-up steps, both AFTER {args.pretrain_steps} training steps "
                                       "from random init (state preparation: past the dead-latent threshold and the lr warm-up) -- the "
-                                      "steady-state train step of SURVEY.md 8d; `from_random_init` has the early-training figure"
+                                      "steady-state train step of SURVEY.md 8d; with --full, `from_random_init` has the early-training figure"
                                       if args.pretrain_steps > 0 else
                                       f"value = {args.steps} steps after {args.warmup} warm-up steps from random init (--pretrain-steps 0)")},
         }

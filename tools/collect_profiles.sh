@@ -19,4 +19,4 @@ done
 python tools/pmc_summary.py $W "$OUT/${TAG}_pmc.txt" "$OUT/${TAG}_encoder_traffic.json" "$TAG"
 # the bench line last, so that its roofline block can cite the traffic file just written (bench.py reads profiles/)
 mkdir -p profiles && cp "$OUT/${TAG}_encoder_traffic.json" profiles/r06_encoder_traffic.json 2>/dev/null
-python bench.py 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_line.json"
+python bench.py --full 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_line.json"
