@@ -451,6 +451,32 @@ int saev_muon_tail(saev_ctx* ctx, float lr, float max_norm, float grad_scale, in
 int64_t saev_muon_workspace_bytes(int64_t rows, int64_t cols);
 int saev_muon_newton_schulz(const void* x_in, int64_t rows, int64_t cols, void* x_out, const saev_muon_cfg* cfg, int32_t normalize,
                             void* workspace, int64_t workspace_bytes, void* stream);
+/* COHERENCE (the log block's metrics/dictionary_coherence, train.py:409-414), context-free.  W is (S, D) fp32 row-major, 16-byte
+ * aligned, 1 <= S <= 2^20, 4 <= D <= 4096, D % 4 == 0.  The value is the reference expression
+ *     (W_n @ W_n.T).abs().triu(1).max(),   W_n = W / W.norm(dim=1, keepdim=True)
+ * with each row divided in fp32 by its fp32 norm: the max of |c_ij| over i < j and the pair (i, j) that attains it, ties to the
+ * lexicographically smallest pair.  S = 1: 0.0 and the pair (-1, -1).  A row whose normalised form is not finite (a zero row,
+ * an inf or NaN entry): NaN, as torch's max propagates it, with the smallest pair that holds the first such row.
+ * route SAEV_COH_AUTO: an fp16 MFMA pass over the upper-triangle tiles of the fp16 images h_i = fp16(2^13 w_i / n_i) bounds every
+ * pair: |c~_ij - c_ij| <= E_ij = 1.02 (||d_i|| ||w^_j|| + ||w^_i|| ||d_j|| + ||d_i|| ||d_j|| + 2.1 Dp 2^-22 (||w^_i|| + ||d_i||)
+ * (||w^_j|| + ||d_j||)), with w^_i = w_i / n_i, d_i = w^_i - 2^-13 h_i measured on the values the MFMA consumes (fp16 subnormals
+ * are flushed in the image) and Dp = D rounded up to 64 -- Cauchy-Schwarz on the rounding errors plus the fp32 accumulation of
+ * the filter and of the exact value.  With L = max over pairs of |c~| - E, every pair with |c~| + E >= L is a candidate: the
+ * maximiser p has |c~_p| + E_p >= c_p = max >= L, so it is always one.  A second pass over the tiles that can hold such a pair
+ * writes the list; each candidate is then recomputed exactly: the fp32 dot product of the fp32 rows w^, in a fixed k order.
+ * Value and pair are bit-reproducible from call to call.  List capacity: min(2^20, S (S - 1) / 2) pairs.  OVERFLOW is never
+ * silent: if more pairs qualify, the call answers on the exact route instead.  route SAEV_COH_EXACT forces that route: fp32 MFMA
+ * (v_mfma_f32_32x32x2_f32) of the rows w^ over the whole upper triangle, the max taken with the same tie rule.
+ * Results are written on the device, nothing is read back: *out_value, out_pair[2] = (i, j), out_info[4] = {route taken
+ * (SAEV_COH_FILTERED / _EXACT / _OVERFLOW), candidates found (may exceed the capacity), tiles the second pass recomputed,
+ * capacity}.  workspace: saev_coherence_workspace_bytes(S, D) bytes of device memory, 256-byte aligned (-1: unsupported shape). */
+#define SAEV_COH_AUTO 0
+#define SAEV_COH_EXACT 1
+#define SAEV_COH_FILTERED 0   /* route taken: fp16 filter and exact refinement */
+#define SAEV_COH_OVERFLOW 2   /* route taken: the list overflowed, the exact route answered */
+int64_t saev_coherence_workspace_bytes(int64_t S, int64_t D);
+int saev_dictionary_coherence(const float* W, int64_t S, int64_t D, int32_t route, void* workspace, int64_t workspace_bytes,
+                              float* out_value, int32_t* out_pair, int32_t* out_info, void* stream);
 /* PARAMETER OWNERSHIP.  With the f16r encoder the context keeps, from one call to the next, what its forward needs of W_enc
  * (fp16 operand images, a slice-major fp32 transpose, bias and norm shares: written by the Adam launch of saev_train_step, or by
  * the last forward that prepared them itself) and uses it for as long as only the library has written the parameter buffer.  A

@@ -117,6 +117,8 @@ _SIGNATURES = {
     "saev_muon_tail": (C.c_int, [P, C.c_float, C.c_float, C.c_float, C.c_int64, C.POINTER(SaevMuonCfg), P]),
     "saev_muon_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "saev_muon_newton_schulz": (C.c_int, [P, C.c_int64, C.c_int64, P, C.POINTER(SaevMuonCfg), C.c_int32, P, C.c_int64, P]),
+    "saev_coherence_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "saev_dictionary_coherence": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int32, P, C.c_int64, P, P, P, P]),
     "saev_comm_unique_id": (C.c_int, [P]),
     "saev_comm_init": (C.c_int, [P, P, C.c_int32, C.c_int32]),
     "saev_comm_world": (C.c_int, [P]),

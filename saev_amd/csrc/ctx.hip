@@ -2302,6 +2302,25 @@ int saev_muon_newton_schulz(const void* x_in, int64_t rows, int64_t cols, void* 
     return SAEV_OK;
 }
 
+// ---- dictionary coherence (include/saev_amd.h: COHERENCE; kernels in coherence.hip) ---------------------------------------
+int64_t saev_coherence_workspace_bytes(int64_t S, int64_t D) {
+    if (S < 1 || S > ((int64_t)1 << 20) || D < 4 || D > 4096 || D % 4 != 0) return -1;
+    return (int64_t)coherence_layout((int)S, (int)D).bytes;
+}
+
+int saev_dictionary_coherence(const float* W, int64_t S, int64_t D, int32_t route, void* workspace, int64_t workspace_bytes,
+                              float* out_value, int32_t* out_pair, int32_t* out_info, void* stream) {
+    const int64_t need = saev_coherence_workspace_bytes(S, D);
+    if (need < 0 || (route != SAEV_COH_AUTO && route != SAEV_COH_EXACT)) return SAEV_INVALID_ARG;
+    if (!W || !workspace || !out_value || !out_pair || !out_info) return SAEV_INVALID_ARG;
+    if (workspace_bytes < need || ((uintptr_t)workspace & 255) != 0 || ((uintptr_t)W & 15) != 0) return SAEV_INVALID_ARG;
+    const CohLayout L = coherence_layout((int)S, (int)D);
+    if (launch_coherence(W, (int)S, (int)D, route, static_cast<uint8_t*>(workspace), L, out_value, out_pair, out_info,
+                         (hipStream_t)stream) != hipSuccess)
+        return SAEV_HIP_ERROR;
+    return SAEV_OK;
+}
+
 int saev_muon_tail(saev_ctx* c, float lr, float max_norm, float grad_scale, int64_t adam_step, const saev_muon_cfg* cfg, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
     REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_muon_tail: a ReLU context runs the forward entries only");

@@ -746,3 +746,15 @@ struct MuonGemmArgs {
 // momentum / load pass left) X in workspace buffer 0; returns the buffer index that holds the result, -1 on a launch error
 int muon_newton_schulz(uint8_t* ws, const MuonLayout& L, int D, int S, int normalize, int steps, float a, float b, float c, float eps,
                        hipStream_t stream, hipError_t* err);
+
+// ---- Dictionary coherence (coherence.hip) ----------------------------------------------------------------------------------
+constexpr long COH_MAX_CANDIDATES = 1L << 20;  // list capacity: min(this, S (S - 1) / 2) pairs
+struct CohLayout {       // one workspace for an (S, D) matrix: image padded to (Sp, Dp) = multiples of (128, 64)
+    int Sp, Dp, nT, cap; // nT: tile rows; cap: candidate list capacity
+    long ntiles;         // upper-triangle tiles, nT (nT + 1) / 2
+    size_t off_ctl, off_nrm, off_rn, off_img, off_hi, off_best, off_cand, off_val, bytes;
+};
+CohLayout coherence_layout(int S, int D);
+// route: SAEV_COH_AUTO / SAEV_COH_EXACT; results written on the device, nothing read back
+hipError_t launch_coherence(const float* W, int S, int D, int route, uint8_t* ws, const CohLayout& L, float* out_value,
+                            int32_t* out_pair, int32_t* out_info, hipStream_t stream);

@@ -136,6 +136,58 @@ def newton_schulz(x: torch.Tensor, muon: MuonConfig | None = None, *, normalize:
     return out.t() if tall else out
 
 
+@dataclasses.dataclass(frozen=True)
+class CoherenceResult:
+    """max_{i<j} |<w_i, w_j>| over the unit-normalised rows and the pair i < j that attains it (ties: the lexicographically
+    smallest).  route: "filter" (fp16 filter + exact fp32 refinement) or "exact" (fp32 over every pair: asked for, or
+    ``overflow`` -- more candidates than the list holds, ``candidates`` of ``capacity``)."""
+
+    value: float
+    i: int
+    j: int
+    route: str
+    candidates: int = 0
+    capacity: int = 0
+    overflow: bool = False
+    tiles_refiltered: int = 0  # 128 x 128 tiles the filter's second pass recomputed
+
+
+_COHERENCE_ROUTES = {"auto": 0, "exact": 1}
+
+
+def dictionary_coherence(W: torch.Tensor, *, route: str = "auto") -> CoherenceResult:
+    """The log block's dictionary coherence (reference train.py:409-414), ``(W_n @ W_n.T).abs().triu(1).max()`` with
+    ``W_n = W / W.norm(dim=1, keepdim=True)``, on the HIP kernels of saev_dictionary_coherence (include/saev_amd.h: COHERENCE):
+    no S x S matrix, one read-back.  W: (S, D) float32 on a HIP device, D % 4 == 0, D <= 4096.  S = 1 gives 0.0 and the pair
+    (-1, -1); a zero or non-finite row gives NaN.  ``route="exact"`` forces the fp32 route over every pair (A/B runs)."""
+    if route not in _COHERENCE_ROUTES:
+        raise ValueError(f"route must be one of {sorted(_COHERENCE_ROUTES)}, got {route!r}")
+    if W.ndim != 2:
+        raise ValueError(f"dictionary_coherence takes an (S, D) matrix, got shape {tuple(W.shape)}")
+    lib = _lib.load()
+    S, D = W.shape
+    nbytes = int(lib.saev_coherence_workspace_bytes(S, D))
+    if nbytes < 0:
+        raise ValueError(f"dictionary_coherence: unsupported shape {(S, D)} (1 <= S <= 2**20, 4 <= D <= 4096, D % 4 == 0)")
+    if not W.is_cuda or W.dtype != torch.float32:
+        raise ValueError("dictionary_coherence takes a float32 device matrix")
+    W = W.contiguous()
+    if W.data_ptr() % 16:
+        W = W.clone()
+    ws = torch.empty(nbytes, device=W.device, dtype=torch.uint8)
+    res = torch.empty(8, device=W.device, dtype=torch.int32)  # value bits | i, j | route, candidates, tiles, capacity
+    with torch.cuda.device(W.device):
+        rc = lib.saev_dictionary_coherence(_ptr(W), S, D, _COHERENCE_ROUTES[route], _ptr(ws), nbytes, _ptr(res), _ptr(res[1:]),
+                                           _ptr(res[3:]), _stream())
+    if rc != 0:
+        raise _lib.SaevError(f"saev_dictionary_coherence failed (status {rc})")
+    h = res.cpu()
+    value = h[:1].view(torch.float32).item()
+    i, j, code, cand, tiles, cap = h[1:7].tolist()
+    return CoherenceResult(value=value, i=i, j=j, route="filter" if code == 0 else "exact", candidates=cand, capacity=cap,
+                           overflow=code == 2, tiles_refiltered=tiles)
+
+
 @dataclasses.dataclass
 class StepStats:
     mse: float
