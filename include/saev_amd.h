@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SAEV_AMD_ABI_VERSION 11
+#define SAEV_AMD_ABI_VERSION 12
 
 typedef enum {
     SAEV_OK = 0,
@@ -144,22 +144,12 @@ typedef struct {
     int32_t dw_route;      /* weight gradients: 0 column slices out of the XCD L2s where the geometry allows, with the products
                               dval = <dL/dx_hat row, decoder row> left by the decode where the shape allows (top_k <= 32,
                               d_model 256 / 512 / 768 / 1024); 1 whole-row gathers (dw_rows) always; 2 column slices with dval
-                              formed by their first pass (the only form for other shapes and for gathered backwards); 4 as 0, but
-                              the decode itself gathers 32-column slices of W_dec out of the XCD L2s (a wash: DESIGN.md 3.3)  */
-    int32_t enc_mfma;      /* single-product encoders: 0 v_mfma_f32_16x16x32 kernel, 32 the 32x32x16 kernel               */
-    int32_t fused_chain;   /* f16r: 1 = survivor select, exact refinement and final select as ONE launch                  */
-    int32_t ngroups;       /* TopK bound groups of the fp16-image encoders: 0 = 32 for top_k <= 32 (64 above), 64 forces
-                              the 64-group bound                                                                          */
-    int32_t enc_wgs;       /* workgroups the fused encoder's grid aims at (0 = 256, one per CU)                           */
-    int32_t refresh_first; /* bound refresh on a workgroup's first N tiles (0 = 8) ...                                    */
-    int32_t refresh_every; /* ... then on every M-th, M a power of two (0 = 2; the 64-group bound defaults to 1)          */
+                              formed by their first pass (the only form for other shapes and for gathered backwards)              */
     int32_t aux_small_max; /* largest dead set the few-dead-latents AuxK kernels take: 0 = 128 where d_model % 128 == 0 (fp32-MFMA kernels; 64 with aux_wide_route = 1), else 40; -1 = never (dense algebra
                               whatever the count); values above 64 are clamped                                           */
     int32_t fwd_route;     /* exact refinement of the f16r encoder: 0 = from 32-column slices of W_enc^T that the XCD L2s hold
                               where the geometry allows (their D / 32 shares per survivor added by the final select), 1 = whole-row
-                              gathers always, 2 = slices with a separate pass that adds the shares (round 4)              */
-    int32_t dead_lag;      /* saev_step_dead sizes the auxiliary work from the tracker record of this many steps ago
-                              (0 = 4, at most 8): shorter = tighter bound of the dead count, longer = more host run-ahead  */
+                              gathers always                                                                              */
     int32_t csc_route;     /* latent-major pair list of the backward: 0 = the training decode sets the (latent, row) bits of the
                               build's bit map while it holds the codes, 1 = the build's own fill pass always, 2 = as 0 with the
                               round-4 scan (two launches) instead of the single look-back scan                               */
@@ -175,10 +165,6 @@ typedef struct {
                               absmax, scale: six launches)                                                                    */
     int32_t aux_small_route; /* 9 ... 64 dead latents (and 1 ... 8 where the one-pass kernel does not take the shape), d_model % 128 == 0:
                               0 = the contractions as fp32 MFMA tiles (v_mfma_f32_32x32x2_f32), 1 = the vector-ALU kernels of rounds 3-4 */
-    int32_t own_check;     /* PARAMETER OWNERSHIP, check (2): 0 = the fused Adam leaves / compares tile checksums of W_enc, 1 = off
-                              (A/B measurements of the Adam launch only)                                                     */
-    int32_t enc_rot;       /* fused encoder: 0 = the workgroups of an XCD that share a W_enc tile walk its k-steps rotated by one
-                              step each, 1 = in lock step (same order: the tile's images are read by all of them at once)     */
     int32_t group_route;   /* several SAEs on the same batches (saev_share_x): 0 = the lender streams its preparation like a context on
                               its own and every member's fused Adam leaves its own W_enc images (from the third step of a group nobody
                               prepares anything from scratch), 1 = round 5: every member prepares from scratch on every step        */

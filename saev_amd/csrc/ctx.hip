@@ -113,11 +113,6 @@ struct saev_ctx {
     float* sq_wave = nullptr;  // per-wave squares of the two passes (DwSlicesArgs::sq_wave_dec, then _enc: contiguous)
     int sq_wave_n = 0;         // > 0: the backward in flight left 2 x this many of them (the tail adds them to the clip norm)
     bool wn2_fresh = false;  // wn2 describes W_dec as it is now (set by the training forward, cleared by whatever writes W_dec)
-    // the decode out of 32-column slices (sparse.hip: decode_s_kernel): slice-major copy of the normalised W_dec left by the step's
-    // normalize_rows, per (slice, row) loss terms; the dval shares go through dvp
-    float* WdS = nullptr;
-    double* dec_part = nullptr;
-    bool wds_fresh = false;  // WdS describes W_dec as it is now (this step's normalize_rows wrote both)
     bool dval_pairs_ready = false;  // the CSC build of this backward has written pv2 from it
     bool fused_forward = false;     // saev_train_step's forward: Matryoshka G blocks past the first are not needed row-major
     // exact refinement of the f16r encoder from 32-column slices (select.hip: refine_slices_kernel): split_f16r leaves x and
@@ -291,18 +286,15 @@ int alloc(saev_ctx* c, T** p, size_t count) {
     return SAEV_OK;
 }
 
-// TopK bound of the fp16-image encoders: the minimum over 32 group maxima for top_k <= 32; 64 groups with the top_k-th
-// largest of the group maxima for 32 < top_k <= 64.  saev_debug_cfg.ngroups = 64 forces the second variant for small k as well: it
-// cuts the candidates per row from ~980 to ~360 at config 2, but its bound phase (32 published maxima per lane, a
-// bisection over packed 16-bit keys) costs more than the shorter lists save (encoder 1.43-1.51 vs 1.35-1.38 ms).
 // {x scale, W scale, x scale, 1, square normaliser, -, -, -} of the step in flight / of the next one (streamed f16r step)
 float* scl(const saev_ctx* c) { return c->f16r_scales + 8 * c->scale_par; }
 float* scl_next(const saev_ctx* c) { return c->f16r_scales + 8 * (c->scale_par ^ 1); }
 
-int f16_ngroups(const saev_ctx* c) {
-    if (c->cfg.top_k > 32 || c->dbg.ngroups == 64) return 64;
-    return 32;
-}
+// TopK bound of the fp16-image encoders: the minimum over 32 group maxima for top_k <= 32; 64 groups with the top_k-th
+// largest of the group maxima for 32 < top_k <= 64.  The second variant for small k as well cut the candidates per row from
+// ~980 to ~360 at config 2, but its bound phase (32 published maxima per lane, a bisection over packed 16-bit keys) cost more
+// than the shorter lists saved (encoder 1.43-1.51 vs 1.35-1.38 ms).
+int f16_ngroups(const saev_ctx* c) { return c->cfg.top_k > 32 ? 64 : 32; }
 
 int encoder_splits(int n_rows, int S, int tile_rows, int tile_latents, int target_wgs) {
     const int nb = (n_rows + tile_rows - 1) / tile_rows;
@@ -427,7 +419,7 @@ int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, s
         c->dws_ok = !rows_only && D % DWS_SLICE == 0 && (uint64_t)S * D * 4ull < (1ull << 32) && MBB < (1l << 24) &&
                     (uint64_t)MBB * K < (1ull << 31);
     }
-    c->fwd_slices = c->cfg.encoder_mode == SAEV_ENCODER_F16R && (c->dbg.fwd_route == 0 || c->dbg.fwd_route == 2) && c->dbg.fused_chain == 0 && D % RS_SLICE == 0 &&
+    c->fwd_slices = c->cfg.encoder_mode == SAEV_ENCODER_F16R && c->dbg.fwd_route == 0 && D % RS_SLICE == 0 &&
                     (uint64_t)S * 128ull < (1ull << 32) - 256ull && fused_supported(c->cfg);
     if (c->fwd_slices) {
         A(rs_part, (size_t)(D / RS_SLICE) * MB * REFINE_CAP); A(surv_rng, MB * RS_MAX_RANGES);
@@ -439,10 +431,7 @@ int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, s
     if (c->fwd_slices && !c->dws_ok) A(xS, MBB * D);
     if (c->dws_ok) {
         A(gS, MBB * D); A(xS, MBB * D); A(dvp, (size_t)(D / DWS_SLICE) * MBB * K);
-        if (c->dbg.dw_route != 2 && decode_forms_dval((int)D, (int)K)) A(dval_rows, MB * K);  // (routes 0, 4: dval from the decode)
-        if (c->dval_rows != nullptr && c->dbg.dw_route == 4 && decode_slices_supported((int)D, (int)S, (int)K, (int)K) && c->cfg.normalize_w_dec) {
-            A(WdS, S * D); A(dec_part, (size_t)(D / 32) * MB * 3);
-        }
+        if (c->dbg.dw_route != 2 && decode_forms_dval((int)D, (int)K)) A(dval_rows, MB * K);  // (route 0: dval from the decode)
         A(pv, MBB * K); A(pv2, MBB * K); A(plat, MBB * K); A(cut_lat, (MBB * K + DWS_RUN - 1) / DWS_RUN); A(cut_list, 4 * (1 + (MBB * K + DWS_RUN - 1) / DWS_RUN)); A(lat_unused, S);
         if (c->dval_rows != nullptr && c->dbg.fin_route == 0) { A(wn2, S); A(sq_wave, (size_t)2 * dw_slices_waves((int)D, (int)(MBB * K))); }
     }
@@ -870,24 +859,17 @@ static int run_encoder(saev_ctx* c, const float* x, int n, int epi, float* h_out
         a.scale_dev = f16r ? scl(c) : nullptr;
         a.arith = bf ? 1 : (f16r ? 2 : 0);
         a.row_margin = f16r ? c->row_margin : nullptr;
-        const int enc_wgs = c->dbg.enc_wgs > 0 ? c->dbg.enc_wgs : 256;
-        a.mfma32 = c->dbg.enc_mfma == 32 ? 1 : 0;
-        a.s_splits = encoder_splits(n, a.S, encode_f16x3_tile_rows(), encode_f16x3_tile_latents(), enc_wgs);
-        a.no_rot = c->dbg.enc_rot == 1 ? 1 : 0;
+        a.s_splits = encoder_splits(n, a.S, encode_f16x3_tile_rows(), encode_f16x3_tile_latents(), 256);  // (one workgroup per CU)
         a.h_out = h_out;
         a.ngroups = f16_ngroups(c); a.top_k = c->cfg.top_k;
         a.gmax = c->gmax; a.gmax_stride = c->gmax_stride; a.cand_cnt = c->cand_cnt; a.cand_val = c->cand_val; a.cand_idx = c->cand_idx;
         a.cand_cap = CAND_CAP; a.cand_stride = CAND_STRIDE;
         a.enable_flag = flag; a.enable_when = when;
         if (predicted) { a.heur_z = c->heur_state; a.tau_max = c->tau_max; }
-        {
-            const int rf = c->dbg.refresh_first > 0 ? c->dbg.refresh_first : 8, re = c->dbg.refresh_every;
-            a.refresh_first = std::max(1, rf);
-            a.refresh_every = (re >= 1 && (re & (re - 1)) == 0) ? re : 2;
-            // the 64-group variant (32 < k <= 64, e.g. 82 k latents at k = 64) refreshes on every tile: with twice the codes
-            // per row and many more tiles per workgroup its lists would outgrow their 4 096 entries otherwise
-            if (a.ngroups > 32 && re <= 0) a.refresh_every = 1;
-        }
+        // the 64-group variant (32 < k <= 64, e.g. 82 k latents at k = 64) refreshes on every tile: with twice the codes
+        // per row and many more tiles per workgroup its lists would outgrow their 4 096 entries otherwise
+        a.refresh_first = 8;
+        a.refresh_every = a.ngroups > 32 ? 1 : 2;
         HIPCHK(c, launch_encode_f16x3(a, epi, s));
         return SAEV_OK;
     }
@@ -979,16 +961,10 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
                 sc.D = c->cfg.d_model; sc.refine_overflow = bad;
                 sc.surv_idx = c->surv_idx; sc.surv_val = c->surv_val; sc.surv_cnt = c->surv_cnt;
                 if (c->fwd_step) { sc.surv_rng = c->surv_rng; sc.lat_range = c->rs_lat_range; sc.n_ranges = c->rs_n_ranges; }
-                // saev_debug_cfg.fused_chain: survivors, their exact values and the final cut in ONE launch (select_refine_kernel).
-                // Opt-in: measured 335 us against 351 for the three kernels when all of them run at seven waves per SIMD,
-                // and slower than them (+0.03 ms per step) once lists of 1 025-2 048 entries stay in registers, which the
-                // survivor select needs (tools/experiments/README.md); a survivor overflow raises `bad` (= need_dense) like
-                // a list overflow does, and the dense route that follows redoes the step exactly
-                const bool chain_fused = c->dbg.fused_chain != 0;
-                if (chain_fused && tau_max == nullptr && first_flag != nullptr) {
-                    HIPCHK(c, launch_select_refine(sc, s));
-                    return SAEV_OK;
-                }
+                // (The three as ONE launch measured 335 us against 351 when all of them ran at seven waves per SIMD, and slower
+                // than them (+0.03 ms per step) once lists of 1 025-2 048 entries stay in registers, which the survivor select
+                // needs (tools/experiments/README.md).)  A survivor overflow raises `bad` (= need_dense) like a list overflow
+                // does, and the dense route that follows redoes the step exactly
                 HIPCHK(c, launch_select_cand(sc, s));
                 sc.enable_flag = flag; sc.ovf = nullptr;
                 if (c->fwd_step) {  // exact values from 32-column slices of W_enc^T that the XCD L2s hold (select.hip)
@@ -998,11 +974,10 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
                     rs.n_rows = n; rs.S = c->cfg.d_sae; rs.D = c->cfg.d_model;
                     rs.lat_range = c->rs_lat_range; rs.n_ranges = c->rs_n_ranges;
                     rs.enable_flag = flag; rs.enable_when = when;
-                    // (the D / 32 shares of a survivor are added by the final select itself: refine_sum_kernel's launch and its
-                    // round trip through surv_val are gone; saev_debug_cfg.fwd_route = 2 keeps the separate pass)
-                    const bool fold = c->dbg.fwd_route != 2;
-                    HIPCHK(c, launch_refine_slices(rs, s, !fold));
-                    if (fold) { sc.sum_part = c->rs_part; sc.sum_bias = sc.b_enc; sc.sum_n = c->cfg.d_model / RS_SLICE; sc.sum_plane = (size_t)n * REFINE_CAP; }
+                    // (the D / 32 shares of a survivor are added by the final select itself: no pass of their own, no round
+                    // trip through surv_val)
+                    HIPCHK(c, launch_refine_slices(rs, s));
+                    sc.sum_part = c->rs_part; sc.sum_bias = sc.b_enc; sc.sum_n = c->cfg.d_model / RS_SLICE; sc.sum_plane = (size_t)n * REFINE_CAP;
                 } else {
                     HIPCHK(c, launch_refine_exact(sc, s));
                 }
@@ -1309,17 +1284,10 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
         c->prep_valid = true;
     }
     if (wdec_ev != nullptr) HIPCHK(c, hipStreamWaitEvent(s, wdec_ev, 0));
-    c->wds_fresh = false;
     if (training) {
-        // (a training step whose decode can take the slices: normalize_rows leaves the slice-major copy on its way)
-        const bool want_slices = c->WdS != nullptr && c->cfg.normalize_w_dec && c->P == 1 && c->dws_ok;
         c->wn2_fresh = false;
-        if (want_slices) {
-            HIPCHK(c, launch_normalize_rows(c->params + c->off_W_dec, S, D, s, c->WdS, c->wn2));
-            c->wds_fresh = true;
-            c->wn2_fresh = c->wn2 != nullptr;
-        } else if (c->cfg.normalize_w_dec) {
-            HIPCHK(c, launch_normalize_rows(c->params + c->off_W_dec, S, D, s, nullptr, c->wn2));
+        if (c->cfg.normalize_w_dec) {
+            HIPCHK(c, launch_normalize_rows(c->params + c->off_W_dec, S, D, s, c->wn2));
             c->wn2_fresh = c->wn2 != nullptr;
         }
     }
@@ -1342,8 +1310,7 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
     // that csc_fill paid 35 us for on their own), provided the bit map is clean at this row pitch -- the previous full backward
     // cleared it behind itself -- and this context's backwards run over its own rows.
     c->bitmap_prefill_words = 0;
-    const bool slices_decode = c->P == 1 && c->wds_fresh && a.dval_out != nullptr && a.gS != nullptr;
-    if (training && c->dbg.csc_route == 0 && c->bitmap != nullptr && c->bitmap_clean && !c->last_backward_gathered && !slices_decode) {
+    if (training && c->dbg.csc_route == 0 && c->bitmap != nullptr && c->bitmap_clean && !c->last_backward_gathered) {
         const int words = ((n + 31) / 32 + 7) / 8 * 8;
         if (words <= c->bitmap_clean_words) {
             a.csc_bitmap = c->bitmap; a.csc_words = words;
@@ -1351,11 +1318,7 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
             c->bitmap_clean = false;
         }
     }
-    if (slices_decode) {
-        DecodeSliceArgs ds{};
-        ds.d = a; ds.WdS = c->WdS; ds.part = c->dec_part; ds.dvp = c->dvp; ds.dvp_pitch = (long)c->back_rows * K;
-        HIPCHK(c, launch_decode_slices(ds, s));
-    } else if (c->P > 1) {
+    if (c->P > 1) {
         MatryArgs m{};
         m.P = c->P;
         for (int p = 0; p < c->P; ++p) m.cuts[p] = c->cuts[p];
@@ -1716,10 +1679,9 @@ int saev_step_dead(saev_ctx* c, int64_t n_rows_global, void* stream) {
     d.toks = c->toks; d.fired = c->fired; d.dead = c->dead; d.S = S;
     d.add_tokens = n_rows_global; d.threshold = c->cfg.dead_threshold_tokens; d.k_aux = c->cfg.k_aux;
     d.n_dead = c->flags + 4; d.k_use = c->flags + 5; d.stats = c->stats; d.scratch = c->flags + 6;
-    // (saev_debug_cfg.dead_lag: how many steps old the record is that sizes this step's auxiliary work -- a shorter lag gives a
-    // tighter bound of the dead count, a longer one lets the host run further ahead of the device)
-    const int lag = c->dbg.dead_lag > 0 ? std::min(c->dbg.dead_lag, DEAD_RING / 2) : DEAD_LAG;
-    d.horizon_tokens = (int64_t)lag * n_rows_global;
+    // (how many steps old the record is that sizes this step's auxiliary work: a shorter lag gives a tighter bound of the dead
+    // count, a longer one lets the host run further ahead of the device)
+    d.horizon_tokens = (int64_t)DEAD_LAG * n_rows_global;
     d.step = step; d.cum_tokens = c->tokens_seen;
     d.rec = c->rec_dev ? c->rec_dev + step % DEAD_RING : nullptr;
     c->dead_list_ready = false;
@@ -1757,7 +1719,7 @@ int saev_step_dead(saev_ctx* c, int64_t n_rows_global, void* stream) {
     const int small_default = mfma_route ? std::max((int)AUX_SMALL_MAX, c->aux_mfma_cap) : (int)AUX_SMALL_DEFAULT;
     const int small_cap = c->dbg.aux_small_max < 0 ? 0 : (c->dbg.aux_small_max == 0 ? small_default : std::min(c->dbg.aux_small_max, (int)AUX_SMALL_MAX));
     const int small_max = std::min(small_cap, c->cfg.k_aux);
-    const int64_t s0 = step - lag;
+    const int64_t s0 = step - DEAD_LAG;
     if (s0 >= c->rec_valid_from) {
         HIPCHK(c, hipEventSynchronize(c->dead_ev[s0 % DEAD_RING]));
         const volatile DeadRecord* r = c->rec_host + s0 % DEAD_RING;
@@ -2175,7 +2137,7 @@ int saev_tail_apply(saev_ctx* c, float lr, float max_norm, float grad_scale, int
             im.mu = c->leader != nullptr ? c->leader->mu : c->mu; im.wmax_prev = c->wmax_prev; im.scales_next = scl_next(c); im.nks = c->Dp / 32; im.S_pad = c->S_pad;
         }
         if (emit_bf16) { im.ws = c->ws; im.nks = c->Dp / 32; im.S_pad = c->S_pad; im.mode = 1; }
-        if ((emit || emit_bf16) && c->wchk != nullptr && c->dbg.own_check == 0) {
+        if ((emit || emit_bf16) && c->wchk != nullptr) {
             // the tiles' checksums: left for the next step, and -- when this step's forward ran on images an earlier Adam left --
             // compared with what that Adam left (an evaluation forward in between changes nothing: W_enc did not move)
             im.chk = c->wchk; im.late = c->stale_dev != nullptr ? c->stale_dev + 1 : nullptr;
@@ -2186,7 +2148,7 @@ int saev_tail_apply(saev_ctx* c, float lr, float max_norm, float grad_scale, int
                                     c->off_b_enc, c->n_params - c->off_b_enc, s, c->unused_valid ? c->lat_unused : nullptr,
                                     (emit || emit_bf16) ? &im : nullptr));
         c->unused_valid = false;
-        c->wchk_valid = (emit || emit_bf16) && c->wchk != nullptr && c->dbg.own_check == 0;
+        c->wchk_valid = (emit || emit_bf16) && c->wchk != nullptr;
         c->wimg_bf16_fresh = emit_bf16;
         if (emit) {
             // the bias of the next centred first pass and the column-norm maxima its margins need: W-only, so they are finished here

@@ -684,7 +684,7 @@ __global__ __launch_bounds__(HTHREADS, 2) void encode_f16x3_kernel(EncodeF16Args
 //   groups touches all 64 banks once.
 // Group of a latent (for the 32 shared group maxima): its position modulo 32.
 // cache policy of encode_m16_kernel's staging loads (" nt", " sc1", ...: experiments; the shipped kernel uses the default for both --
-// tools/experiments/r5_enc_policy.sh)
+// tools/experiments/README.md)
 #ifndef SAEV_ENC_W_POLICY
 #define SAEV_ENC_W_POLICY ""
 #endif
@@ -735,7 +735,7 @@ __global__ __launch_bounds__(HTHREADS, 2) void encode_m16_kernel(EncodeF16Args a
     const int b0 = bb * HTB;
 
     const int nks = Dp / 32;  // k-steps per tile
-    const int rot = a.no_rot ? 0 : (bb & 7) % nks;  // see encode_f16x3_kernel (saev_debug_cfg.enc_rot = 1: lock step)
+    const int rot = (bb & 7) % nks;  // see encode_f16x3_kernel
     auto kmap = [&](int t) { const int k = t + rot; return k >= nks ? k - nks : k; };
 
     const size_t img = (size_t)256 * 32;  // halfs per image
@@ -1147,10 +1147,8 @@ hipError_t launch_encode_f16x3(const EncodeF16Args& a, int epi, hipStream_t stre
     dim3 grid(n_bblocks * a.s_splits, (epi == EPI_DENSE && a.n_batches > 1) ? a.n_batches : 1), block(HTHREADS);
     const size_t smem = sizeof(HSmem);
     static bool attr_set = false;
-    const bool use_m16 = a.mfma32 == 0;
     if (!attr_set) {
-
-        const void* fns[16] = {reinterpret_cast<const void*>(&encode_m16_kernel<1>),
+        const void* fns[12] = {reinterpret_cast<const void*>(&encode_m16_kernel<1>),
                               reinterpret_cast<const void*>(&encode_m16_kernel<2>),
                               reinterpret_cast<const void*>(&encode_m16_kernel<1, 64>),
                               reinterpret_cast<const void*>(&encode_m16_kernel<2, 64>),
@@ -1161,40 +1159,35 @@ hipError_t launch_encode_f16x3(const EncodeF16Args& a, int epi, hipStream_t stre
                               reinterpret_cast<const void*>(&encode_f16x3_kernel<EPI_TOPK, 32, 0>),
                               reinterpret_cast<const void*>(&encode_f16x3_kernel<EPI_TOPK, 64, 0>),
                               reinterpret_cast<const void*>(&encode_f16x3_kernel<EPI_DENSE, 32, 1>),
-                              reinterpret_cast<const void*>(&encode_f16x3_kernel<EPI_TOPK, 32, 1>),
-                              reinterpret_cast<const void*>(&encode_f16x3_kernel<EPI_TOPK, 64, 1>),
-                              reinterpret_cast<const void*>(&encode_f16x3_kernel<EPI_DENSE, 32, 2>),
-                              reinterpret_cast<const void*>(&encode_f16x3_kernel<EPI_TOPK, 32, 2>),
-                              reinterpret_cast<const void*>(&encode_f16x3_kernel<EPI_TOPK, 64, 2>)};
+                              reinterpret_cast<const void*>(&encode_f16x3_kernel<EPI_DENSE, 32, 2>)};
         for (const void* f : fns) {
             hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
             if (e != hipSuccess) return e;
         }
         attr_set = true;
     }
-#define LAUNCH_ENC(E, G, N) hipLaunchKernelGGL((encode_f16x3_kernel<E, G, N>), grid, block, smem, stream, a)
-#define LAUNCH_AR(E, G)                                   \
-    do {                                                  \
-        if (a.arith == 1) LAUNCH_ENC(E, G, 1);            \
-        else if (a.arith == 2) LAUNCH_ENC(E, G, 2);       \
-        else LAUNCH_ENC(E, G, 0);                         \
-    } while (0)
-    if (epi == EPI_DENSE) LAUNCH_AR(EPI_DENSE, 32);
-    else if (a.ngroups <= 32 && a.heur_z != nullptr) {
-        if (a.arith == 1) hipLaunchKernelGGL((encode_f16x3_kernel<EPI_TOPK, 32, 1, true>), grid, block, smem, stream, a);
-        else if (a.arith == 2) hipLaunchKernelGGL((encode_f16x3_kernel<EPI_TOPK, 32, 2, true>), grid, block, smem, stream, a);
-        else hipLaunchKernelGGL((encode_f16x3_kernel<EPI_TOPK, 32, 0, true>), grid, block, smem, stream, a);
-    } else if (a.ngroups <= 32 && a.arith != 0 && use_m16) {
-        // single-product modes: the 16x16x32 kernel (saev_debug_cfg.enc_mfma = 32 brings the 32x32x16 one back for A/B runs)
-        if (a.arith == 1) hipLaunchKernelGGL((encode_m16_kernel<1>), grid, block, smem, stream, a);
-        else hipLaunchKernelGGL((encode_m16_kernel<2>), grid, block, smem, stream, a);
-    } else if (a.ngroups <= 32) LAUNCH_AR(EPI_TOPK, 32);
-    else if (a.arith != 0 && use_m16) {
-        if (a.arith == 1) hipLaunchKernelGGL((encode_m16_kernel<1, 64>), grid, block, smem, stream, a);
-        else hipLaunchKernelGGL((encode_m16_kernel<2, 64>), grid, block, smem, stream, a);
+    // EPI_TOPK with guaranteed bounds: the single-product modes (bf16, fp16) run on the 16x16x32 kernel, the three-product mode
+    // on the 32x32x16 template, which also serves the dense epilogue and the predicted bounds
+#define LAUNCH_ENC(...) hipLaunchKernelGGL((encode_f16x3_kernel<__VA_ARGS__>), grid, block, smem, stream, a)
+#define LAUNCH_M16(...) hipLaunchKernelGGL((encode_m16_kernel<__VA_ARGS__>), grid, block, smem, stream, a)
+    if (epi == EPI_DENSE) {
+        if (a.arith == 1) LAUNCH_ENC(EPI_DENSE, 32, 1);
+        else if (a.arith == 2) LAUNCH_ENC(EPI_DENSE, 32, 2);
+        else LAUNCH_ENC(EPI_DENSE, 32, 0);
+    } else if (a.ngroups <= 32 && a.heur_z != nullptr) {
+        if (a.arith == 1) LAUNCH_ENC(EPI_TOPK, 32, 1, true);
+        else if (a.arith == 2) LAUNCH_ENC(EPI_TOPK, 32, 2, true);
+        else LAUNCH_ENC(EPI_TOPK, 32, 0, true);
+    } else if (a.ngroups <= 32) {
+        if (a.arith == 1) LAUNCH_M16(1);
+        else if (a.arith == 2) LAUNCH_M16(2);
+        else LAUNCH_ENC(EPI_TOPK, 32, 0);
+    } else {
+        if (a.arith == 1) LAUNCH_M16(1, 64);
+        else if (a.arith == 2) LAUNCH_M16(2, 64);
+        else LAUNCH_ENC(EPI_TOPK, 64, 0);
     }
-    else LAUNCH_AR(EPI_TOPK, 64);
-#undef LAUNCH_AR
+#undef LAUNCH_M16
 #undef LAUNCH_ENC
     return hipGetLastError();
 }

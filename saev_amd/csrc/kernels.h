@@ -83,15 +83,13 @@ struct SelectCandArgs {
     int lat_range, n_ranges;
     // optional (the final cut behind refine_slices_kernel): cand_val is not read; the value of candidate j of a row is
     // sum_bias[cand_idx[j]] + the sum_n shares sum_part[c][row][j] (c = 0 .. sum_n - 1, plane pitch sum_plane floats, row pitch
-    // cand_stride) added in slice order -- refine_sum_kernel's pass folded into the select that consumes it
+    // cand_stride) added in slice order, then the bias
     const float* sum_part;
     const float* sum_bias;
     int sum_n;
     size_t sum_plane;
 };
 hipError_t launch_refine_exact(const SelectCandArgs& a, hipStream_t stream);
-// survivors -> exact values -> final cut in one launch (f16r with guaranteed bounds); a.row_margin, x, W_encT, b_enc set
-hipError_t launch_select_refine(const SelectCandArgs& a, hipStream_t stream);
 constexpr int REFINE_CAP = 512;
 // The exact refinement from 32-column slices of W_enc^T (select.hip: refine_slices_kernel).  xS: slice-major x
 // ([D / 32][n_rows][32]); WeS: slice-major W_enc^T ([D / 32][S][32]); part: [D / 32][n_rows][REFINE_CAP] shares of the dot
@@ -106,8 +104,8 @@ struct RefineSlicesArgs {
     int n_rows, S, D, lat_range, n_ranges;
     const int32_t* enable_flag; int enable_when;
 };
-// sum_shares = false: the caller's final select adds the shares itself (SelectCandArgs::sum_part)
-hipError_t launch_refine_slices(const RefineSlicesArgs& a, hipStream_t stream, bool sum_shares = true);
+// (the caller's final select adds the shares itself: SelectCandArgs::sum_part)
+hipError_t launch_refine_slices(const RefineSlicesArgs& a, hipStream_t stream);
 hipError_t launch_select_cand(const SelectCandArgs& a, hipStream_t stream);
 hipError_t launch_init_i32(int32_t* p, int32_t v, int n, hipStream_t stream);
 hipError_t launch_encoder_init(int32_t* cand_cnt, int n_rows, int32_t* gmax, int n_gmax, hipStream_t stream,
@@ -177,18 +175,6 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t stream);
 // whether launch_decode forms dval_out for this shape (otherwise the pointer is ignored and pass A forms the products)
 bool decode_forms_dval(int D, int k);        // plain decode: top_k <= 64 (two register halves above 32), d_model 256 .. 1280
 bool decode_matry_forms_dval(int D, int k);  // Matryoshka decode: top_k <= 32, d_model <= 1024
-// The same decode out of 32-column slices of W_dec that an XCD's L2 holds (decode_s_kernel + decode_s_finish_kernel): the route of a
-// training step whose normalize_rows has just left the slice-major copy WdS.  part: per (slice, row) {sse_scaled, pad, sse64, sumsq64}
-// (n_slices x n_rows x 3 doubles), dvp: per slice the 32 dval shares of every row (pitch dvp_pitch floats per slice, >= n_rows * 32).
-struct DecodeSliceArgs {
-    DecodeArgs d;          // W_dec unused; dval_out receives the summed shares (n_rows, code_stride)
-    const float* WdS;      // [D / 32][S][32]
-    double* part;
-    float* dvp;
-    long dvp_pitch;
-};
-bool decode_slices_supported(int D, int S, int k, int code_stride);
-hipError_t launch_decode_slices(const DecodeSliceArgs& a, hipStream_t stream);
 
 // Matryoshka prefixes (objectives.py:125-138, modeling.py:369-409): P ascending cut points ending at S; prefix p
 // reconstructs from the codes with latent index < cuts[p].
@@ -356,9 +342,8 @@ hipError_t launch_colsum_absmax(const float* m, int n_rows, int D, float* partia
                                 saev_step_stats* zero_stats = nullptr, int32_t* zero_flag = nullptr);
 
 // ---- tail.hip: HBM-bound streaming kernels over the parameter-sized buffers -------------------
-// WS: optional slice-major copy [D / 32][S][32] of the normalised rows (d_model % 32 == 0)
 // wn2 (optional): ||row||^2 of every row as written (1 up to rounding; what remove_parallel_grads divides by)
-hipError_t launch_normalize_rows(float* W, int S, int D, hipStream_t stream, float* WS = nullptr, float* wn2 = nullptr);
+hipError_t launch_normalize_rows(float* W, int S, int D, hipStream_t stream, float* wn2 = nullptr);
 // rows [0, S) of gW projected orthogonal to the rows of W (project != 0); with sq_partials, ceil(S / 4) doubles: the sums
 // of squares of the rows as written (the clip norm's share of W_dec, from the same pass)
 hipError_t launch_rpg(float* gW, const float* W, int S, int D, hipStream_t stream, double* sq_partials = nullptr,
@@ -471,7 +456,6 @@ struct EncodeF16Args {
     const float* scale_dev;   // NULL or two device floats: extra power-of-two scales of the x and W images
     const float* scale_dev_b; // optional: the W images' scale lives elsewhere (*scale_dev_b instead of scale_dev[1])
     int s_splits;
-    int no_rot;            // 1: every workgroup walks the k-steps of a tile in the same order (saev_debug_cfg.enc_rot)
     float* h_out;             // EPI_DENSE
     int ngroups;              // EPI_TOPK: 32 (bound = min over 32 group maxima; needs top_k <= 32) or 64 (bound = top_k-th
                               // largest of 64 group maxima; top_k <= 64)
@@ -499,7 +483,6 @@ struct EncodeF16Args {
     int n_batches;
     int blk_imgs;
     long out_bstride;
-    int mfma32;               // host side only: 1 = the 32x32x16 kernels for the single-product modes too (saev_debug_cfg.enc_mfma)
 };
 hipError_t launch_encode_f16x3(const EncodeF16Args& a, int epi, hipStream_t stream);
 int encode_f16x3_tile_rows();

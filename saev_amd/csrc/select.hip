@@ -487,122 +487,6 @@ __global__ __launch_bounds__(256) void select_cand_kernel(SelectCandArgs a) {
     else select_cand_row_stream(a, row, n, s_idx, s_val, cv, ci);
 }
 
-// ---- the f16r exactness chain in ONE launch -------------------------------------------------------------------------
-// select_cand_kernel (survivors) -> refine_exact_kernel -> select_cand_kernel (final cut) as one kernel, one wave per row:
-// the survivor list and its exact values live in LDS instead of making two global round trips, the two relaunches are gone,
-// and the bit search of one wave (issue-bound) overlaps the row gathers of its neighbours (memory-bound) on the same CU.
-// Same arithmetic in the same order as the three kernels: bit-identical codes.
-
-// survivors of the approximate cut of one row -> lds_idx[0..ns); returns ns (wave-uniform), -1 when more than REFINE_CAP
-template <int EPL>
-__device__ __forceinline__ int survivors_to_lds(const SelectCandArgs& a, int row, int n, const float* cv, const int32_t* ci,
-                                                int32_t* lds_idx) {
-    const int lane = threadIdx.x & 63;
-    const int k = min(a.k, n);
-    uint32_t key[EPL];
-    int32_t idx[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int p = e * 64 + lane;
-        if (p < n) { key[e] = f2ukey(cv[p]); idx[e] = ci[p]; }
-        else { key[e] = 0u; idx[e] = 0x7fffffff; }
-    }
-    uint32_t t = 0;
-    bool done = false;
-    for (int bit = 31; bit >= 0 && !done; --bit) {
-        const uint32_t trial = t | (1u << bit);
-        int c = 0;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) c += __popcll(__ballot(key[e] >= trial));
-        if (c == k) {  // exactly k keys reach the trial value: the k-th largest is the smallest of them
-            uint32_t m = 0xffffffffu;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) m = min(m, key[e] >= trial ? key[e] : 0xffffffffu);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, o, 64));
-            t = m;
-            done = true;
-        } else if (c > k) {
-            t = trial;
-        }
-    }
-    const uint32_t key_lo = f2ukey(ukey2f(t) - a.row_margin[row]);
-    int base = 0;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const bool sv = key[e] >= key_lo && idx[e] != 0x7fffffff;
-        const unsigned long long m = __ballot(sv);
-        const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (sv && pos < REFINE_CAP) lds_idx[pos] = idx[e];
-        base += __popcll(m);
-    }
-    return base > REFINE_CAP ? -1 : base;
-}
-
-template <int NV>
-__global__ __launch_bounds__(256) void select_refine_kernel(SelectCandArgs a) {
-    if (a.enable_flag != nullptr && (*a.enable_flag != 0) != (a.enable_when != 0)) return;
-    __shared__ int32_t l_idx[4][REFINE_CAP];
-    __shared__ float l_val[4][REFINE_CAP];
-    __shared__ int32_t s_idx[4][64];
-    __shared__ float s_val[4][64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int row = blockIdx.x * 4 + w;
-    if (row >= a.n_rows) return;
-    const int cnt = a.cand_cnt[row];
-    if (a.ovf != nullptr && lane == 0 && (cnt > a.cand_cap || !(a.row_margin[row] < 3.0e38f))) atomicOr(&a.ovf[0], 1);
-    const int n = min(cnt, a.cand_cap);
-    const float* cv = a.cand_val + (size_t)row * a.cand_stride;
-    const int32_t* ci = a.cand_idx + (size_t)row * a.cand_stride;
-    int ns;
-    if (n <= 512) ns = survivors_to_lds<8>(a, row, n, cv, ci, l_idx[w]);
-    else if (n <= 1024) ns = survivors_to_lds<16>(a, row, n, cv, ci, l_idx[w]);
-    else if (n <= 2048) ns = survivors_to_lds<32>(a, row, n, cv, ci, l_idx[w]);
-    else {
-        uint32_t T;
-        ns = stream_survivors(a, row, n, cv, ci, l_idx[w], &T);
-        if (ns > REFINE_CAP) ns = -1;
-    }
-    if (ns < 0) {  // the caller's dense route redoes the launch exactly
-        if (lane == 0) *a.refine_overflow = 1;
-        ns = REFINE_CAP;
-    }
-    // exact pre-activations of the survivors (refine_exact_kernel's loop, lists in LDS)
-    const int D4 = a.D >> 2;
-    f32x4 xv[NV];
-    const f32x4* xr = reinterpret_cast<const f32x4*>(a.x + (size_t)row * a.D);
-#pragma unroll
-    for (int q = 0; q < NV; ++q) xv[q] = (lane + 64 * q < D4) ? xr[lane + 64 * q] : f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int j0 = 0; j0 < ns; j0 += 8) {
-        const int32_t my = l_idx[w][min(j0 + (lane & 7), ns - 1)];
-        float p[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int32_t li = __shfl(my, t, 64);
-            const f32x4* wr = reinterpret_cast<const f32x4*>(a.W_encT + (size_t)li * a.D);
-            float acc = 0.f;
-#pragma unroll
-            for (int q = 0; q < NV; ++q) {
-                if (lane + 64 * q < D4) {
-                    const f32x4 wv = wr[lane + 64 * q];
-                    acc += xv[q][0] * wv[0] + xv[q][1] * wv[1] + xv[q][2] * wv[2] + xv[q][3] * wv[3];
-                }
-            }
-            p[t] = acc;
-        }
-        const float r = wave_reduce_scatter8(p, lane);  // lane l holds the sum of slot (l >> 3) & 7
-        if ((lane & 7) == 0) {
-            const int t = lane >> 3;
-            if (j0 + t < ns) l_val[w][j0 + t] = r + a.b_enc[l_idx[w][j0 + t]];
-        }
-    }
-    // the final cut on the exact values (select_cand_kernel without a margin, lists in LDS)
-    SelectCandArgs b = a;
-    b.row_margin = nullptr; b.tau_max = nullptr;
-    if (ns <= 64) select_small_row(b, row, ns, l_val[w], l_idx[w]);
-    else select_cand_row<8>(b, row, ns, s_idx, s_val, l_val[w], l_idx[w]);
-}
-
 __global__ void init_i32_kernel(int32_t* p, int32_t v, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -678,8 +562,8 @@ __global__ __launch_bounds__(256) void refine_exact_kernel(SelectCandArgs a) {
 // written slice-major by the same pass ([slice][latent][32]).  An eight-lane group owns a row: its x slice sits in one float4 per
 // lane, a survivor is one 128-byte gather, four fmas and -- eight survivors at a time -- a reduce-scatter over the group, so
 // lane l stores survivor l's share of the dot product (one 32-byte store per group).  Survivors outside the latent range
-// of the pass cost an out-of-bounds buffer load (no memory access).  refine_sum_kernel adds the D / 32 shares in slice
-// order and the bias: the same fp32 products as the row kernel, summed in another (fixed) order.
+// of the pass cost an out-of-bounds buffer load (no memory access).  The final select adds the D / 32 shares in slice
+// order and the bias (kernels.h: SelectCandArgs::sum_part): the same fp32 products as the row kernel, summed in another (fixed) order.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 rs_buf_load16(__amdgpu_buffer_rsrc_t r, uint32_t voff) {
     const i32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0);
@@ -792,30 +676,6 @@ __global__ __launch_bounds__(256) void refine_slices_kernel(RefineSlicesArgs a, 
         }
         j0 += 8 * RS_BATCHES;
         advance();
-    }
-}
-// surv_val[row][j] = b_enc[latent] + the D / 32 shares in slice order; one wave per row
-__global__ __launch_bounds__(256) void refine_sum_kernel(RefineSlicesArgs a) {
-    if (a.enable_flag != nullptr && (*a.enable_flag != 0) != (a.enable_when != 0)) return;
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= a.n_rows) return;
-    const int cnt = a.surv_cnt[row];
-    const int n_slices = a.D / RS_SLICE;
-    const size_t plane = (size_t)a.n_rows * REFINE_CAP;
-    for (int j = lane; j < cnt; j += 64) {
-        const size_t o = (size_t)row * REFINE_CAP + j;
-        float s = 0.f;
-        int c = 0;
-        for (; c + 8 <= n_slices; c += 8) {  // eight loads in flight, added in slice order
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = a.part[(size_t)(c + u) * plane + o];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; c < n_slices; ++c) s += a.part[(size_t)c * plane + o];
-        a.surv_val[o] = s + a.b_enc[a.surv_idx[o]];
     }
 }
 
@@ -1301,7 +1161,7 @@ hipError_t launch_refine_exact(const SelectCandArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_refine_slices(const RefineSlicesArgs& a, hipStream_t stream, bool sum_shares) {
+hipError_t launch_refine_slices(const RefineSlicesArgs& a, hipStream_t stream) {
     if (a.n_rows <= 0) return hipSuccess;
     if (a.D % RS_SLICE != 0 || (uint64_t)a.S * 128ull >= (1ull << 32) - 256ull || a.n_ranges <= 0) return hipErrorInvalidValue;
     // rows per eight-lane group: 8 evens out the survivor lists of a group's rows (283 -> 257 us at 16 384 rows); a small batch
@@ -1312,22 +1172,6 @@ hipError_t launch_refine_slices(const RefineSlicesArgs& a, hipStream_t stream, b
     const dim3 grid(8 * slice_blocks * a.n_ranges * wg_per_combo);
     if (rows == 4) hipLaunchKernelGGL(refine_slices_kernel<4>, grid, dim3(256), 0, stream, a, wg_per_combo);
     else hipLaunchKernelGGL(refine_slices_kernel<RS_ROWS_MAX>, grid, dim3(256), 0, stream, a, wg_per_combo);
-    // (adding the shares inside the final select instead -- 32 dependent loads per lane of a kernel that lives on its bit
-    // search -- took that select from 20 to 80 us against 42 for this pass)
-    if (sum_shares) hipLaunchKernelGGL(refine_sum_kernel, dim3((a.n_rows + 3) / 4), dim3(256), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_select_refine(const SelectCandArgs& a, hipStream_t stream) {
-    if (a.n_rows <= 0) return hipSuccess;
-    if (a.cand_cap > 4096 || a.row_margin == nullptr) return hipErrorInvalidValue;
-    const dim3 grid((a.n_rows + 3) / 4), block(256);
-    const int nv = (a.D / 4 + 63) / 64;
-#define RF(N) hipLaunchKernelGGL(select_refine_kernel<N>, grid, block, 0, stream, a)
-    if (nv <= 1) RF(1); else if (nv <= 2) RF(2); else if (nv <= 3) RF(3); else if (nv <= 4) RF(4);
-    else if (nv <= 6) RF(6); else if (nv <= 8) RF(8); else if (nv <= 12) RF(12); else if (nv <= 16) RF(16);
-    else return hipErrorInvalidValue;
-#undef RF
     return hipGetLastError();
 }
 

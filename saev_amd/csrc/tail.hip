@@ -8,7 +8,7 @@
 namespace {
 
 template <int NV>
-__global__ __launch_bounds__(256) void normalize_rows_kernel(float* W, int S, int D, float* WS, float* wn2) {
+__global__ __launch_bounds__(256) void normalize_rows_kernel(float* W, int S, int D, float* wn2) {
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= S) return;
@@ -33,8 +33,6 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(float* W, int S, in
 #pragma unroll
             for (int e = 0; e < 4; ++e) { o[e] = v[n][e] / nrm; s2 = __builtin_fmaf(o[e], o[e], s2); }
             r[q] = o;
-            // slice-major copy [D / 32][S][32] for the slice decode (sparse.hip: decode_s_kernel), 128 bytes per (row, slice)
-            if (WS != nullptr) reinterpret_cast<f32x4*>(WS)[((size_t)(q >> 3) * S + i) * 8 + (q & 7)] = o;
         }
     }
     if (wn2 != nullptr) {  // (same fma chain and lane order as rpg_row_stats forms ||w||^2 with)
@@ -736,9 +734,9 @@ __global__ __launch_bounds__(1024) void stats_dead_kernel(StatsArgs A, int n_sta
 
 }  // namespace
 
-hipError_t launch_normalize_rows(float* W, int S, int D, hipStream_t stream, float* WS, float* wn2) {
+hipError_t launch_normalize_rows(float* W, int S, int D, hipStream_t stream, float* wn2) {
     return dispatch_nv(D, [&](auto nv) {
-        hipLaunchKernelGGL(normalize_rows_kernel<decltype(nv)::value>, dim3((S + 3) / 4), dim3(256), 0, stream, W, S, D, WS, wn2);
+        hipLaunchKernelGGL(normalize_rows_kernel<decltype(nv)::value>, dim3((S + 3) / 4), dim3(256), 0, stream, W, S, D, wn2);
     });
 }
 hipError_t launch_rpg(float* gW, const float* W, int S, int D, hipStream_t stream, double* sq_partials, int project) {

@@ -52,15 +52,8 @@ class EngineConfig:
     # route without touching code:
     #   SAEV_AMD_DW=rows          weight gradients by whole-row gathers instead of column slices
     #   SAEV_AMD_DW=slices_a      column slices, but dval = <dL/dx_hat row, decoder row> formed by their first pass instead of by the decode
-    #   SAEV_AMD_DW=slices_s      as the default, but the decode itself gathers 32-column slices of W_dec out of the XCD L2s (decode_s_kernel; a wash)
     #   SAEV_AMD_FWD=rows         exact refinement of the f16r encoder by whole-row gathers instead of 32-column slices
-    #   SAEV_AMD_FWD=sum_pass     slices, with the shares of a survivor added by a pass of their own (round 4) instead of by the final select
-    #   SAEV_AMD_ENC_MFMA=32      single-product encoders on the 32x32x16 MFMA kernel
-    #   SAEV_AMD_FUSED_CHAIN=1    f16r select -> refine -> select as one launch
-    #   SAEV_AMD_NGROUPS=64       64-group TopK bound also for top_k <= 32
-    #   SAEV_AMD_ENC_WGS, SAEV_AMD_REFRESH_FIRST, SAEV_AMD_REFRESH_EVERY   encoder grid / bound-refresh cadence
     #   SAEV_AMD_AUX_SMALL_MAX    largest dead set of the few-dead-latents AuxK kernels (-1: always the dense algebra)
-    #   SAEV_AMD_DEAD_LAG         age in steps of the tracker record that sizes a step's auxiliary work (default 4)
     #   SAEV_AMD_CSC              1: the backward's pair-list build fills its bit map itself (default: the training decode does)
     #   SAEV_AMD_FIN              1: the backward's finalize re-reads the gradient rows for their statistics (round-4 kernels)
     #   SAEV_AMD_PREP             1: every f16r forward prepares its operands from x and W_enc itself (no streamed preparation)
@@ -68,21 +61,12 @@ class EngineConfig:
     #   SAEV_AMD_AUX_SMALL        1: 9-32 dead latents on the vector-ALU kernels of rounds 3-4 instead of the fp32 MFMA ones
     dw_route: str = dataclasses.field(default_factory=lambda: os.environ.get("SAEV_AMD_DW", "slices"))
     fwd_route: str = dataclasses.field(default_factory=lambda: os.environ.get("SAEV_AMD_FWD", "default"))
-    enc_mfma: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_ENC_MFMA", "0")))
-    fused_chain: bool = dataclasses.field(default_factory=lambda: os.environ.get("SAEV_AMD_FUSED_CHAIN", "0") not in ("", "0"))
-    ngroups: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_NGROUPS", "0")))
-    enc_wgs: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_ENC_WGS", "0")))
-    refresh_first: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_REFRESH_FIRST", "0")))
-    refresh_every: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_REFRESH_EVERY", "0")))
     aux_small_max: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_SMALL_MAX", "0")))
-    dead_lag: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_DEAD_LAG", "0")))
     csc_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_CSC", "0")))
     fin_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_FIN", "0")))
     prep_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_PREP", "0")))
     aux_dense_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_DENSE", "0")))
     aux_small_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_SMALL", "0")))
-    own_check: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_OWN_CHECK", "0")))
-    enc_rot: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_ENC_ROT", "0")))
     group_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_GROUP", "0")))
     aux_split_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_SPLIT", "0")))
     aux_wide_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_WIDE", "0")))
@@ -266,14 +250,13 @@ class SaeEngine:
                 bound_mode={"guaranteed": 0, "predicted": 1}[cfg.bounds], max_backward_rows=cfg.max_backward_rows,
                 activation={"topk": 0, "relu": 1}[cfg.activation],
             )
-            if cfg.dw_route not in ("slices", "rows", "slices_a", "slices_s") or cfg.fwd_route not in ("default", "rows", "sum_pass"):
-                raise ValueError(f"EngineConfig.dw_route must be 'slices', 'slices_a', 'slices_s' or 'rows' and fwd_route 'default', 'rows' or 'sum_pass', got {cfg.dw_route!r} / {cfg.fwd_route!r}")
+            if cfg.dw_route not in ("slices", "rows", "slices_a") or cfg.fwd_route not in ("default", "rows"):
+                raise ValueError(f"EngineConfig.dw_route must be 'slices', 'slices_a' or 'rows' and fwd_route 'default' or 'rows', got {cfg.dw_route!r} / {cfg.fwd_route!r}")
             dbg = _lib.SaevDebugCfg(
-                struct_size=C.sizeof(_lib.SaevDebugCfg), dw_route={"slices": 0, "rows": 1, "slices_a": 2, "slices_s": 4}[cfg.dw_route], enc_mfma=cfg.enc_mfma,
-                fused_chain=int(cfg.fused_chain), ngroups=cfg.ngroups, enc_wgs=cfg.enc_wgs, refresh_first=cfg.refresh_first,
-                refresh_every=cfg.refresh_every, aux_small_max=cfg.aux_small_max, fwd_route={"default": 0, "rows": 1, "sum_pass": 2}[cfg.fwd_route],
-                dead_lag=cfg.dead_lag, csc_route=cfg.csc_route, fin_route=cfg.fin_route, prep_route=cfg.prep_route, aux_dense_route=cfg.aux_dense_route, aux_small_route=cfg.aux_small_route,
-                own_check=cfg.own_check, enc_rot=cfg.enc_rot, group_route=cfg.group_route, aux_split_route=cfg.aux_split_route, aux_wide_route=cfg.aux_wide_route)
+                struct_size=C.sizeof(_lib.SaevDebugCfg), dw_route={"slices": 0, "rows": 1, "slices_a": 2}[cfg.dw_route],
+                aux_small_max=cfg.aux_small_max, fwd_route={"default": 0, "rows": 1}[cfg.fwd_route],
+                csc_route=cfg.csc_route, fin_route=cfg.fin_route, prep_route=cfg.prep_route, aux_dense_route=cfg.aux_dense_route, aux_small_route=cfg.aux_small_route,
+                group_route=cfg.group_route, aux_split_route=cfg.aux_split_route, aux_wide_route=cfg.aux_wide_route)
             ctx = C.c_void_p()
             rc = self.lib.saev_create_ex(C.byref(ccfg), C.byref(dbg), self.device.index, C.byref(ctx))
             if rc != 0:

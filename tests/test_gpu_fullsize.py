@@ -6,6 +6,8 @@ import math
 import pytest
 import torch
 
+from topk_exactness import assert_topk_exact
+
 pytestmark = pytest.mark.gpu
 
 
@@ -32,23 +34,8 @@ def test_fused_topk_is_exact_at_full_size(d, s, k, b):
     its margin + exact refinement to get here)."""
     eng, x = build(d, s, k, b)
     idx, val = eng.encode_topk(x)
-    st_idx = idx.long()
     assert idx.shape == (b, k) and (idx[:, 1:] > idx[:, :-1]).all() and idx.min() >= 0 and idx.max() < s
-    W, be = eng.view("W_enc").double(), eng.view("b_enc").double()
-    wmax = W.norm(dim=0).max().item()
-    worst_val = worst_cut = 0.0
-    for lo in range(0, b, 512):
-        rows = slice(lo, min(b, lo + 512))
-        h = x[rows].double() @ W + be
-        tol = 8.0 * 2.0 ** -24 * x[rows].double().norm(dim=1) * wmax
-        err = (h.gather(1, st_idx[rows]) - val[rows].double()).abs().amax(dim=1)
-        worst_val = max(worst_val, (err / tol).max().item())
-        assert (err <= tol).all(), f"rows {lo}..: value error {err.max().item():.3e} > tol {tol.min().item():.3e}"
-        kth = val[rows].min(dim=1).values.double()
-        over = h.scatter(1, st_idx[rows], float("-inf")).amax(dim=1) - kth
-        worst_cut = max(worst_cut, (over / tol).max().item())
-        assert (over <= tol).all(), f"rows {lo}..: a left-out pre-activation exceeds the smallest kept one by {over.max().item():.3e}"
-        del h
+    worst_val, worst_cut = assert_topk_exact(x, idx, val, eng.view("W_enc"), eng.view("b_enc"))
     print(f"full-size TopK ({d}, {s}, {k}, {b}): worst value error {worst_val:.2f} tol, worst cut excess {worst_cut:.2f} tol")
     # the dense route agrees exactly on the selected values
     rows = torch.randperm(b, device="cuda")[:64]

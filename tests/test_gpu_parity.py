@@ -8,6 +8,7 @@ import torch
 
 import sae_ref as R
 from conftest import load_golden
+from topk_exactness import assert_topk_exact
 
 pytestmark = pytest.mark.gpu
 
@@ -964,33 +965,6 @@ def test_teacher_forced_matryoshka_steps_match_oracle(tag):
     assert flips <= 3 and dead_max > 0 and routes & {1, 2, 3}, (flips, dead_max, routes)
 
 
-def test_32x32_first_pass_kernel_still_selectable(tmp_path):
-    """SAEV_AMD_ENC_MFMA=32 brings the 32x32x16 first-pass kernel back (the A/B switch of the 16x16x32 one; read once per
-    process, hence the subprocess): same codes as the default kernel on the same input."""
-    import os
-    import subprocess
-    import sys
-
-    code = (
-        "import torch, math, sys\n"
-        "from saev_amd.engine import EngineConfig, SaeEngine\n"
-        "d, s, k, b = 256, 4096, 16, 700\n"
-        "eng = SaeEngine(EngineConfig(d_model=d, d_sae=s, top_k=k, max_batch=b, k_aux=0, encoder='f16r'))\n"
-        "g = torch.Generator(device='cuda').manual_seed(3)\n"
-        "W = (torch.rand(s, d, device='cuda', generator=g) * 2 - 1) * math.sqrt(6.0 / d)\n"
-        "eng.view('W_dec').copy_(W); eng.view('W_enc').copy_(W.t())\n"
-        "x = torch.randn(b, d, device='cuda', generator=g)\n"
-        "idx, val = eng.encode_topk(x)\n"
-        "torch.save((idx.cpu(), val.cpu()), sys.argv[1])\n")
-    outs = []
-    for shape in ("16", "32"):
-        path = tmp_path / f"mfma{shape}.pt"
-        env = dict(os.environ, SAEV_AMD_ENC_MFMA=shape, PYTHONPATH=os.pathsep.join(sys.path))
-        subprocess.run([sys.executable, "-c", code, str(path)], check=True, env=env, timeout=600)
-        outs.append(torch.load(path))
-    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-
-
 def test_fused_train_step_and_phase_by_phase_agree(encoder_mode):
     """saev_train_step takes the squares of dW_enc from the transpose that ends the backward; the phase-by-phase entry
     points (what a data-parallel caller uses, with its exchange between backward and tail) re-read the gradient.  Same
@@ -1017,10 +991,13 @@ def test_fused_train_step_and_phase_by_phase_agree(encoder_mode):
             torch.testing.assert_close(a.view(key), b.view(key), rtol=1e-5, atol=1e-7, msg=lambda m: f"step {i} {key}: {m}")
 
 
-def test_one_launch_exactness_chain_gives_the_same_codes(monkeypatch):
-    """SAEV_AMD_FUSED_CHAIN=1 runs survivor select -> exact refinement -> final select of the f16r encoder as one kernel
-    (lists in LDS).  Same arithmetic in the same order: the codes must be bit-identical to the three-kernel chain, also on
-    rows whose candidate lists are long (a batch with a strong common direction) and on near-ties."""
+def test_default_exactness_chain_is_exact_on_long_candidate_lists():
+    """Survivor select -> exact refinement -> final select of the f16r encoder (three kernels) on rows whose candidate lists are
+    long (a batch with a strong common direction) and whose margins differ (every seventh row scaled by 0.01): on every row the
+    emitted values are the fp64 pre-activations at the emitted latents and nothing left out exceeds the smallest kept value, to
+    the rounding of a d-term fp32 dot product (topk_exactness.assert_topk_exact).  Not set equality with the fp64 top-k: 2 of
+    these 600 rows have an fp64 gap between the k-th and the (k+1)-th value below 2e-5 (smallest 1.09e-5), where a correct
+    fp32 result may keep either latent."""
     d, s, k, n = 256, 4096, 32, 600
     p = rand_params(d, s, seed=300)
     g = torch.Generator().manual_seed(301)
@@ -1028,15 +1005,12 @@ def test_one_launch_exactness_chain_gives_the_same_codes(monkeypatch):
     x[::7] = x[::7] * 0.01  # rows of a very different scale: other margins, other list lengths
     eng = make_engine(d, s, k, max_batch=n, encoder="f16r")
     eng.load_params(p)
-    monkeypatch.delenv("SAEV_AMD_FUSED_CHAIN", raising=False)
-    idx0, val0 = eng.encode_topk(x.cuda())
+    idx, val = eng.encode_topk(x.cuda())
     torch.cuda.synchronize()
-    monkeypatch.setenv("SAEV_AMD_FUSED_CHAIN", "1")
-    idx1, val1 = eng.encode_topk(x.cuda())
-    torch.cuda.synchronize()
-    assert torch.equal(idx0, idx1) and torch.equal(val0, val1)
     h = x.double() @ p["W_enc"].double() + p["b_enc"].double()
-    torch.testing.assert_close(h.gather(1, idx1.cpu().long()).float(), val1.cpu(), rtol=1e-5, atol=1e-5)
+    torch.testing.assert_close(h.gather(1, idx.cpu().long()).float(), val.cpu(), rtol=1e-5, atol=1e-5)
+    worst = assert_topk_exact(x.cuda(), idx, val, eng.view("W_enc"), eng.view("b_enc"))
+    print(f"default chain on long lists: worst value error {worst[0]:.2f} tol, worst cut excess {worst[1]:.2f} tol")
 
 
 @pytest.mark.parametrize("n_dead,d,n", [(1, 128, 200), (9, 128, 200), (17, 256, 333), (24, 768, 96), (32, 1024, 64), (31, 1280, 130),

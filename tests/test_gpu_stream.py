@@ -9,6 +9,8 @@ import math
 import pytest
 import torch
 
+from topk_exactness import assert_topk_exact
+
 pytestmark = [pytest.mark.gpu, pytest.mark.encoder_modes("f16r")]  # the streamed preparation belongs to the f16r encoder
 
 
@@ -187,17 +189,17 @@ def test_train_step_gather_equals_gather_then_train_step():
 
 @pytest.mark.parametrize("d,s,k,b", [(1024, 8192, 32, 2048), (768, 6144, 32, 1000), (256, 2048, 16, 300)])
 def test_shares_added_by_the_final_select_equal_the_separate_pass(d, s, k, b):
-    """saev_debug_cfg.fwd_route = 2 keeps refine_sum_kernel; the default lets the final select add a survivor's D / 32 shares itself,
-    in the same order: codes, values and therefore whole runs are bit-identical."""
-    from saev_amd.engine import EngineConfig, SaeEngine  # noqa: F401
-
-    engs = [_engine(d, s, k, b, 0, seed=21, fwd_route=r) for r in ("default", "sum_pass")]
+    """The final select adds a survivor's D / 32 shares itself (the pass that once did so on its own, bit-identically, is gone with
+    its switch).  Over four training steps the codes of every step are exact against an fp64 product of the parameters that
+    step's forward ran on (topk_exactness.assert_topk_exact: values at the emitted latents, nothing left out above the smallest
+    kept value, to the rounding of a d-term fp32 dot product)."""
+    eng = _engine(d, s, k, b, 0, seed=21)
     for i, x in enumerate(_batches(d, b, 4, seed=22)):
-        for eng in engs:
-            eng.train_step(x, 1e-3, 1.0)
-        (i0, v0, _), (i1, v1, _) = (e.last_codes(b) for e in engs)
-        assert torch.equal(i0, i1) and torch.equal(v0, v1), i
-    _same(*engs)
+        W_enc, b_enc = eng.view("W_enc").clone(), eng.view("b_enc").clone()
+        eng.train_step(x, 1e-3, 1.0)
+        idx, val, _ = eng.last_codes(b)
+        worst = assert_topk_exact(x, idx, val, W_enc, b_enc, what=f"step {i}: ")
+        print(f"step {i} ({d}, {s}, {k}, {b}): worst value error {worst[0]:.2f} tol, worst cut excess {worst[1]:.2f} tol")
 
 
 def test_bf16_images_left_by_adam_equal_a_fresh_split():

@@ -39,12 +39,14 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
 
 
 def test_struct_layouts_match_header(tmp_path):
-    """The ctypes mirrors of saev_cfg / saev_step_stats against what a C compiler makes of include/saev_amd.h."""
+    """The ctypes mirrors of saev_cfg / saev_step_stats / saev_debug_cfg / saev_muon_cfg against what a C compiler makes of
+    include/saev_amd.h."""
     import ctypes
 
     from saev_amd import _lib
 
-    fields = {"saev_cfg": [f for f, _ in _lib.SaevCfg._fields_], "saev_step_stats": [f for f, _ in _lib.SaevStepStats._fields_]}
+    mirrors = {"saev_cfg": _lib.SaevCfg, "saev_step_stats": _lib.SaevStepStats, "saev_debug_cfg": _lib.SaevDebugCfg, "saev_muon_cfg": _lib.SaevMuonCfg}
+    fields = {st: [f for f, _ in cls._fields_] for st, cls in mirrors.items()}
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "saev_amd.h"', "int main(void) {"]
     for st, fs in fields.items():
         src.append(f'printf("{st} %zu\\n", sizeof({st}));')
@@ -53,7 +55,7 @@ def test_struct_layouts_match_header(tmp_path):
     (tmp_path / "layout.c").write_text("\n".join(src))
     subprocess.run(["gcc", "-I", str(ROOT / "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
     want = dict(line.split() for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
-    for st, cls in (("saev_cfg", _lib.SaevCfg), ("saev_step_stats", _lib.SaevStepStats)):
+    for st, cls in mirrors.items():
         assert ctypes.sizeof(cls) == int(want[st]), st
         for f in fields[st]:
             assert getattr(cls, f).offset == int(want[f"{st}.{f}"]), f"{st}.{f}"

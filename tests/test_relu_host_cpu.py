@@ -34,7 +34,7 @@ def test_abi_version_agrees_between_header_and_library():
 
     m = re.search(r"#define SAEV_AMD_ABI_VERSION (\d+)", _header())
     assert m is not None
-    assert int(m.group(1)) == _lib.ABI_VERSION == _lib.load().saev_abi_version() == 11
+    assert int(m.group(1)) == _lib.ABI_VERSION == _lib.load().saev_abi_version() == 12
 
 
 def test_cfg_carries_the_activation_last():
