@@ -463,6 +463,49 @@ int saev_muon_newton_schulz(const void* x_in, int64_t rows, int64_t cols, void* 
 int64_t saev_coherence_workspace_bytes(int64_t S, int64_t D);
 int saev_dictionary_coherence(const float* W, int64_t S, int64_t D, int32_t route, void* workspace, int64_t workspace_bytes,
                               float* out_value, int32_t* out_pair, int32_t* out_info, void* stream);
+/* BATCH STATISTICS (the log block, train.py:365-442; evaluate, train.py:510-618; the inference pass, inference.py), context-free:
+ * one call per batch leaves every sum those three form, with no n x D or n x k temporary.  Inputs: x (n x D fp32) and its
+ * reconstruction x_hat (n x D fp32, may be NULL), both 16-byte aligned; the codes as padded rows, idx (n x cap int32), val
+ * (n x cap fp32) and row_nnz (n int32; NULL: every row has cap entries, as TopK rows do; a count above cap reads as cap, as in
+ * saev_decode_rows); keep (n bytes, may be NULL): rows with keep[b] == 0 contribute nothing.  4 <= D <= 4096, D % 4 == 0
+ * (anything else is SAEV_UNSUPPORTED), any n >= 0, S >= 0, cap >= 0 below 2^31; n = 0 returns SAEV_OK and writes nothing.
+ * Outputs are the caller's device buffers in saev_batch_acc; each may be NULL, which skips its work.  The call ADDS to them,
+ * so a pass over many batches needs no host arithmetic; flags = SAEV_BATCH_OVERWRITE stores instead (live excepted):
+ *   col_sum   (D doubles)  sum over kept rows of x[:, c]
+ *   scalars   (8 doubles)  [kept rows, sum x, sum x^2, sum r, sum r^2, 0, 0, 0], r = x - x_hat formed in fp64 from the fp32
+ *                          operands (exact to one rounding), squares as fp64 fmas; without x_hat the r sums add 0
+ *   n_pos     (S int64)    kept codes with val > 0
+ *   value_sum (S doubles)  sum of val over kept codes with val != 0
+ *   live      (S int32)    set to 1 where a kept code has |val| > live_eps (plain stores; the call never clears it)
+ * Codes whose index lies outside [0, S) are ignored.  NaN and Inf propagate as IEEE arithmetic gives them.
+ * col_sum and scalars are BIT-REPRODUCIBLE from run to run: per-workgroup partial sums in the workspace, added in workgroup order
+ * by a finishing pass, no floating-point atomics.  n_pos is integer, hence exact.  value_sum uses fp64 vector atomics and is
+ * reproducible only to fp64 rounding (the order of the adds is not fixed).
+ * workspace: saev_batch_stats_workspace_bytes(n, D) bytes of device memory, 256-byte aligned (-1: unsupported shape); needed only
+ * when col_sum or scalars is asked for.  Arguments are checked before the device is touched; a refused call leaves its message
+ * with saev_last_error(NULL) (per thread).  Nothing synchronises. */
+#define SAEV_BATCH_OVERWRITE 1
+typedef struct {
+    int32_t struct_size;   /* sizeof(saev_batch_acc) of the caller (fields past it read as 0) */
+    int32_t flags;         /* 0 or SAEV_BATCH_OVERWRITE                                       */
+    float live_eps;        /* the log block passes 1e-12 (train.py:404)                       */
+    int32_t reserved;
+    double* col_sum;
+    double* scalars;
+    int64_t* n_pos;
+    double* value_sum;
+    int32_t* live;
+} saev_batch_acc;
+int64_t saev_batch_stats_workspace_bytes(int64_t n, int64_t D);
+int saev_batch_stats(const float* x, const float* x_hat, const int32_t* idx, const float* val, const int32_t* row_nnz,
+                     const uint8_t* keep, int64_t n, int64_t D, int64_t S, int64_t cap, const saev_batch_acc* acc, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+/* metrics/avg_decoder_row_norm (train.py:406): *out = the mean over the S rows of W (S x D fp32 row-major, 16-byte aligned, same
+ * limits on D, S >= 1) of each row's fp32 L2 norm -- the squares exact in fp64, summed in a fixed order, the root rounded once to
+ * fp32 -- added in a fixed order as doubles: one device double, bit-reproducible.  workspace: SAEV_ROW_NORM_WORKSPACE_BYTES bytes,
+ * 256-byte aligned. */
+#define SAEV_ROW_NORM_WORKSPACE_BYTES 8192
+int saev_row_norm_mean(const float* W, int64_t S, int64_t D, double* out, void* workspace, int64_t workspace_bytes, void* stream);
 /* PARAMETER OWNERSHIP.  With the f16r encoder the context keeps, from one call to the next, what its forward needs of W_enc
  * (fp16 operand images, a slice-major fp32 transpose, bias and norm shares: written by the Adam launch of saev_train_step, or by
  * the last forward that prepared them itself) and uses it for as long as only the library has written the parameter buffer.  A

@@ -53,6 +53,18 @@ class SaevMuonCfg(C.Structure):
                [(n, C.c_int32) for n in ("nesterov", "ns_steps", "adjust_lr")]
 
 
+class SaevBatchAcc(C.Structure):
+    """include/saev_amd.h: saev_batch_acc (output pointers of saev_batch_stats; NULL skips the output)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("flags", C.c_int32), ("live_eps", C.c_float), ("reserved", C.c_int32),
+                ("col_sum", C.c_void_p), ("scalars", C.c_void_p), ("n_pos", C.c_void_p), ("value_sum", C.c_void_p),
+                ("live", C.c_void_p)]
+
+
+BATCH_OVERWRITE = 1
+ROW_NORM_WORKSPACE_BYTES = 8192
+
+
 class SaevError(RuntimeError):
     pass
 
@@ -119,6 +131,9 @@ _SIGNATURES = {
     "saev_muon_newton_schulz": (C.c_int, [P, C.c_int64, C.c_int64, P, C.POINTER(SaevMuonCfg), C.c_int32, P, C.c_int64, P]),
     "saev_coherence_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "saev_dictionary_coherence": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int32, P, C.c_int64, P, P, P, P]),
+    "saev_batch_stats_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "saev_batch_stats": (C.c_int, [P, P, P, P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(SaevBatchAcc), P, C.c_int64, P]),
+    "saev_row_norm_mean": (C.c_int, [P, C.c_int64, C.c_int64, P, P, C.c_int64, P]),
     "saev_comm_unique_id": (C.c_int, [P]),
     "saev_comm_init": (C.c_int, [P, P, C.c_int32, C.c_int32]),
     "saev_comm_world": (C.c_int, [P]),

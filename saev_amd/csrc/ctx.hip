@@ -340,7 +340,8 @@ int saev_layout(const saev_cfg* cfg, saev_layout_t* out) {
     return SAEV_OK;
 }
 
-const char* saev_last_error(const saev_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+// (the context-free entries of batchstats.hip leave their message per thread; a NULL context reads it)
+const char* saev_last_error(const saev_ctx* ctx) { return ctx ? ctx->err.c_str() : free_error(); }
 
 int saev_create(const saev_cfg* cfg, int device, saev_ctx** out) { return saev_create_ex(cfg, nullptr, device, out); }
 

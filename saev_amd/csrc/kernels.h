@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "../../include/saev_amd.h"
 
 enum { EPI_DENSE = 0, EPI_TOPK = 1 };
@@ -741,3 +743,7 @@ CohLayout coherence_layout(int S, int D);
 // route: SAEV_COH_AUTO / SAEV_COH_EXACT; results written on the device, nothing read back
 hipError_t launch_coherence(const float* W, int S, int D, int route, uint8_t* ws, const CohLayout& L, float* out_value,
                             int32_t* out_pair, int32_t* out_info, hipStream_t stream);
+
+// ---- Batch statistics (batchstats.hip: kernels and their C entries) ---------------------------------------------------------
+// message of the last refused context-free call on this thread ("null context" before any): what saev_last_error(NULL) returns
+const char* free_error();

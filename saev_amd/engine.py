@@ -172,6 +172,147 @@ def dictionary_coherence(W: torch.Tensor, *, route: str = "auto") -> CoherenceRe
                            overflow=code == 2, tiles_refiltered=tiles)
 
 
+def row_norm_mean(W: torch.Tensor) -> float:
+    """``W.norm(dim=1).mean()`` of an (S, D) float32 device matrix on the HIP kernels of saev_row_norm_mean (the log block's
+    metrics/avg_decoder_row_norm): exact fp64 squares, each norm rounded once to fp32, every sum in a fixed order; one read-back
+    of one double."""
+    if W.ndim != 2:
+        raise ValueError(f"row_norm_mean takes an (S, D) matrix, got shape {tuple(W.shape)}")
+    S, D = W.shape
+    if S < 1 or D < 4 or D > 4096 or D % 4:
+        raise ValueError(f"row_norm_mean: unsupported shape {(S, D)} (S >= 1, 4 <= D <= 4096, D % 4 == 0)")
+    if not W.is_cuda or W.dtype != torch.float32:
+        raise ValueError("row_norm_mean takes a float32 device matrix")
+    lib = _lib.load()
+    W = W.contiguous()
+    if W.data_ptr() % 16:
+        W = W.clone()
+    ws = torch.empty(_lib.ROW_NORM_WORKSPACE_BYTES + 8, device=W.device, dtype=torch.uint8)  # [partials | the result]
+    out = ws[_lib.ROW_NORM_WORKSPACE_BYTES:].view(torch.float64)
+    with torch.cuda.device(W.device):
+        rc = lib.saev_row_norm_mean(_ptr(W), S, D, _ptr(out), _ptr(ws), _lib.ROW_NORM_WORKSPACE_BYTES, _stream())
+    _lib.check(lib, None, rc, "saev_row_norm_mean")
+    return out.item()
+
+
+@dataclasses.dataclass(frozen=True)
+class BatchStatsHost:
+    """What ``BatchStats.read()`` brings back (CPU tensors; an output the accumulator was created without is None)."""
+
+    n_kept: float
+    sum_x: float
+    sum_xx: float
+    sum_r: float
+    sum_rr: float
+    extra: torch.Tensor              # (8) float64, the caller's own slots
+    col_sum: torch.Tensor | None     # (D) float64
+    n_pos: torch.Tensor | None       # (S) int64
+    value_sum: torch.Tensor | None   # (S) float64
+    live: torch.Tensor | None        # (S) int32
+
+
+class BatchStats:
+    """Accumulators of saev_batch_stats (include/saev_amd.h: BATCH STATISTICS) and its workspace, as torch tensors that alias
+    ONE device buffer: ``sums`` = [extra (8) | scalars (8) | col_sum (D)] float64 -- ``extra`` belongs to the caller, so that
+    a data-parallel run reduces its own per-batch scalars and the kernel's sums in one ``all_reduce`` --, then ``value_sum``
+    (S float64), ``n_pos`` (S int64), ``live`` (S int32).  ``want`` names the outputs to keep; the others are not computed
+    (without ``scalars`` and ``col_sum`` the pass over x and x_hat does not run at all).  ``add`` accumulates a batch, ``read`` is one device-to-host copy of everything."""
+
+    OUTPUTS = ("scalars", "col_sum", "n_pos", "value_sum", "live")
+
+    def __init__(self, d_model: int, d_sae: int, device, *, want=OUTPUTS, live_eps: float = 1e-12):
+        unknown = set(want) - set(self.OUTPUTS)
+        if unknown:
+            raise ValueError(f"BatchStats: unknown outputs {sorted(unknown)} (known: {self.OUTPUTS})")
+        if d_model < 4 or d_model > 4096 or d_model % 4:
+            raise ValueError(f"BatchStats: unsupported d_model {d_model} (4 <= D <= 4096, D % 4 == 0)")
+        self.lib = _lib.load()
+        self.d_model, self.d_sae, self.live_eps = d_model, d_sae, live_eps
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        D, S = d_model, d_sae
+        sizes = [("extra", 8 * 8), ("scalars", 8 * 8), ("col_sum", 8 * D if "col_sum" in want else 0),
+                 ("value_sum", 8 * S if "value_sum" in want else 0), ("n_pos", 8 * S if "n_pos" in want else 0),
+                 ("live", 4 * S if "live" in want else 0)]
+        self._spans, off = {}, 0
+        for name, nbytes in sizes:
+            self._spans[name] = (off, off + nbytes)
+            off += nbytes
+        self.buf = torch.zeros(off, device=self.device, dtype=torch.uint8)
+        dtypes = {"extra": torch.float64, "scalars": torch.float64, "col_sum": torch.float64, "value_sum": torch.float64,
+                  "n_pos": torch.int64, "live": torch.int32}
+        self._dtypes = dtypes
+        for name, (lo, hi) in self._spans.items():
+            setattr(self, name, self.buf[lo:hi].view(dtypes[name]) if hi > lo else None)
+        self.sums = self.buf[:self._spans["col_sum"][1]].view(torch.float64)
+        self._ws = None
+        self._acc = _lib.SaevBatchAcc(struct_size=C.sizeof(_lib.SaevBatchAcc), flags=0, live_eps=live_eps,
+                                      col_sum=_ptr(self.col_sum), scalars=_ptr(self.scalars) if "scalars" in want else None, n_pos=_ptr(self.n_pos),
+                                      value_sum=_ptr(self.value_sum), live=_ptr(self.live))
+
+    def zero_(self) -> "BatchStats":
+        self.buf.zero_()
+        return self
+
+    def _workspace(self, n: int):
+        need = int(self.lib.saev_batch_stats_workspace_bytes(n, self.d_model))
+        if need < 0:
+            raise _lib.SaevError(f"saev_batch_stats: unsupported shape n={n}, d_model={self.d_model}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        return self._ws
+
+    def _add_ptrs(self, x, x_hat, idx, val, row_nnz, keep, n: int, cap: int, overwrite: bool, scalars: bool = True):
+        if keep is not None:
+            if keep.dtype == torch.bool:
+                keep = keep.view(torch.uint8)
+            if keep.dtype != torch.uint8 or keep.shape != (n,) or keep.device != self.device or not keep.is_contiguous():
+                raise ValueError(f"keep must be a contiguous bool / uint8 vector of {n} rows on {self.device}")
+        ws = self._workspace(n)
+        acc = self._acc
+        if not scalars and acc.scalars:  # (this batch's scalar sums come from elsewhere: the step's own statistics)
+            acc = _lib.SaevBatchAcc.from_buffer_copy(acc)
+            acc.scalars = None
+        acc.flags = _lib.BATCH_OVERWRITE if overwrite else 0
+        with torch.cuda.device(self.device):
+            rc = self.lib.saev_batch_stats(x, x_hat, idx, val, row_nnz, _ptr(keep), n, self.d_model, self.d_sae, cap,
+                                           C.byref(acc), _ptr(ws), ws.numel(), _stream())
+        _lib.check(self.lib, None, rc, "saev_batch_stats")
+
+    def add(self, x: torch.Tensor, x_hat: torch.Tensor | None, idx: torch.Tensor | None, val: torch.Tensor | None,
+            row_nnz: torch.Tensor | None = None, keep: torch.Tensor | None = None, *, overwrite: bool = False,
+            scalars: bool = True) -> None:
+        """One batch: x, x_hat (n, D) float32; padded code rows idx (n, cap) int32 / val (n, cap) float32 with row_nnz (n) int32
+        (None: full rows); keep (n) bool.  ``overwrite`` stores instead of adding (``live`` is never cleared);
+        ``scalars=False`` leaves the scalar sums out of this batch."""
+        def chk(t, dtype, shape, what):
+            if t is None:
+                return None
+            if t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device:
+                raise ValueError(f"{what} must be {dtype} of shape {shape} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            return t.contiguous()
+        if x.ndim != 2:
+            raise ValueError(f"x must be (n, {self.d_model}), got {tuple(x.shape)}")
+        n = x.shape[0]
+        x = chk(x, torch.float32, (n, self.d_model), "x")
+        x_hat = chk(x_hat, torch.float32, (n, self.d_model), "x_hat")
+        if (idx is None) != (val is None):
+            raise ValueError("idx and val come together")
+        cap = 0 if idx is None else idx.shape[-1]
+        idx = chk(idx, torch.int32, (n, cap), "idx")
+        val = chk(val, torch.float32, (n, cap), "val")
+        row_nnz = chk(row_nnz, torch.int32, (n,), "row_nnz")
+        self._add_ptrs(_ptr(x), _ptr(x_hat), _ptr(idx), _ptr(val), _ptr(row_nnz), keep, n, cap, overwrite, scalars)
+
+    def read(self) -> BatchStatsHost:
+        h = self.buf.cpu()  # the one device-to-host copy
+        part = {name: (h[lo:hi].view(self._dtypes[name]) if hi > lo else None) for name, (lo, hi) in self._spans.items()}
+        n_kept, sx, sxx, sr, srr = part["scalars"][:5].tolist()
+        return BatchStatsHost(n_kept=n_kept, sum_x=sx, sum_xx=sxx, sum_r=sr, sum_rr=srr, extra=part["extra"], col_sum=part["col_sum"],
+                              n_pos=part["n_pos"], value_sum=part["value_sum"], live=part["live"])
+
+
 @dataclasses.dataclass
 class StepStats:
     mse: float
@@ -270,6 +411,7 @@ class SaeEngine:
             self._chk(self.lib.saev_bind_sumsq(ctx, _ptr(self.sumsq)), "saev_bind_sumsq")
         self.adam_steps = 0
         self._x_keepalive = None
+        self._last_n = 0  # rows of the last step_forward (0: none, or a fused step ran since)
         self._w_enc_t = None
         # ReLU rows: capacity of the next encode_relu (grows to the largest count seen) and how many calls needed a second launch
         self.relu_row_cap = min(cfg.d_sae, 512)
@@ -500,6 +642,7 @@ class SaeEngine:
         self._note_param_writes()
         n = x.shape[0]
         self._chk(self.lib.saev_step_forward(self.ctx, _ptr(x), n, n_rows_global or n, int(training), _stream()), "saev_step_forward")
+        self._last_n = n
 
     def step_dead(self, n_rows_global: int):
         self._topk_only("step_dead")
@@ -639,6 +782,7 @@ class SaeEngine:
         self._x_keepalive = x
         self._note_param_writes()
         self._chk(self.lib.saev_train_step(self.ctx, _ptr(x), x.shape[0], lr, max_norm, self.adam_steps + 1, _stream()), "saev_train_step")
+        self._last_n = 0
         self.adam_steps += 1  # (counted once the step is enqueued: a refused call -- SAEV_STALE_PARAMS -- is not an optimizer step)
 
     # data parallel behind the C ABI (include/saev_amd.h: DATA PARALLEL): RCCL inside the library, two collectives per step
@@ -665,6 +809,7 @@ class SaeEngine:
         self._x_keepalive = x
         self._note_param_writes()
         self._chk(self.lib.saev_train_step_dp(self.ctx, _ptr(x), x.shape[0], lr, max_norm, self.adam_steps + 1, _stream()), "saev_train_step_dp")
+        self._last_n = 0
         self.adam_steps += 1  # (counted once the step is enqueued: a refused call -- SAEV_STALE_PARAMS -- is not an optimizer step)
 
     def train_step_gather(self, pool: torch.Tensor, rows: torch.Tensor, lr: float, max_norm: float = 1.0, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -682,6 +827,7 @@ class SaeEngine:
         self._note_param_writes()
         self._chk(self.lib.saev_train_step_gather(self.ctx, _ptr(pool), _ptr(rows), _ptr(out), n, lr, max_norm, self.adam_steps + 1, _stream()),
                   "saev_train_step_gather")
+        self._last_n = 0
         self.adam_steps += 1
         return out
 
@@ -690,11 +836,27 @@ class SaeEngine:
         self._chk(self.lib.saev_read_stats(self.ctx, C.byref(st), _stream()), "saev_read_stats")
         return StepStats(**{f: getattr(st, f) for f, _ in _lib.SaevStepStats._fields_})
 
-    def last_codes(self, n_rows: int):
+    def add_batch_stats(self, acc: BatchStats, x: torch.Tensor, keep: torch.Tensor | None = None, *, overwrite: bool = False,
+                        x_hat: bool = True, scalars: bool = True) -> None:
+        """Accumulate the statistics of the last ``step_forward`` -- whose batch ``x`` was -- into ``acc`` straight from the
+        context's own codes and reconstruction (saev_last_idx / _val / _x_hat): no copy of either is made.  ``x_hat=False``
+        leaves the reconstruction unread (the residual sums then add 0); ``scalars=False`` leaves the scalar sums out."""
+        self._topk_only("add_batch_stats")
+        x = self._check_x(x)
+        if self._last_n == 0 or x.shape[0] != self._last_n:
+            raise _lib.SaevError(f"add_batch_stats: x has {x.shape[0]} rows, the last step_forward had {self._last_n or 'none'}")
+        if acc.d_model != self.cfg.d_model or acc.d_sae != self.cfg.d_sae or acc.device != self.device:
+            raise _lib.SaevError("add_batch_stats: the accumulator was made for another shape or device")
+        p = lambda v: C.c_void_p(v)  # noqa: E731
+        acc._add_ptrs(_ptr(x), p(self.lib.saev_last_x_hat(self.ctx)) if x_hat else None, p(self.lib.saev_last_idx(self.ctx)),
+                      p(self.lib.saev_last_val(self.ctx)), None, keep, x.shape[0], min(self.cfg.top_k, self.cfg.d_sae), overwrite, scalars)
+
+    def last_codes(self, n_rows: int, *, x_hat: bool = True):
+        """Copies of the last forward's codes and (unless ``x_hat=False``: None then) reconstruction."""
         k = min(self.cfg.top_k, self.cfg.d_sae)
         idx = torch.empty(n_rows, k, device=self.device, dtype=torch.int32)
         val = torch.empty(n_rows, k, device=self.device, dtype=torch.float32)
-        x_hat = torch.empty(n_rows, self.cfg.d_model, device=self.device, dtype=torch.float32)
+        x_hat = torch.empty(n_rows, self.cfg.d_model, device=self.device, dtype=torch.float32) if x_hat else None
         self._chk(self.lib.saev_copy_last(self.ctx, n_rows, _ptr(idx), _ptr(val), _ptr(x_hat), _stream()), "saev_copy_last")
         return idx, val, x_hat
 

@@ -32,6 +32,7 @@ import torch
 
 from .. import disk, nn
 from ..data import Metadata, OrderedConfig, OrderedDataLoader
+from ..engine import BatchStats
 from ..metrics import Metrics
 
 logger = logging.getLogger("inference.py")
@@ -127,17 +128,16 @@ def worker_fn(cfg: Config):
     eng = sae._eng(batch_size)
     relu = isinstance(sae.cfg.activation, nn.modeling.Relu)
 
+    # every sum of the pass -- column sums of x, sum x^2 and sum (x - x_hat)^2 over the kept rows in fp64, per-latent positive
+    # counts and value sums -- from one kernel per batch, TopK or ReLU, masked or not (engine.BatchStats)
+    acc = BatchStats(D, S, device, want=("scalars", "col_sum", "n_pos", "value_sum") if cfg.save else ("scalars", "col_sum"))
     if cfg.save:
-        value_sum = torch.zeros(S, device=device)
-        n_pos = torch.zeros(S, device=device)
         distributions = np.zeros((loader.n_samples, cfg.n_dists), dtype=np.float32)
         csr_data: list[np.ndarray] = []
         csr_cols: list[np.ndarray] = []
         csr_counts: list[np.ndarray] = []
     ignore = torch.tensor(cfg.ignore_labels, dtype=torch.int64)
-    sse = torch.zeros((), dtype=torch.float64, device=device)
-    sum_sq = torch.zeros((), dtype=torch.float64, device=device)
-    sum_vec = torch.zeros(D, dtype=torch.float64, device=device)
+    sse_own, sum_sq_own = 0.0, 0.0  # unmasked TopK batches: the step's own fp64 reductions
     n_tokens = 0
     prev_i = -1
     logger.info("Loaded SAE and data.")
@@ -150,7 +150,6 @@ def worker_fn(cfg: Config):
             x_hat = eng.decode_rows(idx, val, row_nnz)[:, 0]
         else:
             eng.step_forward(x, training=False)
-            idx, val, x_hat = eng.last_codes(b)
         keep_host = torch.ones(b, dtype=torch.bool)
         if "token_labels" in batch:  # segmentation caches: drop tokens whose label is ignored
             keep_host = torch.isin(batch["token_labels"], ignore, invert=True)
@@ -158,19 +157,20 @@ def worker_fn(cfg: Config):
         n_tokens += n_keep
         keep = keep_host.to(device)
         if n_keep > 0:
-            if n_keep == b and not relu:
+            mask = None if n_keep == b else keep
+            if relu:
+                acc.add(x, x_hat, idx, val, row_nnz, mask)
+            elif mask is None:
                 st = eng.read_stats()  # fp64 sums of this batch from the step's own reduction
-                sse += st.sse
-                sum_sq += st.sum_sq
-                sum_vec += x.to(torch.float64).sum(dim=0)
+                sse_own += st.sse
+                sum_sq_own += st.sum_sq
+                eng.add_batch_stats(acc, x, x_hat=False, scalars=False)
             else:
-                x64 = x[keep].to(torch.float64)
-                diff = x64 - x_hat[keep].to(torch.float64)
-                sse += (diff * diff).sum()
-                sum_sq += (x64 * x64).sum()
-                sum_vec += x64.sum(dim=0)
+                eng.add_batch_stats(acc, x, mask)
         if not cfg.save:
             continue
+        if not relu:
+            idx, val, _ = eng.last_codes(b, x_hat=False)
 
         g = batch["example_idx"] * T + batch["token_idx"]
         assert g[0].item() == prev_i + 1 and bool((g[1:] == g[:-1] + 1).all()), "batches must arrive in global order"
@@ -181,8 +181,6 @@ def worker_fn(cfg: Config):
         else:
             live = (val != 0) & keep[:, None]  # what a dense -> CSR conversion of the masked f_x would keep
         cols, vals = idx[live].long(), val[live]
-        value_sum.index_add_(0, cols, vals)
-        n_pos.index_add_(0, cols, (vals > 0).to(torch.float32))
         csr_counts.append(live.sum(dim=1).cpu().numpy())
         csr_cols.append(cols.to(torch.int32).cpu().numpy())
         csr_data.append(vals.cpu().numpy())
@@ -193,6 +191,7 @@ def worker_fn(cfg: Config):
         head[rows, idx[small].long()] = val[small]
         distributions[batch["example_idx"][keep_host].numpy()] = head.cpu().numpy()[keep_host.numpy()]
 
+    got = acc.read()
     if cfg.save:
         counts = np.concatenate(csr_counts) if csr_counts else np.zeros(0, dtype=np.int64)
         indptr = np.zeros(counts.shape[0] + 1, dtype=np.int64)
@@ -204,16 +203,17 @@ def worker_fn(cfg: Config):
              (np.concatenate(csr_cols) if csr_cols else np.zeros(0, np.int32)).astype(itype), indptr.astype(itype)),
             shape=(counts.shape[0], S))
         scipy.sparse.save_npz(fpaths.token_acts, token_acts)
-        torch.save((value_sum / n_pos).cpu(), fpaths.mean_values)
-        torch.save((n_pos / loader.n_samples).cpu(), fpaths.sparsity)
+        torch.save((got.value_sum / got.n_pos.to(torch.float64)).to(torch.float32), fpaths.mean_values)  # 0 / 0 = NaN: never positive
+        torch.save(got.n_pos.to(torch.float32) / loader.n_samples, fpaths.sparsity)
         torch.save(torch.from_numpy(distributions), fpaths.distributions)
 
     assert n_tokens > 0, "Inference dataloader yielded zero valid tokens; cannot compute metrics."
-    sse_baseline = sum_sq.item() - torch.dot(sum_vec, sum_vec).item() / n_tokens
+    sse, sum_sq, sum_vec = sse_own + got.sum_rr, sum_sq_own + got.sum_xx, got.col_sum
+    sse_baseline = sum_sq - torch.dot(sum_vec, sum_vec).item() / n_tokens
     if sse_baseline <= 0.0:
         raise RuntimeError(
             f"Baseline variance is non-positive (sse_baseline={sse_baseline:.6e}); cannot compute normalized MSE.")
-    metrics = Metrics.from_accumulators(sse_recon=sse.item(), sse_baseline=sse_baseline, n_tokens=n_tokens, d_model=D)
+    metrics = Metrics.from_accumulators(sse_recon=sse, sse_baseline=sse_baseline, n_tokens=n_tokens, d_model=D)
     with open(fpaths.metrics, "w") as fd:
         json.dump(metrics.to_dict(), fd, indent=2)
     return metrics

@@ -36,7 +36,7 @@ from .. import nn
 from ..nn import modeling, objectives
 from ..utils import scheduling
 from ..utils.statistics import batch_entropy
-from ..engine import MuonConfig, dictionary_coherence
+from ..engine import BatchStats, MuonConfig, dictionary_coherence, row_norm_mean
 from .ddp import DataParallelStepper
 
 logger = logging.getLogger("train")
@@ -327,7 +327,7 @@ def _loader_spread(batch, dataloader, dist=None, world: int = 1) -> dict[str, fl
 def _decoder_metrics(sae, cfg: Config) -> dict[str, object]:
     """The two log-block metrics that look at W_dec.  The reference evaluates them after the backward and BEFORE the
     optimizer step (train.py:365-442 precedes opt.step() at :444), i.e. on the rows normalised at the top of the step."""
-    out = {"metrics/avg_decoder_row_norm": sae.W_dec.norm(dim=1).mean().item()}
+    out = {"metrics/avg_decoder_row_norm": row_norm_mean(sae.W_dec)}
     if cfg.log_coherence:
         out["metrics/dictionary_coherence"] = _coherence(sae.W_dec)
     return out
@@ -340,29 +340,27 @@ def _log_metrics(sae, eng, x: Tensor, lr: float, n_patches_seen: int, cfg: Confi
     the batch is the union of the ranks' shards: every quantity is formed from sums that are all-reduced first (one
     collective of D + 8 doubles and one of d_sae flags per log step), so all ranks log the global-batch values."""
     st = eng.read_stats()
-    n = x.shape[0]
-    idx, val, x_hat = eng.last_codes(n)
-    x64 = x.to(torch.float64)
-    residual = x - x_hat
-    r64 = residual.to(torch.float64)
-    # [sum_vec (D) | sum x | sum r | sum r^2 (centred later) | sse | sum_sq | mse | aux | l0 | l1 | n]
-    sums = torch.cat([x64.sum(dim=0), torch.stack([x64.sum(), r64.sum(), (r64 * r64).sum()]),
-                      torch.tensor([st.sse, st.sum_sq, st.mse * n, st.aux * n, st.l0 * n, st.l1 * n, float(n)],
-                                   dtype=torch.float64, device=x.device)])
-    live = torch.zeros(sae.cfg.d_sae, device=x.device, dtype=torch.int32)
-    live[idx[val.abs() > 1e-12].long()] = 1
-    if dist is not None:
-        dist.all_reduce(sums, op=dist.ReduceOp.SUM)
-        dist.all_reduce(live, op=dist.ReduceOp.MAX)
-    D = x.shape[1]
-    sum_vec, (sx, sr, srr, sse, sum_sq, mse_n, aux_n, l0_n, l1_n, n_all) = sums[:D], sums[D:].tolist()
+    n, D = x.shape
+    # one pass over x, the context's own x_hat and its codes (engine.BatchStats, DESIGN.md 3.12): the column sums, sum x,
+    # sum x^2, sum r, sum r^2 (r = x - x_hat) in fp64 and the live flags -- no copy, no n x D temporary
+    acc = getattr(eng, "_log_acc", None)
+    if acc is None:
+        acc = eng._log_acc = BatchStats(D, sae.cfg.d_sae, x.device, want=("scalars", "col_sum", "live"), live_eps=1e-12)
+    acc.zero_()
+    eng.add_batch_stats(acc, x)
+    own = [st.sse, st.sum_sq, st.mse * n, st.aux * n, st.l0 * n, st.l1 * n, float(n)]
+    if dist is not None:  # the step's own scalars ride in the accumulator's caller slots: one SUM, one MAX
+        acc.extra[:7].copy_(torch.tensor(own, dtype=torch.float64))
+        dist.all_reduce(acc.sums, op=dist.ReduceOp.SUM)
+        dist.all_reduce(acc.live, op=dist.ReduceOp.MAX)
+    h = acc.read()
+    sse, sum_sq, mse_n, aux_n, l0_n, l1_n, n_all = own if dist is None else h.extra[:7].tolist()
+    sum_vec, live = h.col_sum, h.live
     sse_baseline = sum_sq - torch.dot(sum_vec, sum_vec).item() / n_all
     assert sse_baseline > 0, f"Batch baseline variance non-positive: sse_baseline={sse_baseline:.6e}"
-    if dist is None:  # the reference's own expression, in fp32 (train.py:402)
-        explained = (1 - residual.var() / x.var()).item()
-    else:  # same quantity from the reduced sums (unbiased variances over all n_all * D elements)
-        m = n_all * D
-        explained = 1 - ((srr - sr * sr / m) / (m - 1)) / ((sum_sq - sx * sx / m) / (m - 1))
+    # 1 - var(r) / var(x), unbiased variances over all n_all * D elements, from the fp64 sums
+    m = n_all * D
+    explained = 1 - ((h.sum_rr - h.sum_r * h.sum_r / m) / (m - 1)) / ((h.sum_xx - h.sum_x * h.sum_x / m) / (m - 1))
     mse, aux = mse_n / n_all, aux_n / n_all
     fill = dataloader.reservoir.fill() if getattr(dataloader, "reservoir", None) is not None else 1.0
     return {
@@ -432,17 +430,14 @@ def evaluate(cfgs: list[Config], saes: torch.nn.ModuleList, objs: torch.nn.Modul
     n_val = min(dataloader.n_samples, cfg.n_val)
     limiter = scheduling.BatchLimiter(dataloader, n_val, rows_scale=world)
     S, D = saes[0].cfg.d_sae, saes[0].cfg.d_model
-    n_fired = torch.zeros(len(cfgs), S, device=device)
-    values = torch.zeros(len(cfgs), S, device=device)
-    acc = torch.zeros(len(cfgs), 4, dtype=torch.float64, device=device)  # l0*b, l1*b, mse*b, sse
-    sum_sq = torch.zeros((), dtype=torch.float64, device=device)
-    sum_vec = torch.zeros(D, dtype=torch.float64, device=device)
+    # per SAE: positive counts (int64) and value sums (fp64) per latent; member 0 also the column sums of x (engine.BatchStats)
+    stats = [BatchStats(D, S, device, want=("col_sum", "n_pos", "value_sum") if i == 0 else ("n_pos", "value_sum")) for i in range(len(cfgs))]
+    acc = torch.zeros(len(cfgs), 4, dtype=torch.float64)  # l0*b, l1*b, mse*b, sse
+    sum_sq = torch.zeros((), dtype=torch.float64)
     n_tokens = 0
     for batch in limiter:
         x = batch["act"]
         b = x.shape[0]
-        x64 = x.to(torch.float64)
-        sum_vec += x64.sum(dim=0)
         n_tokens += b
         for i, (sae, obj) in enumerate(zip(saes, objs)):
             eng = obj._bind(sae, b)
@@ -452,22 +447,22 @@ def evaluate(cfgs: list[Config], saes: torch.nn.ModuleList, objs: torch.nn.Modul
             st = eng.read_stats()
             if i == 0:
                 sum_sq += st.sum_sq
-            idx, val, _ = eng.last_codes(b)
-            pos = val > 0
-            n_fired[i].index_add_(0, idx[pos].long(), torch.ones_like(val[pos]))
-            values[i].index_add_(0, idx.reshape(-1).long().clamp_min(0), val.reshape(-1))
-            acc[i] += torch.tensor([st.l0 * b, st.l1 * b, st.mse * b, st.sse], dtype=torch.float64, device=device)
+            eng.add_batch_stats(stats[i], x, x_hat=False)
+            acc[i] += torch.tensor([st.l0 * b, st.l1 * b, st.mse * b, st.sse], dtype=torch.float64)
     if dist is not None:
-        t = torch.tensor([float(n_tokens)], dtype=torch.float64, device=device)
-        for buf in (n_fired, values, acc, sum_sq, sum_vec, t):
+        host = torch.cat([acc.reshape(-1), sum_sq.reshape(1), torch.tensor([float(n_tokens)], dtype=torch.float64)]).to(device)
+        for buf in [host, stats[0].sums] + [t for s in stats for t in (s.n_pos, s.value_sum)]:
             dist.all_reduce(buf, op=dist.ReduceOp.SUM)
-        n_tokens = int(t.item())
+        host = host.cpu()
+        acc, sum_sq, n_tokens = host[:-2].reshape(len(cfgs), 4), host[-2], int(host[-1].item())
     assert n_tokens > 0, "Validation dataloader yielded zero tokens; cannot compute normalized MSE."
+    read = [s.read() for s in stats]
+    sum_vec = read[0].col_sum
     sse_baseline = (sum_sq - torch.dot(sum_vec, sum_vec) / n_tokens).item()
     assert sse_baseline > 0, f"Validation baseline variance non-positive: sse_baseline={sse_baseline:.6e}"
-    freqs = (n_fired / n_tokens).cpu()
-    mean_values = (values / n_fired).cpu()
-    acc = acc.cpu()
+    n_fired = torch.stack([r.n_pos for r in read])
+    freqs = n_fired.to(torch.float32) / n_tokens
+    mean_values = (torch.stack([r.value_sum for r in read]) / n_fired.to(torch.float64)).to(torch.float32)  # 0 / 0 = NaN: never fired
     out = []
     for i in range(len(cfgs)):
         out.append(EvalMetrics(

@@ -2,6 +2,7 @@
 shards -> feed (streaming reservoir or resident pool) -> train step, one epoch each.
 
     python tools/bench_train_e2e.py --gb 12 --root /dev/shm
+    python tools/bench_train_e2e.py --gb 12 --root /dev/shm --modes resident --log-every 25   # with the log block (coherence on)
 
 The cache is page-cache hot, so the streaming number is the framework's ceiling, not a disk measurement.  make_saes
 (reference train.py:108-189) consumes the first batches; the rate is over the train loop only."""
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--dead-threshold", type=int, default=10_000_000)
     ap.add_argument("--modes", nargs="+", default=["streaming", "resident"])
+    ap.add_argument("--log-every", type=int, default=10**9, help="log block every this many steps (default: never, the bare loop)")
     a = ap.parse_args()
     D, Tk = a.d_model, a.tokens
     n_ex = int(a.gb * 1e9 / (4 * D * (Tk + 1)))
@@ -51,7 +53,7 @@ def main():
                 train_data=dcfg, val_data=dcfg, n_train=n_rows * a.epochs, n_val=a.batch,
                 sae=nn.SparseAutoencoderConfig(d_model=D, d_sae=D * a.exp, reinit_blend=0.0,
                                                activation=modeling.TopK(top_k=a.top_k)),
-                objective=objectives.Matryoshka(n_prefixes=1, dead_threshold_tokens=a.dead_threshold), log_every=10**9, track=False,
+                objective=objectives.Matryoshka(n_prefixes=1, dead_threshold_tokens=a.dead_threshold), log_every=a.log_every, track=False,
                 runs_root=os.path.join(root, "runs"), device="cuda")
             import saev_amd.utils.scheduling as sched
             t_loop = {}
