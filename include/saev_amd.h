@@ -1,5 +1,5 @@
 /*
- * saev_amd.h — C ABI of libsaev_amd.so: the MI355X (gfx950) TopK-SAE train-step path.
+ * saev_amd.h — C ABI of libsaev_amd.so: the MI355X (gfx950) TopK / BatchTopK SAE train-step path and the ReLU forward.
  *
  * This is the drop-in boundary for the hot path of OSU-NLP-Group/saev.  The reference has no FFI of
  * its own (it is pure PyTorch); each entry point below names the reference code it replaces
@@ -36,8 +36,11 @@ typedef enum {
     SAEV_UNSUPPORTED = -3,
     SAEV_NOT_BOUND = -4,
     SAEV_RCCL_ERROR = -5,
-    SAEV_STALE_PARAMS = -6 /* W_enc was written outside the library without saev_params_touched and a step has already run on
+    SAEV_STALE_PARAMS = -6, /* W_enc was written outside the library without saev_params_touched and a step has already run on
                               stale operand images (PARAMETER OWNERSHIP below); the context itself recovers */
+    SAEV_ROW_OVERFLOW = -7  /* BatchTopK: a row of the forward has more codes than the context's row_cap.  Nothing was decoded, the
+                               threshold was not updated, no step is in flight; saev_row_overflow_need gives the capacity that
+                               holds every row -- create a context with at least that row_cap and repeat the forward */
 } saev_status;
 
 /* Static configuration of one SAE (nn/modeling.py:259-284 SparseAutoencoderConfig, :119-130 TopK,
@@ -75,7 +78,7 @@ typedef struct {
                                       the rows of ALL data-parallel ranks); sizes only the backward's pair order, slice-major
                                       copies and partial rows -- the forward's buffers (candidate lists, dense fallback,
                                       AuxK, ...) stay at max_batch, which is then the LOCAL batch.                      */
-    int32_t activation;            /* SAEV_ACT_TOPK (0) or SAEV_ACT_RELU.  A ReLU context (nn/modeling.py:111-113 Relu, :150-156
+    int32_t activation;            /* SAEV_ACT_TOPK (0), SAEV_ACT_RELU or SAEV_ACT_BATCHTOPK (BATCHTOPK below).  A ReLU context (nn/modeling.py:111-113 Relu, :150-156
                                       ReluActivation) ignores top_k and needs k_aux = 0; it runs the forward entries only:
                                       saev_encode_relu, saev_decode_rows, saev_scatter_rows and the single ops, while the
                                       step entries and saev_encode_topk return SAEV_UNSUPPORTED (training a ReLU SAE is not
@@ -84,6 +87,7 @@ typedef struct {
 
 #define SAEV_ACT_TOPK 0
 #define SAEV_ACT_RELU 1
+#define SAEV_ACT_BATCHTOPK 2
 
 /* Element offsets of the four tensors inside each flat buffer, its total length, and the per-rank chunk lengths of the
  * two halves (all in floats) for this configuration.  Without shard_world: off_W_dec 0, off_b_dec S*D, off_W_enc
@@ -183,6 +187,62 @@ int saev_create(const saev_cfg* cfg, int device, saev_ctx** out);
 /* The same with route switches (dbg may be NULL = all defaults). */
 int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, saev_ctx** out);
 void saev_destroy(saev_ctx* ctx);
+
+/* BATCHTOPK (nn/modeling.py:132-140 BatchTopK, :183-244 BatchTopKActivation; nn/objectives.py:101-156).  saev_cfg.activation =
+ * SAEV_ACT_BATCHTOPK; saev_cfg.top_k keeps its meaning, codes per row ON AVERAGE.  For h = x W_enc + b_enc of shape (n, S):
+ *   training   the T = min(top_k n, S n) largest entries of the flattened h by signed value are kept (negative and zero values too
+ *              when they are among the largest), f = h there and 0 elsewhere.  Ties at the cut are deterministic: among entries
+ *              EQUAL to the cut value, lower flat index (row-major) first (the reference's are unspecified).  Then
+ *              threshold <- (1 - momentum) threshold + momentum min{f : f > 0}, on every training-mode encode as in the reference;
+ *              a batch without a positive kept value leaves the threshold as it is (the reference raises there)
+ *   eval       f = h where h > threshold (h > 0 when threshold <= 0), elementwise; the threshold does not move
+ *   gradient   df/dh is the mask; the threshold carries none.  l0 counts f != 0, the dead-latent tracker |f| > 0; AuxK, Matryoshka
+ *              prefixes, the MSE rescale, remove_parallel_grads, the clip, Adam / Muon and renormalisation as for TopK.
+ * Codes are PADDED ROWS as for ReLU: idx / val (n x row_cap), row b's entries in its first row_nnz[b] slots in ascending latent
+ * order, the other slots idx = -1, val = 0.  row_cap is fixed per context (saev_batch_topk_cfg.row_cap; 0 = min(d_sae, max(64,
+ * 4 top_k)) rounded up to 64) and sizes everything a TopK context sizes by top_k.  OVERFLOW IS NEVER SILENT: a forward one of whose rows
+ * needs more slots returns SAEV_ROW_OVERFLOW before anything is decoded (and before the threshold moves, so a repeated training
+ * forward applies the update once); the forward reads one device word back per call to know (4 bytes, one synchronisation of the
+ * stream -- an open lever).  The count reported is taken BEFORE the tie rule drops cut-valued entries, so a batch with many ties at
+ * the cut may ask for more than its final rows hold.
+ * The select is exact (integer keys and counts, no floating-point atomics) and works on the dense h that the exact fp32 encoder
+ * writes (as saev_encode_dense); encoder_mode BF16 is SAEV_UNSUPPORTED.  On such a context saev_step_forward / _dead / _backward /
+ * _tail, saev_muon_tail and saev_train_step (= the four phases back to back) run; saev_encode_topk, saev_encode_relu,
+ * saev_share_x (either side), saev_train_step_gather, saev_train_step_dp, saev_backward_override, saev_copy_step_state and a
+ * backward over part of the latents return SAEV_UNSUPPORTED (a batch-wide top-k over several ranks needs a distributed select). */
+typedef struct {
+    int32_t struct_size;   /* sizeof(saev_batch_topk_cfg) of the caller (fields past it read as 0)                          */
+    int32_t row_cap;       /* slots per padded code row; 0 = the default above                                              */
+    double batch_momentum; /* EMA weight m of the threshold update (modeling.py:139), a double as the reference's Python float is:
+                              the kernel multiplies by float(1 - m) and float(m) as torch's mul_ / add_ do.  The default
+                              without this struct is 0.1                                                                    */
+    int32_t list_cap;      /* 0 = default.  Route switch for tests: capacity of the select's key list (a cut bin with more
+                              entries sends the select's later levels over h again; same result)                          */
+    int32_t reserved;
+} saev_batch_topk_cfg;
+/* saev_create_ex for a BatchTopK context with its own settings (bt NULL: the defaults, as saev_create_ex gives them). */
+int saev_create_batch_topk(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_batch_topk_cfg* bt, int device, saev_ctx** out);
+/* The threshold word (one device float, 0 at creation) is owned by the context unless the caller binds its own -- a torch buffer
+ * that aliases it, like the tracker (the value is NOT copied: seed the caller's word first). */
+int saev_bind_threshold(saev_ctx* ctx, float* threshold);
+float* saev_threshold_device(saev_ctx* ctx);
+int32_t saev_row_cap(const saev_ctx* ctx);             /* 0 unless BatchTopK */
+int32_t saev_row_overflow_need(const saev_ctx* ctx);   /* after SAEV_ROW_OVERFLOW: the largest row count met */
+/* The activation alone on a dense h (n x d_sae, 16-byte aligned, n <= max_batch) the caller holds: select + compaction (training != 0,
+ * threshold update included) or the threshold compaction, into idx_out / val_out (n x row_cap of the context) and row_nnz_out (n,
+ * exact also past row_cap).  *overflow_out (device int32) = 0, or the largest row count when that exceeds row_cap: the caller reads
+ * it back, as after saev_encode_relu; the threshold moves only when it is 0. */
+int saev_batch_topk_dense(saev_ctx* ctx, const float* h, int32_t n_rows, int32_t training, int32_t* row_nnz_out, int32_t* idx_out,
+                          float* val_out, int32_t* overflow_out, void* stream);
+/* modeling.py:343-347 encode + the activation, for encode / encode_sparse: the same on h = x W_enc + b_enc (exact fp32). */
+int saev_encode_batch_topk(saev_ctx* ctx, const float* x, int32_t n_rows, int32_t training, int32_t* row_nnz_out, int32_t* idx_out,
+                           float* val_out, int32_t* overflow_out, void* stream);
+/* What the last training-mode select left on the device, read back (synchronises `stream`): the cut value, the number of entries
+ * strictly above it, how many entries equal to it are kept (>= 1) and how many entries equal it. */
+int saev_batch_topk_state(saev_ctx* ctx, float* cut, int64_t* n_above, int64_t* tie_quota, int64_t* n_ties, void* stream);
+/* row_nnz (n_rows int32) of the last saev_step_forward of a BatchTopK context, copied like saev_copy_last copies the padded rows
+ * (idx / val there are n_rows x row_cap). */
+int saev_copy_last_row_nnz(saev_ctx* ctx, int32_t n_rows, int32_t* row_nnz_out, void* stream);
 
 /* Borrow the caller's flat buffers (see layout above).  grads/adam_m/adam_v may be NULL for a
  * forward-only context.  Pointers must stay valid until re-bound or destroy. */

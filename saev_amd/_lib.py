@@ -61,6 +61,15 @@ class SaevBatchAcc(C.Structure):
                 ("live", C.c_void_p)]
 
 
+class SaevBatchTopKCfg(C.Structure):
+    """include/saev_amd.h: saev_batch_topk_cfg (settings of a BatchTopK context beside saev_cfg; zeros = defaults)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("row_cap", C.c_int32), ("batch_momentum", C.c_double), ("list_cap", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+ACT_TOPK, ACT_RELU, ACT_BATCHTOPK = 0, 1, 2
+ROW_OVERFLOW = -7  # saev_status SAEV_ROW_OVERFLOW
 BATCH_OVERWRITE = 1
 ROW_NORM_WORKSPACE_BYTES = 8192
 
@@ -76,6 +85,15 @@ _SIGNATURES = {
     "saev_layout": (C.c_int, [C.POINTER(SaevCfg), C.POINTER(SaevLayout)]),
     "saev_create": (C.c_int, [C.POINTER(SaevCfg), C.c_int, C.POINTER(P)]),
     "saev_create_ex": (C.c_int, [C.POINTER(SaevCfg), C.POINTER(SaevDebugCfg), C.c_int, C.POINTER(P)]),
+    "saev_create_batch_topk": (C.c_int, [C.POINTER(SaevCfg), C.POINTER(SaevDebugCfg), C.POINTER(SaevBatchTopKCfg), C.c_int, C.POINTER(P)]),
+    "saev_bind_threshold": (C.c_int, [P, P]),
+    "saev_threshold_device": (P, [P]),
+    "saev_row_cap": (C.c_int32, [P]),
+    "saev_row_overflow_need": (C.c_int32, [P]),
+    "saev_batch_topk_dense": (C.c_int, [P, P, C.c_int32, C.c_int32, P, P, P, P, P]),
+    "saev_encode_batch_topk": (C.c_int, [P, P, C.c_int32, C.c_int32, P, P, P, P, P]),
+    "saev_batch_topk_state": (C.c_int, [P, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), P]),
+    "saev_copy_last_row_nnz": (C.c_int, [P, C.c_int32, P, P]),
     "saev_destroy": (None, [P]),
     "saev_bind": (C.c_int, [P, P, P, P, P]),
     "saev_bind_tracker": (C.c_int, [P, P, P]),

@@ -240,6 +240,15 @@ struct saev_ctx {
     int ov_n = 0;
     float* db_aux = nullptr;       // the auxiliary term's share of db_dec, kept apart while an override is active
     bool trust_grads = false;      // the caller vouches that nothing touches the gradient between backward and tail
+    // BatchTopK (include/saev_amd.h: BATCHTOPK; kernels in batchtopk.hip).  cfg.top_k of such a context is its ROW CAPACITY -- what
+    // every buffer and loop a TopK context sizes by top_k goes by -- and btk_k the configured codes per row on average.
+    bool btk = false;
+    int btk_k = 0, btk_list_cap = 0;
+    double btk_momentum = 0.1;
+    float *threshold = nullptr, *threshold_own = nullptr;  // the word in use (own, or caller-bound: saev_bind_threshold)
+    uint32_t* btk_ws = nullptr;       // select state, histograms, key list, per-row tie counters (btk_workspace_words)
+    int32_t *row_nnz = nullptr, *btk_over = nullptr;  // of the last forward; the overflow word
+    int btk_need = 0;                 // after SAEV_ROW_OVERFLOW: the largest row count met
     // state of the step in flight
     const float* x_last = nullptr;
     int n_last = 0;
@@ -346,9 +355,32 @@ const char* saev_last_error(const saev_ctx* ctx) { return ctx ? ctx->err.c_str()
 int saev_create(const saev_cfg* cfg, int device, saev_ctx** out) { return saev_create_ex(cfg, nullptr, device, out); }
 
 int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, saev_ctx** out) {
+    return saev_create_batch_topk(cfg, dbg, nullptr, device, out);
+}
+
+int saev_create_batch_topk(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_batch_topk_cfg* bt_in, int device, saev_ctx** out) {
     if (!cfg || !out) return SAEV_INVALID_ARG;
     *out = nullptr;
-    if (cfg->activation != SAEV_ACT_TOPK && cfg->activation != SAEV_ACT_RELU) return SAEV_INVALID_ARG;
+    if (cfg->activation != SAEV_ACT_TOPK && cfg->activation != SAEV_ACT_RELU && cfg->activation != SAEV_ACT_BATCHTOPK) return SAEV_INVALID_ARG;
+    const bool btk = cfg->activation == SAEV_ACT_BATCHTOPK;
+    if (bt_in != nullptr && !btk) return SAEV_INVALID_ARG;
+    saev_batch_topk_cfg bt{};
+    if (bt_in != nullptr && bt_in->struct_size > 0) std::memcpy(&bt, bt_in, std::min((size_t)bt_in->struct_size, sizeof(bt)));
+    else bt.batch_momentum = 0.1;
+    // a BatchTopK context: everything TopK sizes by top_k is sized by the row capacity instead
+    saev_cfg btk_cfg;
+    int btk_k = 0;
+    if (btk) {
+        if (cfg->top_k <= 0 || cfg->d_sae <= 0 || bt.row_cap < 0 || bt.list_cap < 0 || !(bt.batch_momentum >= 0.0 && bt.batch_momentum <= 1.0))
+            return SAEV_INVALID_ARG;
+        if (cfg->encoder_mode == SAEV_ENCODER_BF16 || cfg->shard_world > 1 || cfg->max_backward_rows > cfg->max_batch) return SAEV_UNSUPPORTED;
+        if ((uint64_t)cfg->max_batch * (uint64_t)cfg->d_sae >= (1ull << 31)) return SAEV_UNSUPPORTED;  // (32-bit counts of the select)
+        btk_k = std::min(cfg->top_k, cfg->d_sae);
+        const long want = bt.row_cap > 0 ? bt.row_cap : std::max(64L, 4L * btk_k);
+        btk_cfg = *cfg;
+        btk_cfg.top_k = (int32_t)std::min<long>(cfg->d_sae, (want + 63) / 64 * 64);
+        cfg = &btk_cfg;
+    }
     // a ReLU context (forward entries only) has no k: its TopK-sized scratch is sized for k = 1
     saev_cfg relu_cfg;
     if (cfg->activation == SAEV_ACT_RELU) {
@@ -371,6 +403,7 @@ int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, s
     if (dbg != nullptr && dbg->struct_size > 0)
         std::memcpy(&c->dbg, dbg, std::min((size_t)dbg->struct_size, sizeof(saev_debug_cfg)));
     c->device = device;
+    c->btk = btk; c->btk_k = btk_k; c->btk_momentum = bt.batch_momentum; c->btk_list_cap = bt.list_cap;
     if (hipSetDevice(device) != hipSuccess) {
         delete c;
         return SAEV_HIP_ERROR;
@@ -417,10 +450,10 @@ int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, s
     A(dW_encT, S * D); A(partials, (size_t)c->max_part * 2 * D); A(db_partials, c->max_part); A(row_proj, S); A(enc_sq, S);
     {
         const bool rows_only = c->dbg.dw_route == 1;
-        c->dws_ok = !rows_only && D % DWS_SLICE == 0 && (uint64_t)S * D * 4ull < (1ull << 32) && MBB < (1l << 24) &&
+        c->dws_ok = !rows_only && !btk && D % DWS_SLICE == 0 && (uint64_t)S * D * 4ull < (1ull << 32) && MBB < (1l << 24) &&
                     (uint64_t)MBB * K < (1ull << 31);
     }
-    c->fwd_slices = c->cfg.encoder_mode == SAEV_ENCODER_F16R && c->dbg.fwd_route == 0 && D % RS_SLICE == 0 &&
+    c->fwd_slices = !btk && c->cfg.encoder_mode == SAEV_ENCODER_F16R && c->dbg.fwd_route == 0 && D % RS_SLICE == 0 &&
                     (uint64_t)S * 128ull < (1ull << 32) - 256ull && fused_supported(c->cfg);
     if (c->fwd_slices) {
         A(rs_part, (size_t)(D / RS_SLICE) * MB * REFINE_CAP); A(surv_rng, MB * RS_MAX_RANGES);
@@ -461,6 +494,7 @@ int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, s
     if (c->stream_ok || c->cfg.encoder_mode == SAEV_ENCODER_BF16) A(wchk, (size_t)2 * ((S + 255) / 256) * ((D + 31) / 32));
     A(toks, S); A(fired, S); A(dead, S); A(flags, 16); A(upper, 1); A(stats, 1);
     A(tau_max, MB); A(heur_state, 8); A(stats_scratch, STATS_SCRATCH_DOUBLES); A(tickets, 8); A(db_aux, D);
+    if (btk) { A(btk_ws, btk_workspace_words((int)MB)); A(row_nnz, MB); A(btk_over, 1); A(threshold_own, 1); }
 #undef A
     if (rc != SAEV_OK) {
         // keep the context so the caller can read the message, but report failure
@@ -472,6 +506,12 @@ int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, s
     hipMemset(c->fired, 0, S * sizeof(int32_t));
     hipMemset(c->dead, 0, S * sizeof(int32_t));
     hipMemset(c->flags, 0, 16 * sizeof(int32_t));
+    if (btk) {
+        hipMemset(c->threshold_own, 0, sizeof(float));
+        hipMemset(c->btk_ws, 0, BTK_ST_WORDS * sizeof(uint32_t));
+        hipMemset(c->btk_over, 0, sizeof(int32_t));
+        c->threshold = c->threshold_own;
+    }
     if (c->stream_ok || c->cfg.encoder_mode == SAEV_ENCODER_BF16) {
         void* hp = nullptr;
         if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess &&
@@ -646,6 +686,7 @@ int saev_tracker_touched(saev_ctx* c) {
 int saev_share_x(saev_ctx* c, saev_ctx* leader) {
     if (!c) return SAEV_INVALID_ARG;
     if (leader == nullptr || leader == c) { unlink_from_leader(c); return SAEV_OK; }
+    REQUIRE(c, !c->btk && !leader->btk, SAEV_UNSUPPORTED, "saev_share_x: a BatchTopK context neither lends nor borrows");
     REQUIRE(c, leader->device == c->device && leader->cfg.d_model == c->cfg.d_model && leader->cfg.encoder_mode == c->cfg.encoder_mode,
             SAEV_INVALID_ARG, "saev_share_x: both contexts must live on one device with the same d_model and encoder mode");
     REQUIRE(c, leader->leader == nullptr, SAEV_INVALID_ARG, "saev_share_x: the leader must build its own x-derived buffers");
@@ -678,6 +719,39 @@ int saev_copy_last(saev_ctx* c, int32_t n_rows, int32_t* idx_out, float* val_out
     if (idx_out) HIPCHK(c, hipMemcpyAsync(idx_out, c->idx, nk * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (val_out) HIPCHK(c, hipMemcpyAsync(val_out, c->val, nk * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (x_hat_out) HIPCHK(c, hipMemcpyAsync(x_hat_out, c->x_hat, nd * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return SAEV_OK;
+}
+
+int saev_copy_last_row_nnz(saev_ctx* c, int32_t n_rows, int32_t* row_nnz_out, void* stream) {
+    if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->btk, SAEV_UNSUPPORTED, "saev_copy_last_row_nnz: the context is not a BatchTopK context");
+    REQUIRE(c, c->n_last > 0 && n_rows == c->n_last && row_nnz_out, SAEV_INVALID_ARG,
+            "saev_copy_last_row_nnz: n_rows differs from the batch of the last forward (or none has run)");
+    HIPCHK(c, hipMemcpyAsync(row_nnz_out, c->row_nnz, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SAEV_OK;
+}
+
+int saev_bind_threshold(saev_ctx* c, float* threshold) {
+    if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->btk, SAEV_UNSUPPORTED, "saev_bind_threshold: the context is not a BatchTopK context");
+    c->threshold = threshold != nullptr ? threshold : c->threshold_own;
+    return SAEV_OK;
+}
+float* saev_threshold_device(saev_ctx* c) { return c ? c->threshold : nullptr; }
+int32_t saev_row_cap(const saev_ctx* c) { return c && c->btk ? c->cfg.top_k : 0; }
+int32_t saev_row_overflow_need(const saev_ctx* c) { return c ? c->btk_need : 0; }
+
+int saev_batch_topk_state(saev_ctx* c, float* cut, int64_t* n_above, int64_t* tie_quota, int64_t* n_ties, void* stream) {
+    if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->btk, SAEV_UNSUPPORTED, "saev_batch_topk_state: the context is not a BatchTopK context");
+    uint32_t h[BTK_ST_WORDS];
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(c, hipMemcpyAsync(h, c->btk_ws, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (cut) std::memcpy(cut, &h[BTK_ST_CUT], sizeof(float));
+    if (n_above) *n_above = h[BTK_ST_ABOVE];
+    if (tie_quota) *tie_quota = h[BTK_ST_RANK];
+    if (n_ties) *n_ties = h[BTK_ST_TIES];
     return SAEV_OK;
 }
 
@@ -1069,7 +1143,8 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
 
 int saev_encode_topk(saev_ctx* c, const float* x, int32_t n, int32_t* idx_out, float* val_out, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_encode_topk: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED,
+            "saev_encode_topk: a TopK context only (ReLU: saev_encode_relu, BatchTopK: saev_encode_batch_topk)");
     REQUIRE(c, c->params, SAEV_NOT_BOUND, "parameters not bound");
     REQUIRE(c, x && idx_out && val_out && n > 0 && n <= c->cfg.max_batch, SAEV_INVALID_ARG,
             "saev_encode_topk: bad arguments (n_rows must be in 1..max_batch)");
@@ -1123,6 +1198,59 @@ int saev_decode_sparse(saev_ctx* c, const int32_t* idx, const float* val, int32_
                                        hipMemcpyDeviceToDevice, s));
     }
     return SAEV_OK;
+}
+
+// ---- BatchTopK activation (batchtopk.hip) --------------------------------------------------------
+
+namespace {
+// select + compaction (training) or threshold compaction over a dense h into padded rows of the context's row capacity
+int btk_codes(saev_ctx* c, const float* h, int n, int training, int32_t* row_nnz_out, int32_t* idx_out, float* val_out,
+              int32_t* overflow_out, hipStream_t s) {
+    BtkArgs a{};
+    a.h = h; a.n_rows = n; a.S = c->cfg.d_sae; a.top_k = c->btk_k; a.row_cap = c->cfg.top_k; a.training = training ? 1 : 0;
+    a.update_threshold = a.training; a.momentum = c->btk_momentum; a.threshold = c->threshold;
+    a.idx_out = idx_out; a.val_out = val_out; a.row_nnz_out = row_nnz_out; a.overflow = overflow_out;
+    a.ws = c->btk_ws; a.max_rows = c->cfg.max_batch; a.list_cap = c->btk_list_cap;
+    HIPCHK(c, launch_batch_topk(a, s));
+    return SAEV_OK;
+}
+// h = x W_enc + b_enc into the context's dense buffer: the exact fp32 kernel in the f32 and f16r modes, the split-fp16 one in f16x3
+int btk_dense_h(saev_ctx* c, const float* x, int n, hipStream_t s) {
+    if (c->cfg.encoder_mode != SAEV_ENCODER_F16R) {
+        int rc = prepare_encoder(c, x, n, nullptr, s);
+        if (rc != SAEV_OK) return rc;
+    } else {
+        int rc = wait_wenc(c, s);
+        if (rc != SAEV_OK) return rc;
+    }
+    return run_encoder(c, x, n, EPI_DENSE, c->h_dense, nullptr, 0, s);
+}
+}  // namespace
+
+int saev_batch_topk_dense(saev_ctx* c, const float* h, int32_t n, int32_t training, int32_t* row_nnz_out, int32_t* idx_out,
+                          float* val_out, int32_t* overflow_out, void* stream) {
+    if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->btk, SAEV_UNSUPPORTED, "saev_batch_topk_dense: the context is not a BatchTopK context");
+    REQUIRE(c, h && row_nnz_out && idx_out && val_out && overflow_out && n > 0 && n <= c->cfg.max_batch, SAEV_INVALID_ARG,
+            "saev_batch_topk_dense: bad arguments (n_rows must be in 1..max_batch)");
+    REQUIRE(c, ((uintptr_t)h % 16) == 0, SAEV_INVALID_ARG, "h must be 16-byte aligned");
+    return btk_codes(c, h, n, training, row_nnz_out, idx_out, val_out, overflow_out, (hipStream_t)stream);
+}
+
+int saev_encode_batch_topk(saev_ctx* c, const float* x, int32_t n, int32_t training, int32_t* row_nnz_out, int32_t* idx_out,
+                           float* val_out, int32_t* overflow_out, void* stream) {
+    if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, c->btk, SAEV_UNSUPPORTED, "saev_encode_batch_topk: the context is not a BatchTopK context");
+    REQUIRE(c, c->params, SAEV_NOT_BOUND, "parameters not bound");
+    REQUIRE(c, x && row_nnz_out && idx_out && val_out && overflow_out && n > 0 && n <= c->cfg.max_batch, SAEV_INVALID_ARG,
+            "saev_encode_batch_topk: bad arguments (n_rows must be in 1..max_batch)");
+    REQUIRE(c, ((uintptr_t)x % 16) == 0, SAEV_INVALID_ARG, "x must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    bind_x_sources(c, x, n, false);
+    c->xprep_x = nullptr;
+    int rc = btk_dense_h(c, x, n, s);
+    if (rc != SAEV_OK) return rc;
+    return btk_codes(c, c->h_dense, n, training, row_nnz_out, idx_out, val_out, overflow_out, s);
 }
 
 // ---- ReLU SAE forward (relu.hip) --------------------------------------------------------------
@@ -1202,7 +1330,7 @@ int saev_gather_rows(saev_ctx* c, const float* pool, const int64_t* rows, int32_
 int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_global, int32_t training,
                       void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_step_forward: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU, SAEV_UNSUPPORTED, "saev_step_forward: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params, SAEV_NOT_BOUND, "parameters not bound");
     REQUIRE(c, x && n > 0 && n <= c->cfg.max_batch, SAEV_INVALID_ARG,
             "saev_step_forward: n_rows must be in 1..max_batch");
@@ -1224,7 +1352,8 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
     c->wdec_ready = nullptr;
     // everything that depends on x alone comes from the context this one shares its batches with, if that one has just
     // built it for this very batch (saev_share_x); otherwise it is built here
-    const bool borrowed = bind_x_sources(c, x, n, true);
+    const bool btk = c->btk;  // (BatchTopK: nothing is shared, streamed or fused -- dense h, select, compaction, then the generic decode)
+    const bool borrowed = bind_x_sources(c, x, n, !btk);
     // The streamed preparation: this context neither lends nor borrows, a previous batch has left a centre, a scale
     // and a normaliser, and the operand images of W_enc describe the parameters as they are, centred on that very centre.
     if (c->stale_host != nullptr && reinterpret_cast<volatile int32_t*>(c->stale_host)[1] != 0) {
@@ -1261,7 +1390,7 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
         HIPCHK(c, launch_gather_rows(c->gather_pool, c->gather_rows, n, D, const_cast<float*>(x), s));
     if (c->stream_step) {
         c->xprep_x = nullptr;  // (xprep_kernel / pre_encode2_kernel, enqueued by encode_topk_impl, do all of the below)
-    } else if (!borrowed && c->cfg.encoder_mode == SAEV_ENCODER_F16R) {
+    } else if (!borrowed && !btk && c->cfg.encoder_mode == SAEV_ENCODER_F16R) {
         // one pass: max|x| for the MSE and the column sums the encoder centres on; the launch that finishes them also clears
         // the step's statistics and the force-dense flag (flags[0])
         c->xprep_x = nullptr;
@@ -1276,7 +1405,26 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
         }
     }
     (void)n_rows_global;
-    int rc = encode_topk_impl(c, x, n, c->idx, c->val, c->flags, s, c->upper_c, borrowed);
+    int rc;
+    if (btk) {
+        rc = btk_dense_h(c, x, n, s);
+        if (rc == SAEV_OK) rc = btk_codes(c, c->h_dense, n, training, c->row_nnz, c->idx, c->val, c->btk_over, s);
+        if (rc == SAEV_OK) {
+            // the step's one read-back: no row may be truncated, and nothing downstream can be sized on the device
+            int32_t need = 0;
+            HIPCHK(c, hipMemcpyAsync(&need, c->btk_over, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            if (need > 0) {
+                c->btk_need = need;
+                c->x_last = nullptr; c->n_last = 0; c->training_last = 0;  // no step is in flight: a backward or tail must not follow
+                c->err = "BatchTopK: a row holds " + std::to_string(need) + " codes, the context's row_cap is " + std::to_string(K) +
+                         " (create a context with a larger saev_batch_topk_cfg.row_cap and repeat the forward; the threshold has not moved)";
+                return SAEV_ROW_OVERFLOW;
+            }
+        }
+    } else {
+        rc = encode_topk_impl(c, x, n, c->idx, c->val, c->flags, s, c->upper_c, borrowed);
+    }
     if (rc != SAEV_OK) return rc;
     if (!borrowed) { c->xprep_x = x; c->xprep_n = n; c->xprep_serial++; }
     if (!borrowed && c->stream_ok && !c->stream_step && c->fwd_step) {
@@ -1333,7 +1481,7 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
     for (int p = 0; p < c->P; ++p) c->cuts_last[p] = c->cuts[p];  // a later saev_set_prefixes must not reach this step's backward
     // (list statistics from the candidate counters themselves unless the fused encoder is out of play or predicts bounds,
     // where overflow_check_kernel leaves them in flags[2..3])
-    const bool lists = fused_supported(c->cfg) && !(c->cfg.bound_mode != 0 && c->cfg.encoder_mode != SAEV_ENCODER_F32 && f16_ngroups(c) == 32);
+    const bool lists = !btk && fused_supported(c->cfg) && !(c->cfg.bound_mode != 0 && c->cfg.encoder_mode != SAEV_ENCODER_F32 && f16_ngroups(c) == 32);
     c->stats_pending = false;
     if (c->train_fused && training) {  // (saev_train_step: the tracker update that follows takes this reduction into its launch)
         c->stats_pending = true;
@@ -1853,6 +2001,8 @@ int saev_backward_rows_part(saev_ctx* c, int32_t lat_lo, int32_t lat_hi, int32_t
     const bool ov = c->ov_x != nullptr;
     const int n = ov ? c->ov_n : c->n_last;
     REQUIRE(c, 0 <= lat_lo && lat_lo < lat_hi && lat_hi <= S, SAEV_INVALID_ARG, "saev_backward_rows: bad latent range");
+    REQUIRE(c, !c->btk || (part == 0 && lat_lo == 0 && lat_hi == S), SAEV_UNSUPPORTED,
+            "saev_backward_rows: a BatchTopK context runs the backward over all latents in one part");
     hipStream_t s = (hipStream_t)stream;
     DwRowsArgs a{};
     a.starts = c->starts; a.chunk_starts = c->chunk_starts; a.work_latent = c->work_latent;
@@ -1931,6 +2081,7 @@ int saev_bind_w_enc_t(saev_ctx* c, float* scratch) {
 
 int saev_copy_step_state(saev_ctx* c, int32_t n_rows, float* g_out, int32_t* idx_out, float* val_out, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, !c->btk, SAEV_UNSUPPORTED, "saev_copy_step_state: not for a BatchTopK context (no sparse-state exchange)");
     REQUIRE(c, c->n_last > 0 && c->training_last && n_rows == c->n_last, SAEV_INVALID_ARG,
             "saev_copy_step_state: n_rows must be the row count of the training forward in flight");
     hipStream_t s = (hipStream_t)stream;
@@ -1946,6 +2097,7 @@ int saev_backward_override(saev_ctx* c, const float* x_all, const float* g_all, 
                            int32_t n_all) {
     if (!c) return SAEV_INVALID_ARG;
     if (x_all == nullptr) { c->ov_x = nullptr; c->ov_n = 0; return SAEV_OK; }
+    REQUIRE(c, !c->btk, SAEV_UNSUPPORTED, "saev_backward_override: not for a BatchTopK context (a batch-wide top-k over ranks needs a distributed select)");
     REQUIRE(c, g_all && idx_all && val_all && n_all > 0, SAEV_INVALID_ARG, "saev_backward_override: NULL buffer");
     REQUIRE(c, n_all <= c->back_rows, SAEV_INVALID_ARG,
             "saev_backward_override: the gathered row count exceeds saev_cfg.max_backward_rows (set it to the GLOBAL batch)");
@@ -2045,7 +2197,7 @@ int saev_wdec_ready_event(saev_ctx* c, void* event) {
 
 int saev_tail_prepare(saev_ctx* c, int32_t shard_rank, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_tail_prepare: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU, SAEV_UNSUPPORTED, "saev_tail_prepare: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params && c->grads, SAEV_NOT_BOUND, "saev_tail_prepare: params/grads not bound");
     TailRanges r;
     int rc = tail_ranges(c, shard_rank, &r);
@@ -2097,7 +2249,7 @@ int saev_tail_prepare(saev_ctx* c, int32_t shard_rank, void* stream) {
 int saev_tail_apply(saev_ctx* c, float lr, float max_norm, float grad_scale, int64_t adam_step, int32_t shard_rank,
                     void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_tail_apply: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU, SAEV_UNSUPPORTED, "saev_tail_apply: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params && c->grads && c->adam_m && c->adam_v, SAEV_NOT_BOUND,
             "saev_tail_apply: params/grads/adam state not bound");
     REQUIRE(c, adam_step >= 1, SAEV_INVALID_ARG, "adam_step is 1-based");
@@ -2193,6 +2345,7 @@ int saev_train_step_gather(saev_ctx* c, const float* pool, const int64_t* rows, 
                            int64_t adam_step, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
     REQUIRE(c, pool && rows && x_out, SAEV_INVALID_ARG, "saev_train_step_gather: NULL buffer");
+    REQUIRE(c, !c->btk, SAEV_UNSUPPORTED, "saev_train_step_gather: not for a BatchTopK context (draw the batch first: saev_gather_rows)");
     c->gather_pool = pool; c->gather_rows = rows;
     const int rc = saev_train_step(c, x_out, n, lr, max_norm, adam_step, stream);
     c->gather_pool = nullptr; c->gather_rows = nullptr;
@@ -2286,7 +2439,7 @@ int saev_dictionary_coherence(const float* W, int64_t S, int64_t D, int32_t rout
 
 int saev_muon_tail(saev_ctx* c, float lr, float max_norm, float grad_scale, int64_t adam_step, const saev_muon_cfg* cfg, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_muon_tail: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU, SAEV_UNSUPPORTED, "saev_muon_tail: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params && c->grads && c->adam_m && c->adam_v, SAEV_NOT_BOUND, "saev_muon_tail: params/grads/adam state not bound");
     REQUIRE(c, adam_step >= 1, SAEV_INVALID_ARG, "adam_step is 1-based");
     REQUIRE(c, !c->wenc_t_pending, SAEV_INVALID_ARG, "saev_muon_tail: runs after the phases, not inside saev_train_step");
@@ -2352,6 +2505,13 @@ int saev_muon_tail(saev_ctx* c, float lr, float max_norm, float grad_scale, int6
 int saev_train_step(saev_ctx* c, const float* x, int32_t n, float lr, float max_norm, int64_t adam_step,
                     void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    if (c->btk) {  // the four phases back to back: nothing of the fused tail applies
+        int rcb = saev_step_forward(c, x, n, n, 1, stream);
+        if (rcb == SAEV_OK) rcb = saev_step_dead(c, n, stream);
+        if (rcb == SAEV_OK) rcb = saev_step_backward(c, stream);
+        if (rcb == SAEV_OK) rcb = saev_step_tail(c, lr, max_norm, 1.0f, adam_step, stream);
+        return rcb;
+    }
     c->fused_forward = c->dws_ok && c->GS != nullptr;  // (the backward below takes the column slices: nothing reads G's blocks 1..P-1)
     c->train_fused = true;
     int rc = saev_step_forward(c, x, n, n, 1, stream);
@@ -2468,7 +2628,7 @@ int saev_comm_destroy(saev_ctx* c) {
 
 int saev_train_step_dp(saev_ctx* c, const float* x_local, int32_t n_local, float lr, float max_norm, int64_t adam_step, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_train_step_dp: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_train_step_dp: a TopK context only (ReLU runs the forward entries, BatchTopK one GPU)");
     REQUIRE(c, c->comm != nullptr, SAEV_INVALID_ARG, "saev_train_step_dp: no communicator (saev_comm_init)");
     REQUIRE(c, c->grads != nullptr, SAEV_NOT_BOUND, "saev_train_step_dp: no gradient buffer bound");
     hipStream_t s = (hipStream_t)stream;

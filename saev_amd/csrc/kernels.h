@@ -700,6 +700,43 @@ hipError_t launch_relu_decode(const ReluDecodeArgs& a, hipStream_t stream);
 hipError_t launch_relu_scatter(const int32_t* idx, const float* val, const int32_t* row_nnz, int row_cap, int n_rows, int S,
                                float* f_out, hipStream_t stream);
 
+// ---- BatchTopK activation (batchtopk.hip) -----------------------------------------------------------------------------------
+constexpr int BTK_BINS = 4096;            // bins of a select level (12 key bits; the last level uses 256 of them)
+constexpr int BTK_LIST_CAP = 1 << 20;     // keys of the cut bin the second pass can list; more: the later levels re-read h
+// state words the select leaves on the device
+enum { BTK_ST_PREFIX = 0,  // the cut's key (bits found so far while the select runs)
+       BTK_ST_RANK = 1,    // rank left inside the current bin; at the end: the tie quota (entries EQUAL to the cut that are kept, >= 1)
+       BTK_ST_ABOVE = 2,   // entries strictly above the cut
+       BTK_ST_LIST = 3,    // entries of the level-0 cut bin (may exceed the list's capacity)
+       BTK_ST_TIES = 4,    // entries equal to the cut
+       BTK_ST_CUT = 5,     // the cut value's fp32 bits
+       BTK_ST_MINPOS = 6,  // bits of the smallest positive kept value (0x7f800000: none)
+       BTK_ST_WORDS = 16 };
+size_t btk_workspace_words(int max_rows);  // uint32 words: state, three histograms, the key list, two per-row tie counters
+struct BtkArgs {
+    const float* h;         // (n_rows, S), 16-byte aligned, S % 4 == 0, n_rows * S < 2^31
+    int n_rows, S, top_k;   // training: min(n_rows * top_k, n_rows * S) entries are kept
+    int row_cap;            // slots of a padded output row
+    int training;           // 1: batch-wide select; 0: h > *threshold (h > 0 when *threshold <= 0), elementwise
+    int update_threshold;   // training: apply the EMA to *threshold (not applied when a row overflowed)
+    double momentum;        // m of threshold <- float(1 - m) threshold + float(m) min
+    float* threshold;       // device word
+    int32_t* idx_out;       // (n_rows, row_cap) ascending latents, then -1
+    float* val_out;         // (n_rows, row_cap) values, then 0
+    int32_t* row_nnz_out;   // (n_rows) exact, also past row_cap
+    int32_t* overflow;      // device word: 0, or the largest count a row had to store when that exceeded row_cap (training: cut-valued
+                            // entries counted in full, before the tie rule drops some)
+    uint32_t* ws;           // btk_workspace_words(max_rows) words
+    int max_rows;
+    int list_cap;           // 0 = BTK_LIST_CAP; smaller: tests of the route that re-reads h
+};
+struct BtkCompactArgs {
+    const float* h; int n_rows, S, row_cap, training;
+    uint32_t* st; const float* threshold;
+    int32_t* idx_out; float* val_out; int32_t* row_nnz_out; int32_t* row_ties; int32_t* overflow;
+};
+hipError_t launch_batch_topk(const BtkArgs& a, hipStream_t stream);
+
 // ---- Muon (muon.hip) ---------------------------------------------------------------------------------------------------
 // Rounding contract of the Newton-Schulz GEMMs: fp32 accumulation of bf16 products, the fp32 epilogue alpha * acc + beta * Cin,
 // one rounding to bf16 (nearest even) of each output element -- as the vendor BLAS does for torch's bf16 addmm.

@@ -71,8 +71,15 @@ class EngineConfig:
     aux_split_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_SPLIT", "0")))
     aux_wide_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_WIDE", "0")))
     # "topk" (default), or "relu": a forward-only context for a ReLU SAE (top_k is ignored, k_aux must be 0): encode_relu,
-    # decode_rows, scatter_rows and the single ops run; the step entries raise NotImplementedError
+    # decode_rows, scatter_rows and the single ops run; the step entries raise NotImplementedError.
+    # "batch_topk" (include/saev_amd.h: BATCHTOPK): top_k codes per row ON AVERAGE, chosen over the whole batch in training mode
+    # and by the learned threshold in eval mode; codes are padded rows of row_cap slots.  The phases, train_step (= the phases),
+    # muon_tail, encode_batch_topk and batch_topk_dense run; one GPU, no share_x, no deferred gather.
     activation: str = "topk"
+    row_cap: int = 0             # batch_topk: slots per code row; 0 = min(d_sae, max(64, 4 top_k)) rounded up to 64.  A forward that
+                                 # meets a longer row rebuilds the context with the needed capacity (rounded up to 64) and repeats
+    batch_momentum: float = 0.1  # batch_topk: EMA weight of the threshold update
+    select_list_cap: int = 0     # batch_topk route switch for tests: capacity of the select's key list (0 = default; same results)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -371,8 +378,12 @@ class SaeEngine:
             raise ValueError(f"EngineConfig.bounds (SAEV_AMD_BOUNDS) must be 'guaranteed' or 'predicted', got {cfg.bounds!r}")
         if cfg.encoder not in ("f32", "f16x3", "bf16", "f16r"):
             raise ValueError(f"EngineConfig.encoder (SAEV_AMD_ENCODER) must be one of f32, f16x3, bf16, f16r, got {cfg.encoder!r}")
-        if cfg.activation not in ("topk", "relu"):
-            raise ValueError(f"EngineConfig.activation must be 'topk' or 'relu', got {cfg.activation!r}")
+        if cfg.activation not in ("topk", "relu", "batch_topk"):
+            raise ValueError(f"EngineConfig.activation must be 'topk', 'relu' or 'batch_topk', got {cfg.activation!r}")
+        if cfg.activation == "batch_topk" and cfg.encoder == "bf16":
+            raise NotImplementedError("the bf16 encoder is not available for BatchTopK SAEs: use f32, f16x3 or f16r")
+        if cfg.activation == "batch_topk" and (cfg.shard_world > 1 or cfg.max_backward_rows > cfg.max_batch):
+            raise NotImplementedError("a BatchTopK engine runs on one GPU (a batch-wide top-k over ranks needs a distributed select)")
         if cfg.activation == "relu" and cfg.k_aux != 0:
             raise ValueError("a ReLU engine has no auxiliary loss: k_aux must be 0")
         with torch.cuda.device(self.device):
@@ -382,49 +393,97 @@ class SaeEngine:
             self.adam_v = torch.zeros_like(self.params) if with_optim else None
             self.toks_since_active = torch.zeros(S, device=self.device, dtype=torch.int64)
             self.fired = torch.zeros(S, device=self.device, dtype=torch.int32)
-            ccfg = _lib.SaevCfg(
-                d_model=D, d_sae=S, top_k=cfg.top_k, k_aux=cfg.k_aux, alpha=cfg.alpha,
-                dead_threshold_tokens=cfg.dead_threshold_tokens,
-                normalize_w_dec=int(cfg.normalize_w_dec), remove_parallel_grads=int(cfg.remove_parallel_grads),
-                max_batch=cfg.max_batch, encoder_mode={"f32": 0, "f16x3": 1, "bf16": 2, "f16r": 3}[cfg.encoder],
-                aux_dead_cap=cfg.aux_dead_cap, shard_world=cfg.shard_world,
-                bound_mode={"guaranteed": 0, "predicted": 1}[cfg.bounds], max_backward_rows=cfg.max_backward_rows,
-                activation={"topk": 0, "relu": 1}[cfg.activation],
-            )
             if cfg.dw_route not in ("slices", "rows", "slices_a") or cfg.fwd_route not in ("default", "rows"):
                 raise ValueError(f"EngineConfig.dw_route must be 'slices', 'slices_a' or 'rows' and fwd_route 'default' or 'rows', got {cfg.dw_route!r} / {cfg.fwd_route!r}")
-            dbg = _lib.SaevDebugCfg(
-                struct_size=C.sizeof(_lib.SaevDebugCfg), dw_route={"slices": 0, "rows": 1, "slices_a": 2}[cfg.dw_route],
-                aux_small_max=cfg.aux_small_max, fwd_route={"default": 0, "rows": 1}[cfg.fwd_route],
-                csc_route=cfg.csc_route, fin_route=cfg.fin_route, prep_route=cfg.prep_route, aux_dense_route=cfg.aux_dense_route, aux_small_route=cfg.aux_small_route,
-                group_route=cfg.group_route, aux_split_route=cfg.aux_split_route, aux_wide_route=cfg.aux_wide_route)
-            ctx = C.c_void_p()
-            rc = self.lib.saev_create_ex(C.byref(ccfg), C.byref(dbg), self.device.index, C.byref(ctx))
-            if rc != 0:
-                raise _lib.SaevError(f"saev_create failed with status {rc} for {cfg}")
-            self.ctx = ctx
-            self._chk(self.lib.saev_bind(ctx, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v)), "saev_bind")
-            self._params_version = self._pversion()
-            self._chk(self.lib.saev_bind_tracker(ctx, _ptr(self.toks_since_active), _ptr(self.fired)), "saev_bind_tracker")
             # the tail's sum of squares lives in a torch tensor from the start, so that a collective can reach it
             self.sumsq = torch.zeros(1, device=self.device, dtype=torch.float64)
-            self._chk(self.lib.saev_bind_sumsq(ctx, _ptr(self.sumsq)), "saev_bind_sumsq")
+            # BatchTopK: the inference threshold (the module's registered buffer aliases this word) and the rows' capacity
+            self.threshold = torch.zeros((), device=self.device, dtype=torch.float32) if cfg.activation == "batch_topk" else None
+            self.row_cap = 0
+            self.row_regrows = 0  # forwards that met a row longer than row_cap and rebuilt the context
+            self._w_enc_t = None
+            self._prefixes = None
+            self.ctx = None
+            self._create_ctx()
+            self._params_version = self._pversion()
         self.adam_steps = 0
         self._x_keepalive = None
         self._last_n = 0  # rows of the last step_forward (0: none, or a fused step ran since)
-        self._w_enc_t = None
         # ReLU rows: capacity of the next encode_relu (grows to the largest count seen) and how many calls needed a second launch
         self.relu_row_cap = min(cfg.d_sae, 512)
         self.relu_second_launches = 0
 
     # ---- plumbing -------------------------------------------------------------------------
+    def _create_ctx(self) -> None:
+        """The C-ABI context for ``self.cfg``, bound to this engine's tensors.  Everything a context carries from step to step that
+        matters to results -- parameters, gradients, moments, tracker, threshold -- lives in those tensors, so a context can be
+        replaced (``_grow_rows``) without losing any of it."""
+        cfg, S, D = self.cfg, self.cfg.d_sae, self.cfg.d_model
+        ccfg = _lib.SaevCfg(
+            d_model=D, d_sae=S, top_k=cfg.top_k, k_aux=cfg.k_aux, alpha=cfg.alpha,
+            dead_threshold_tokens=cfg.dead_threshold_tokens,
+            normalize_w_dec=int(cfg.normalize_w_dec), remove_parallel_grads=int(cfg.remove_parallel_grads),
+            max_batch=cfg.max_batch, encoder_mode={"f32": 0, "f16x3": 1, "bf16": 2, "f16r": 3}[cfg.encoder],
+            aux_dead_cap=cfg.aux_dead_cap, shard_world=cfg.shard_world,
+            bound_mode={"guaranteed": 0, "predicted": 1}[cfg.bounds], max_backward_rows=cfg.max_backward_rows,
+            activation={"topk": _lib.ACT_TOPK, "relu": _lib.ACT_RELU, "batch_topk": _lib.ACT_BATCHTOPK}[cfg.activation],
+        )
+        dbg = _lib.SaevDebugCfg(
+            struct_size=C.sizeof(_lib.SaevDebugCfg), dw_route={"slices": 0, "rows": 1, "slices_a": 2}[cfg.dw_route],
+            aux_small_max=cfg.aux_small_max, fwd_route={"default": 0, "rows": 1}[cfg.fwd_route],
+            csc_route=cfg.csc_route, fin_route=cfg.fin_route, prep_route=cfg.prep_route, aux_dense_route=cfg.aux_dense_route, aux_small_route=cfg.aux_small_route,
+            group_route=cfg.group_route, aux_split_route=cfg.aux_split_route, aux_wide_route=cfg.aux_wide_route)
+        ctx = C.c_void_p()
+        if cfg.activation == "batch_topk":
+            bt = _lib.SaevBatchTopKCfg(struct_size=C.sizeof(_lib.SaevBatchTopKCfg), row_cap=cfg.row_cap, batch_momentum=cfg.batch_momentum,
+                                       list_cap=cfg.select_list_cap)
+            rc = self.lib.saev_create_batch_topk(C.byref(ccfg), C.byref(dbg), C.byref(bt), self.device.index, C.byref(ctx))
+        else:
+            rc = self.lib.saev_create_ex(C.byref(ccfg), C.byref(dbg), self.device.index, C.byref(ctx))
+        if rc != 0:
+            raise _lib.SaevError(f"saev_create failed with status {rc} for {cfg}")
+        self.ctx = ctx
+        self._chk(self.lib.saev_bind(ctx, _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v)), "saev_bind")
+        self._chk(self.lib.saev_bind_tracker(ctx, _ptr(self.toks_since_active), _ptr(self.fired)), "saev_bind_tracker")
+        self._chk(self.lib.saev_bind_sumsq(ctx, _ptr(self.sumsq)), "saev_bind_sumsq")
+        if self._w_enc_t is not None:
+            self._chk(self.lib.saev_bind_w_enc_t(ctx, _ptr(self._w_enc_t)), "saev_bind_w_enc_t")
+        if self.threshold is not None:
+            self._chk(self.lib.saev_bind_threshold(ctx, _ptr(self.threshold)), "saev_bind_threshold")
+            self.row_cap = int(self.lib.saev_row_cap(ctx))
+        if self._prefixes is not None:
+            self.set_prefixes(self._prefixes)
+
+    def _grow_rows(self, need: int) -> None:
+        """BatchTopK: a forward met a row of ``need`` codes, more than the context's rows hold.  A context with row_cap = need
+        rounded up to 64 takes its place; parameters, moments, tracker, threshold and adam_steps are this engine's tensors and
+        attributes and carry over as they are (the tracker as after ``set_tracker``: the new context reads the dead count back
+        for its first steps)."""
+        if need <= self.row_cap:
+            raise _lib.SaevError(f"BatchTopK row overflow reported {need} codes for rows of {self.row_cap}")
+        torch.cuda.synchronize(self.device)
+        self.lib.saev_destroy(self.ctx)
+        self.ctx = None
+        self.cfg = dataclasses.replace(self.cfg, row_cap=min(self.cfg.d_sae, (need + 63) // 64 * 64))
+        with torch.cuda.device(self.device):
+            self._create_ctx()
+        self.row_regrows += 1
+        self._last_n = 0
+
     def _chk(self, rc, what):
         _lib.check(self.lib, self.ctx, rc, what)
 
     def _topk_only(self, what: str):
+        if self.cfg.activation == "batch_topk":
+            raise NotImplementedError(f"{what} is not available for a BatchTopK SAE (one GPU, the phases or train_step, encode_batch_topk)")
         if self.cfg.activation != "topk":
             raise NotImplementedError(f"{what}: training and the TopK forward are not on the HIP path for a {self.cfg.activation} SAE "
                                       "(only its forward is: encode_relu / decode_rows)")
+
+    def _trains(self, what: str):
+        """TopK and BatchTopK engines run the step entries; a ReLU engine its forward only."""
+        if self.cfg.activation == "relu":
+            self._topk_only(what)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -462,9 +521,11 @@ class SaeEngine:
         """Matryoshka cut points for the following steps (ascending, last == d_sae); None / one entry = plain."""
         if prefixes is None:
             self._n_prefixes = 1
+            self._prefixes = None
             self._chk(self.lib.saev_set_prefixes(self.ctx, None, 0), "saev_set_prefixes")
             return
         pre = [int(p) for p in prefixes]
+        self._prefixes = pre
         self._n_prefixes = max(1, len(pre))
         arr = (C.c_int64 * len(pre))(*pre)
         self._chk(self.lib.saev_set_prefixes(self.ctx, arr, len(pre)), "saev_set_prefixes")
@@ -472,6 +533,8 @@ class SaeEngine:
     def share_x(self, leader: "SaeEngine | None") -> None:
         """Borrow what a step derives from x alone (statistics, centring, operand images) from ``leader`` whenever it has
         just run its forward on the same batch tensor: several SAEs on the same batches (train()'s parallel groups)."""
+        if leader is not None and "batch_topk" in (self.cfg.activation, leader.cfg.activation):
+            raise NotImplementedError("share_x: a BatchTopK engine neither lends nor borrows what a step derives from x")
         self._leader = leader  # keeps it alive for as long as the link exists
         self._chk(self.lib.saev_share_x(self.ctx, leader.ctx if leader is not None else None), "saev_share_x")
 
@@ -624,6 +687,50 @@ class SaeEngine:
                                              _ptr(f), _stream()), "saev_scatter_rows")
         return f
 
+    # ---- BatchTopK activation: padded rows of row_cap slots, -1 / 0 past row_nnz (include/saev_amd.h: BATCHTOPK) -------------
+    def _btk_rows(self, what: str, src: torch.Tensor, training: bool):
+        if self.cfg.activation != "batch_topk":
+            raise _lib.SaevError(f"{what} needs an engine created with activation='batch_topk'")
+        n = src.shape[0]
+        fn = getattr(self.lib, f"saev_{what}")
+        over = torch.empty(1, device=self.device, dtype=torch.int32)
+        row_nnz = torch.empty(n, device=self.device, dtype=torch.int32)
+        for attempt in range(2):
+            idx = torch.empty(n, self.row_cap, device=self.device, dtype=torch.int32)
+            val = torch.empty(n, self.row_cap, device=self.device, dtype=torch.float32)
+            self._chk(fn(self.ctx, _ptr(src), n, int(training), _ptr(row_nnz), _ptr(idx), _ptr(val), _ptr(over), _stream()), f"saev_{what}")
+            need = int(over.item())  # the call's one read-back: 0, or the largest row count when a row overflowed
+            if need == 0:
+                return idx, val, row_nnz
+            if attempt == 1:
+                raise _lib.SaevError(f"saev_{what} overflowed rows of {self.row_cap} sized from its own count {need}")
+            self._grow_rows(need)  # (the threshold has not moved: the repeated call applies the update, once)
+
+    def encode_batch_topk(self, x: torch.Tensor, *, training: bool):
+        """``(idx, val, row_nnz)`` of f = BatchTopK(x W_enc + b_enc): training mode selects over the whole batch and updates the
+        threshold, eval mode keeps h > threshold.  A row longer than ``row_cap`` grows the engine's rows and repeats the call."""
+        x = self._check_x(x)
+        self._note_param_writes()
+        return self._btk_rows("encode_batch_topk", x, training)
+
+    def batch_topk_dense(self, h: torch.Tensor, *, training: bool = True):
+        """The activation alone on a dense (n, d_sae) float32 device matrix: ``(idx, val, row_nnz)``."""
+        if h.device != self.device or h.dtype != torch.float32 or h.ndim != 2 or h.shape[1] != self.cfg.d_sae:
+            raise _lib.SaevError(f"batch_topk_dense takes a float32 (n, {self.cfg.d_sae}) matrix on {self.device}")
+        h = h.contiguous()
+        if h.data_ptr() % 16:
+            h = h.clone()
+        return self._btk_rows("batch_topk_dense", h, training)
+
+    def batch_topk_state(self) -> dict:
+        """What the last training-mode select left on the device: the cut value, the entries strictly above it, how many of the
+        entries equal to it are kept (the tie quota) and how many there are."""
+        cut = C.c_float()
+        above, quota, ties = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.saev_batch_topk_state(self.ctx, C.byref(cut), C.byref(above), C.byref(quota), C.byref(ties), _stream()),
+                  "saev_batch_topk_state")
+        return {"cut": cut.value, "n_above": above.value, "tie_quota": quota.value, "n_ties": ties.value}
+
     def remove_parallel_grads(self):
         self._chk(self.lib.saev_remove_parallel_grads(self.ctx, _stream()), "saev_remove_parallel_grads")
 
@@ -636,20 +743,25 @@ class SaeEngine:
 
     # ---- the step -------------------------------------------------------------------------
     def step_forward(self, x: torch.Tensor, *, training: bool = True, n_rows_global: int | None = None):
-        self._topk_only("step_forward")
+        self._trains("step_forward")
         x = self._check_x(x)
         self._x_keepalive = x
         self._note_param_writes()
         n = x.shape[0]
-        self._chk(self.lib.saev_step_forward(self.ctx, _ptr(x), n, n_rows_global or n, int(training), _stream()), "saev_step_forward")
+        rc = self.lib.saev_step_forward(self.ctx, _ptr(x), n, n_rows_global or n, int(training), _stream())
+        if rc == _lib.ROW_OVERFLOW:
+            # BatchTopK: nothing was decoded and the threshold has not moved; larger rows, then the same forward again
+            self._grow_rows(int(self.lib.saev_row_overflow_need(self.ctx)))
+            rc = self.lib.saev_step_forward(self.ctx, _ptr(x), n, n_rows_global or n, int(training), _stream())
+        self._chk(rc, "saev_step_forward")
         self._last_n = n
 
     def step_dead(self, n_rows_global: int):
-        self._topk_only("step_dead")
+        self._trains("step_dead")
         self._chk(self.lib.saev_step_dead(self.ctx, n_rows_global, _stream()), "saev_step_dead")
 
     def step_backward(self):
-        self._topk_only("step_backward")
+        self._trains("step_backward")
         self._chk(self.lib.saev_step_backward(self.ctx, _stream()), "saev_step_backward")
 
     # backward in pieces (data-parallel overlap, see framework/ddp.py)
@@ -676,7 +788,7 @@ class SaeEngine:
     def step_tail(self, lr: float, max_norm: float = 1.0, grad_scale: float = 1.0, *, trusted: bool = False):
         """``trusted``: nothing wrote the gradient buffer since ``backward_end`` -- the tail may use the row statistics the
         backward left behind (projection inside Adam, no rpg pass), as ``train_step`` does."""
-        self._topk_only("step_tail")
+        self._trains("step_tail")
         self.adam_steps += 1
         if trusted:
             self._chk(self.lib.saev_trust_gradients(self.ctx, 1), "saev_trust_gradients")
@@ -689,7 +801,7 @@ class SaeEngine:
     def muon_tail(self, lr: float, max_norm: float = 1.0, grad_scale: float = 1.0, muon: MuonConfig | None = None):
         """The tail of a Muon step after the phases (saev_muon_tail): rpg, clip, Adam on the biases, Muon on W_dec / W_enc.
         The momentum buffers are the W_dec / W_enc segments of ``adam_m``."""
-        self._topk_only("muon_tail")
+        self._trains("muon_tail")
         cfg = (muon or MuonConfig()).c_struct()
         self.adam_steps += 1
         self._chk(self.lib.saev_muon_tail(self.ctx, lr, max_norm, grad_scale, self.adam_steps, C.byref(cfg), _stream()), "saev_muon_tail")
@@ -777,11 +889,15 @@ class SaeEngine:
         ``grad_views()`` is NOT a valid gradient afterwards: the W_enc gradient stays in the transposed scratch and the
         dW_dec rows are stored un-projected (the fused Adam projects them as it reads).  To look at gradients run the phases
         (``step_forward`` / ``step_dead`` / ``step_backward`` / ``step_tail``), as the log steps of ``train()`` do."""
-        self._topk_only("train_step")
+        self._trains("train_step")
         x = self._check_x(x)
         self._x_keepalive = x
         self._note_param_writes()
-        self._chk(self.lib.saev_train_step(self.ctx, _ptr(x), x.shape[0], lr, max_norm, self.adam_steps + 1, _stream()), "saev_train_step")
+        rc = self.lib.saev_train_step(self.ctx, _ptr(x), x.shape[0], lr, max_norm, self.adam_steps + 1, _stream())
+        if rc == _lib.ROW_OVERFLOW:  # (BatchTopK: the step stopped in its forward, before anything moved)
+            self._grow_rows(int(self.lib.saev_row_overflow_need(self.ctx)))
+            rc = self.lib.saev_train_step(self.ctx, _ptr(x), x.shape[0], lr, max_norm, self.adam_steps + 1, _stream())
+        self._chk(rc, "saev_train_step")
         self._last_n = 0
         self.adam_steps += 1  # (counted once the step is enqueued: a refused call -- SAEV_STALE_PARAMS -- is not an optimizer step)
 
@@ -841,7 +957,7 @@ class SaeEngine:
         """Accumulate the statistics of the last ``step_forward`` -- whose batch ``x`` was -- into ``acc`` straight from the
         context's own codes and reconstruction (saev_last_idx / _val / _x_hat): no copy of either is made.  ``x_hat=False``
         leaves the reconstruction unread (the residual sums then add 0); ``scalars=False`` leaves the scalar sums out."""
-        self._topk_only("add_batch_stats")
+        self._trains("add_batch_stats")  # (BatchTopK rows are padded with idx = -1, which the kernel ignores: no row_nnz needed)
         x = self._check_x(x)
         if self._last_n == 0 or x.shape[0] != self._last_n:
             raise _lib.SaevError(f"add_batch_stats: x has {x.shape[0]} rows, the last step_forward had {self._last_n or 'none'}")
@@ -849,16 +965,25 @@ class SaeEngine:
             raise _lib.SaevError("add_batch_stats: the accumulator was made for another shape or device")
         p = lambda v: C.c_void_p(v)  # noqa: E731
         acc._add_ptrs(_ptr(x), p(self.lib.saev_last_x_hat(self.ctx)) if x_hat else None, p(self.lib.saev_last_idx(self.ctx)),
-                      p(self.lib.saev_last_val(self.ctx)), None, keep, x.shape[0], min(self.cfg.top_k, self.cfg.d_sae), overwrite, scalars)
+                      p(self.lib.saev_last_val(self.ctx)), None, keep, x.shape[0], self._code_width(), overwrite, scalars)
 
-    def last_codes(self, n_rows: int, *, x_hat: bool = True):
-        """Copies of the last forward's codes and (unless ``x_hat=False``: None then) reconstruction."""
-        k = min(self.cfg.top_k, self.cfg.d_sae)
+    def _code_width(self) -> int:
+        """Columns of the context's code rows: top_k, or the row capacity of a BatchTopK engine."""
+        return self.row_cap if self.cfg.activation == "batch_topk" else min(self.cfg.top_k, self.cfg.d_sae)
+
+    def last_codes(self, n_rows: int, *, x_hat: bool = True, row_nnz: bool = False):
+        """Copies of the last forward's codes and (unless ``x_hat=False``: None then) reconstruction.  A BatchTopK engine's codes
+        are its padded rows (n_rows, row_cap); ``row_nnz=True`` appends their counts: ``(idx, val, x_hat, row_nnz)``."""
+        k = self._code_width()
         idx = torch.empty(n_rows, k, device=self.device, dtype=torch.int32)
         val = torch.empty(n_rows, k, device=self.device, dtype=torch.float32)
         x_hat = torch.empty(n_rows, self.cfg.d_model, device=self.device, dtype=torch.float32) if x_hat else None
         self._chk(self.lib.saev_copy_last(self.ctx, n_rows, _ptr(idx), _ptr(val), _ptr(x_hat), _stream()), "saev_copy_last")
-        return idx, val, x_hat
+        if not row_nnz:
+            return idx, val, x_hat
+        nnz = torch.empty(n_rows, device=self.device, dtype=torch.int32)
+        self._chk(self.lib.saev_copy_last_row_nnz(self.ctx, n_rows, _ptr(nnz), _stream()), "saev_copy_last_row_nnz")
+        return idx, val, x_hat, nnz
 
     def aux_route(self) -> int:
         """What the last step_dead did for the auxiliary loss: 0 nothing, 1 few-dead-latents kernels without reading

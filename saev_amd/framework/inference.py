@@ -126,7 +126,9 @@ def worker_fn(cfg: Config):
     batch_size = cfg.data.batch_size // T * T  # whole examples per batch (inference.py:158-165)
     loader = OrderedDataLoader(dataclasses.replace(cfg.data, batch_size=batch_size), device=device)
     eng = sae._eng(batch_size)
-    relu = isinstance(sae.cfg.activation, nn.modeling.Relu)
+    batch_topk = isinstance(sae.cfg.activation, nn.modeling.BatchTopK)
+    # padded variable-length rows: a ReLU SAE's positives, a BatchTopK SAE's eval-mode codes (h > threshold, all positive too)
+    relu = batch_topk or isinstance(sae.cfg.activation, nn.modeling.Relu)
 
     # every sum of the pass -- column sums of x, sum x^2 and sum (x - x_hat)^2 over the kept rows in fp64, per-latent positive
     # counts and value sums -- from one kernel per batch, TopK or ReLU, masked or not (engine.BatchStats)
@@ -146,7 +148,7 @@ def worker_fn(cfg: Config):
         x = batch["act"]
         b = x.shape[0]
         if relu:
-            idx, val, row_nnz = eng.encode_relu(x)
+            idx, val, row_nnz = eng.encode_batch_topk(x, training=False) if batch_topk else eng.encode_relu(x)
             x_hat = eng.decode_rows(idx, val, row_nnz)[:, 0]
         else:
             eng.step_forward(x, training=False)

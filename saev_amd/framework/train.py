@@ -185,13 +185,16 @@ def _make_loader(cfg_data, device, rank, world, pool=None):
 
 
 def _require_topk(cfgs: list[Config], what: str) -> None:
-    """Only TopK SAEs train on the HIP path: a ReLU SAE runs its forward (nn.modeling, framework.inference) only, BatchTopK
-    nothing."""
+    """TopK and BatchTopK SAEs train on the HIP path; a ReLU SAE runs its forward (nn.modeling, framework.inference) only."""
     for c in cfgs:
         act = c.sae.activation
-        if not isinstance(act, modeling.TopK):
-            raise NotImplementedError(f"{what}: {type(act).__name__} SAEs are not trained on the HIP path (TopK only; a Relu SAE's "
-                                      "forward runs through nn.SparseAutoencoder and framework.inference)")
+        if not isinstance(act, (modeling.TopK, modeling.BatchTopK)):
+            raise NotImplementedError(f"{what}: {type(act).__name__} SAEs are not trained on the HIP path (TopK and BatchTopK only; a "
+                                      "Relu SAE's forward runs through nn.SparseAutoencoder and framework.inference)")
+
+
+def _is_batch_topk(cfg: Config) -> bool:
+    return isinstance(cfg.sae.activation, modeling.BatchTopK)
 
 
 def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=None) -> tuple[torch.nn.ModuleList, torch.nn.ModuleList, RunLog, int]:
@@ -200,6 +203,9 @@ def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=No
     ``train_pool`` optionally supplies an in-memory (n, d_model) activation pool instead of a shard dir; ``train_feed`` a
     ready loader-shaped object (e.g. data.ExtractionFeed: activations straight out of a transformer's forward hooks)."""
     _require_topk(cfgs, "train")
+    if any(_is_batch_topk(c) for c in cfgs) and _dist()[2] > 1:
+        raise NotImplementedError("BatchTopK SAEs train on one GPU: a batch-wide top-k over the shards of several ranks needs a "
+                                  "distributed select (DESIGN.md 3.13)")
     if len(split_cfgs(cfgs)) != 1:
         raise ValueError(f"Configs are not parallelizeable: {cfgs}.")
     cfg = cfgs[0]
@@ -250,15 +256,18 @@ def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=No
         eng = obj._bind(sae, dataloader.local_batch)
         if world > 1:  # identical replicas: rank 0's initial parameters everywhere
             dist.broadcast(eng.params, src=0)
-        if steppers:  # one batch feeds every SAE of the group (train.py:334-348): the first engine's x statistics,
-            eng.share_x(steppers[0].engine)  # centring and operand images serve the others
+        # one batch feeds every SAE of the group (train.py:334-348): the first TopK engine's x statistics, centring and operand
+        # images serve the other TopK members (a BatchTopK engine works from its own dense pre-activations: nothing to share)
+        lender = next((s.engine for s, sc in zip(steppers, cfgs) if not _is_batch_topk(sc)), None)
+        if lender is not None and not _is_batch_topk(c):
+            eng.share_x(lender)
         steppers.append(DataParallelStepper(eng, dist, world, tail=tail_mode, exchange=exchange, muon=mu))
         scheds.append(scheduling.WarmupCosine(0.0, c.n_lr_warmup, c.lr, len(limiter), 0.0))
         lrs.append(0.0)  # first optimizer step is pure warm-up (train.py:118)
     dataloader.engine = steppers[0].engine
     # One rank, a resident pool: the loader hands over (pool, row indices) and the first SAE's step draws the batch in its own
     # first kernel (SaeEngine.train_step_gather) -- no gather pass, and for a single SAE the streamed preparation of the step.
-    if world == 1 and hasattr(dataloader, "defer_gather") and muons[0] is None:
+    if world == 1 and hasattr(dataloader, "defer_gather") and muons[0] is None and not _is_batch_topk(cfgs[0]):
         dataloader.defer_gather = True
 
     global_step, n_patches_seen = 0, 0

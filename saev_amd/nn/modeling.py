@@ -12,10 +12,11 @@ files move between the two unchanged:
 
 What differs: every compute method runs hand-written HIP kernels through libsaev_amd.so on the
 module's parameters, which are views into one flat device buffer owned by ``saev_amd.engine.SaeEngine``.
-There is no CPU implementation: calling a compute method on CPU tensors raises.  TopK SAEs train and
-run on the accelerated path (BASELINE.json north_star); ``Relu`` SAEs run their forward (``encode /
-decode / forward``, the inference pass) but do not train; ``BatchTopK`` configs still parse and
-round-trip through checkpoints but raise ``NotImplementedError`` when run.
+There is no CPU implementation: calling a compute method on CPU tensors raises.  TopK and BatchTopK SAEs
+train and run on the accelerated path (BASELINE.json north_star; BatchTopK on one GPU, DESIGN.md 3.13);
+``Relu`` SAEs run their forward (``encode / decode / forward``, the inference pass) but do not train.
+A BatchTopK module carries the reference's ``activation.threshold`` buffer, so its ``sae.pt`` files move
+between the two code bases in both directions.
 """
 
 from __future__ import annotations
@@ -137,8 +138,8 @@ class Output:
     """Forward outputs with the reference's field names (modeling.py:299-304).
 
     The HIP path keeps the k-sparse codes ``idx`` / ``val`` (batch, top_k); the dense ``h_x`` / ``f_x``
-    (batch, d_sae) matrices are materialised only when read.  A ReLU SAE's codes are padded rows: ``idx`` /
-    ``val`` (batch, cap) with ``row_nnz`` (batch) valid entries each (``SaeEngine.encode_relu``)."""
+    (batch, d_sae) matrices are materialised only when read.  A ReLU or BatchTopK SAE's codes are padded rows: ``idx`` /
+    ``val`` (batch, cap) with ``row_nnz`` (batch) valid entries each (``SaeEngine.encode_relu`` / ``encode_batch_topk``)."""
 
     def __init__(self, sae: "SparseAutoencoder", x: Tensor, idx: Tensor, val: Tensor, x_hats: Tensor | None,
                  h_x: Tensor | None = None, prefixes: Tensor | None = None, row_nnz: Tensor | None = None):
@@ -210,15 +211,29 @@ class ReluActivation(torch.nn.Module):
         return torch.nn.functional.relu(x)
 
 
-class _Unsupported(torch.nn.Module):
-    def __init__(self, cfg):
+class BatchTopKActivation(torch.nn.Module):
+    """BatchTopK over dense pre-activations (modeling.py:183-244) on the HIP select and compaction kernels.
+
+    Training mode keeps the ``min(top_k * batch, d_sae * batch)`` largest entries of the flattened matrix by signed value --
+    ties at the cut: lower flat index first -- and moves ``threshold`` towards the smallest positive kept value by
+    ``cfg.momentum`` (a batch that keeps nothing positive leaves it alone; the reference raises there).  Eval mode keeps
+    ``x > threshold`` (``x > 0`` while ``threshold <= 0``), elementwise.  ``threshold`` is a registered buffer, as in the
+    reference: ``state_dict()`` has the key ``activation.threshold``.  Once the owning module has an engine, the buffer IS the
+    device word the kernels read and update.  There is no CPU path: anything but a HIP tensor raises."""
+
+    def __init__(self, cfg: BatchTopK, sae: "SparseAutoencoder | None" = None):
         super().__init__()
         self.cfg = cfg
+        self.__dict__["_sae"] = sae  # not a submodule
+        self.register_buffer("threshold", torch.tensor(0.0))
 
-    def forward(self, x):
-        raise NotImplementedError(
-            f"{type(self.cfg).__name__} is outside the MI355X hot path (TopK, and the ReLU forward); the config is kept so "
-            "sweeps/checkpoints parse.")
+    def forward(self, x: Tensor) -> Tensor:
+        sae = self.__dict__["_sae"]
+        if not isinstance(x, Tensor) or x.device.type != "cuda" or sae is None:
+            raise NotImplementedError("BatchTopKActivation runs on a HIP device through its owning SparseAutoencoder only "
+                                      "(there is no CPU path)")
+        eng = sae._eng(x.shape[0])
+        return eng.scatter_rows(*eng.batch_topk_dense(x, training=self.training))
 
 
 class SparseAutoencoder(torch.nn.Module):
@@ -244,7 +259,7 @@ class SparseAutoencoder(torch.nn.Module):
         elif isinstance(cfg.activation, Relu):
             self.activation = ReluActivation(cfg.activation, self)
         else:
-            self.activation = _Unsupported(cfg.activation)
+            self.activation = BatchTopKActivation(cfg.activation, self)
         self.__dict__["_engine"] = None
         self.__dict__["_engine_max_batch"] = 0
 
@@ -258,12 +273,22 @@ class SparseAutoencoder(torch.nn.Module):
                 dead_threshold_tokens=getattr(self, "_dead_threshold_tokens", 10_000_000), normalize_w_dec=self.cfg.normalize_w_dec,
                 remove_parallel_grads=self.cfg.remove_parallel_grads, max_batch=max_batch, activation="relu",
             )
-        if not isinstance(act, TopK):
-            raise NotImplementedError(f"{type(act).__name__} activation is not on the HIP path (TopK only)")
+        if not isinstance(act, (TopK, BatchTopK)):
+            raise NotImplementedError(f"{type(act).__name__} activation is not on the HIP path (TopK, BatchTopK, and the ReLU forward)")
         if not isinstance(act.sparsity, NoSparsity):
-            raise NotImplementedError("TopK with an explicit sparsity penalty is not on the HIP path")
+            raise NotImplementedError(f"{type(act).__name__} with an explicit sparsity penalty is not on the HIP path")
         aux = act.aux
         thr = getattr(self, "_dead_threshold_tokens", 10_000_000)
+        if isinstance(act, BatchTopK):
+            if getattr(self, "_shard_world", 1) > 1 or getattr(self, "_max_backward_rows", 0) > 0:
+                raise NotImplementedError("a BatchTopK SAE trains on one GPU (a batch-wide top-k over ranks needs a distributed select)")
+            return EngineConfig(
+                d_model=self.cfg.d_model, d_sae=self.cfg.d_sae, top_k=act.top_k,
+                k_aux=aux.k_aux if isinstance(aux, AuxK) else 0, alpha=aux.alpha if isinstance(aux, AuxK) else 0.0,
+                dead_threshold_tokens=thr, normalize_w_dec=self.cfg.normalize_w_dec,
+                remove_parallel_grads=self.cfg.remove_parallel_grads, max_batch=max_batch, activation="batch_topk",
+                batch_momentum=act.momentum, row_cap=getattr(self, "_row_cap", 0),
+            )
         return EngineConfig(
             d_model=self.cfg.d_model, d_sae=self.cfg.d_sae, top_k=act.top_k,
             k_aux=aux.k_aux if isinstance(aux, AuxK) else 0, alpha=aux.alpha if isinstance(aux, AuxK) else 0.0,
@@ -291,7 +316,10 @@ class SparseAutoencoder(torch.nn.Module):
         if stale:
             old = eng
             values = {n: getattr(self, n).detach().clone() for n in ("W_dec", "b_dec", "W_enc", "b_enc")}
-            eng = SaeEngine(self._engine_cfg(max(want_batch, 1024)), dev)
+            ecfg = self._engine_cfg(max(want_batch, 1024))
+            if old is not None and ecfg.activation == "batch_topk":  # (rows an earlier forward has grown stay grown)
+                ecfg = dataclasses.replace(ecfg, row_cap=max(ecfg.row_cap, old.row_cap))
+            eng = SaeEngine(ecfg, dev)
             eng.load_params(values)
             if old is not None and old.device == dev:
                 eng.set_tracker(old.toks_since_active)
@@ -306,6 +334,12 @@ class SparseAutoencoder(torch.nn.Module):
             eng.watch([getattr(self, n) for n in eng.offsets])  # (their version counters are their own: see SaeEngine.watch)
             self.__dict__["_engine"] = eng
             self.__dict__["_engine_max_batch"] = eng.cfg.max_batch
+        if eng.threshold is not None and self.activation.threshold.data_ptr() != eng.threshold.data_ptr():
+            # BatchTopK: the registered buffer becomes the device word the kernels read and update (its value first: a loaded
+            # checkpoint's, or what the previous engine left).  load_state_dict writes it in place; a buffer somebody replaced
+            # (a new tensor assigned, .to()) is re-adopted here
+            eng.threshold.copy_(self.activation.threshold.detach().to(dev, torch.float32).reshape(()))
+            self.activation._buffers["threshold"] = eng.threshold
         # The engine keeps what its forward needs of W_enc / W_dec between calls (include/saev_amd.h, PARAMETER OWNERSHIP).  The four
         # Parameters are views of its buffer with version counters of their own: an in-place write through them (load_state_dict,
         # an initialiser, a user's sae.W_enc.mul_()) shows here and drops what the engine kept.  Writes through .data show nowhere.
@@ -324,6 +358,11 @@ class SparseAutoencoder(torch.nn.Module):
         if isinstance(self.cfg.activation, Relu):
             idx, val, row_nnz = eng.encode_relu(x)
             return Output(self, x, idx, val, eng.decode_rows(idx, val, row_nnz), row_nnz=row_nnz)
+        if isinstance(self.cfg.activation, BatchTopK):
+            # sae.train() / sae.eval() select the mode, as in the reference: the batch-wide select (which also moves the threshold)
+            # or the threshold.  Not step_forward: a module forward must not touch the objective's dead-latent tracker
+            idx, val, row_nnz = eng.encode_batch_topk(x, training=self.training)
+            return Output(self, x, idx, val, eng.decode_rows(idx, val, row_nnz), row_nnz=row_nnz)
         eng.step_forward(x, training=False)
         idx, val, x_hat = eng.last_codes(x.shape[0])
         return Output(self, x, idx, val, x_hat[:, None, :])
@@ -340,9 +379,12 @@ class SparseAutoencoder(torch.nn.Module):
 
     def encode_sparse(self, x: Tensor) -> tuple[Tensor, ...]:
         """(idx, val) codes, (batch, top_k) each, without materialising the dense matrices.  ReLU: (idx, val, row_nnz), padded
-        rows of ascending latents (``SaeEngine.encode_relu``)."""
+        rows of ascending latents (``SaeEngine.encode_relu``); BatchTopK: the same form, in the module's mode
+        (``SaeEngine.encode_batch_topk``)."""
         if isinstance(self.cfg.activation, Relu):
             return self._eng(x.shape[0]).encode_relu(x)
+        if isinstance(self.cfg.activation, BatchTopK):
+            return self._eng(x.shape[0]).encode_batch_topk(x, training=self.training)
         return self._eng(x.shape[0]).encode_topk(x)
 
     def decode(self, f_x: Tensor, *, prefixes: Tensor | None = None) -> Tensor:
@@ -419,7 +461,8 @@ def _git_commit() -> str:
 
 def dump(fpath: pathlib.Path | str, sae: SparseAutoencoder):
     """Write ``sae.pt``: header line ``{"schema":5,"cfg":...,"commit":...,"lib":...}\\n`` then
-    ``torch.save(state_dict)`` with four independent CPU tensors, keys ``W_dec,b_dec,W_enc,b_enc``."""
+    ``torch.save(state_dict)`` with independent CPU tensors, keys ``W_dec,b_dec,W_enc,b_enc`` (+ ``activation.threshold``
+    for a BatchTopK SAE, as the reference writes it)."""
     cfg_dict = dataclasses.asdict(sae.cfg)
     cfg_dict["activation"] = _ser(sae.cfg.activation)
     header = {"schema": SCHEMA_VERSION, "cfg": cfg_dict, "commit": _git_commit(), "lib": __version__}
@@ -508,9 +551,9 @@ def _config_fields(header: dict[str, tp.Any], where: str) -> dict[str, tp.Any]:
 
 def load(fpath: pathlib.Path | str, *, device="cpu") -> SparseAutoencoder:
     """Read an ``sae.pt``: schema 5 (what ``dump`` here and the reference's ``nn.dump`` write, modeling.py:548-574) and every
-    older layout the reference's loader still reads (modeling.py:586-645; table above ``_config_fields``).  Only TopK
-    checkpoints train on the HIP path and ReLU ones run their forward; BatchTopK ones load (parameters and config) and raise
-    when run."""
+    older layout the reference's loader still reads (modeling.py:586-645; table above ``_config_fields``).  TopK and
+    BatchTopK checkpoints train on the HIP path (a BatchTopK one brings its ``activation.threshold``), ReLU ones run their
+    forward."""
     with open(fpath, "rb") as fd:
         first_line = fd.readline()
         payload = io.BytesIO(fd.read())

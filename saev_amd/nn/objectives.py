@@ -1,7 +1,7 @@
 """saev.nn.objectives' public surface (reference: src/saev/nn/objectives.py) over the HIP engine.
 
 ``get_objective(Matryoshka(...))`` returns a module whose ``forward(sae, x)`` gives
-``(MatryoshkaLoss, Output)`` like the reference (objectives.py:92-156): encode + TopK, dead-latent
+``(MatryoshkaLoss, Output)`` like the reference (objectives.py:92-156): encode + TopK / BatchTopK, dead-latent
 tracking, decode, MSE with the max|x| rescale (objectives.py:223-237), AuxK (modeling.py:75-103).
 All of it runs in libsaev_amd.so; ``loss.loss.backward()`` runs the HIP sparse backward and leaves the
 four parameter gradients in ``param.grad`` (views of the engine's flat gradient buffer).
@@ -149,10 +149,14 @@ class MatryoshkaObjective(Objective):
             mse=t(st.mse), sparsity=torch.tensor(0.0), l0=t(st.l0), l1=t(st.l1), aux=t(st.aux),
             n_dead=torch.tensor(st.n_dead, device=dev) if self.training else torch.tensor(0), total=total,
         )
-        idx, val, x_hat = eng.last_codes(n)
+        if isinstance(sae.cfg.activation, modeling.BatchTopK):
+            # padded rows (the batch-wide select in training, the threshold in eval: saev_step_forward's `training` picks it)
+            idx, val, x_hat, row_nnz = eng.last_codes(n, row_nnz=True)
+        else:
+            (idx, val, x_hat), row_nnz = eng.last_codes(n), None
         if self.cfg.n_prefixes > 1:
-            return loss, modeling.Output(sae, x, idx, val, None, prefixes=prefixes)
-        return loss, modeling.Output(sae, x, idx, val, x_hat[:, None, :])
+            return loss, modeling.Output(sae, x, idx, val, None, prefixes=prefixes, row_nnz=row_nnz)
+        return loss, modeling.Output(sae, x, idx, val, x_hat[:, None, :], row_nnz=row_nnz)
 
 
 @functools.lru_cache(maxsize=8)
