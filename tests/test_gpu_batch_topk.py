@@ -27,6 +27,7 @@ import torch
 
 import sae_ref as R
 from conftest import load_golden
+from step_restatement import restated_gradients
 from test_inference_host_cpu import write_cache
 
 pytestmark = pytest.mark.gpu
@@ -308,20 +309,6 @@ def test_module_api_matches_the_reference(tmp_path, encoder_mode):
 # ------------------------------------------------------------------------------------------------
 
 
-def restated_gradients(params, x, mask, dead_mask, prefixes, k_aux, alpha):
-    """loss = mean over prefixes of the rescaled MSE + AuxK, with f = h * mask (df/dh = the mask; the threshold has no gradient)."""
-    leaves = {k: v.clone().requires_grad_(True) for k, v in params.items()}
-    h = x @ leaves["W_enc"] + leaves["b_enc"]
-    f = h * mask
-    x_hats = R.decode(f, leaves["W_dec"], leaves["b_dec"], prefixes)
-    P = x_hats.shape[1]
-    mse = R.mean_squared_err(x_hats, x[:, None, :].expand(-1, P, -1)).mean()
-    aux = R.auxk_loss(x=x, h=h, x_hat_last=x_hats[:, -1, :], dead_mask=dead_mask, W_dec=leaves["W_dec"], b_dec=leaves["b_dec"],
-                      k_aux=k_aux, alpha=alpha)
-    (mse + aux).backward()
-    return float(mse), float(aux), {k: v.grad for k, v in leaves.items()}
-
-
 @pytest.mark.parametrize("case", ["plain", "prefixes", "dead"])
 def test_gradients_match_a_dense_autograd_restatement(case, encoder_mode):
     g = load_golden("g20_batch_topk_train_p1")
@@ -354,7 +341,7 @@ def test_gradients_match_a_dense_autograd_restatement(case, encoder_mode):
     dead = R.update_dead_tracker(toks.clone(), f.cpu(), thr)
     assert torch.equal(eng.toks_since_active.cpu(), torch.where((f.cpu().abs() > 0).any(dim=0), 0, toks + b))
     assert st.n_dead == int(dead.sum()) and (case != "dead" or st.n_dead >= 1)
-    mse, aux, grads = restated_gradients(params, x, got.float(), dead, prefixes, k_aux, float(g["alpha"]))
+    mse, aux, grads = restated_gradients(params, x, got.float(), dead, prefixes, k_aux, float(g["alpha"]), dtype=torch.float32)
     assert math.isclose(st.mse, mse, rel_tol=1e-4)
     assert math.isclose(st.aux, aux, rel_tol=1e-4, abs_tol=1e-9) and (case != "dead" or st.aux > 0)
     assert math.isclose(st.l0, float(k), rel_tol=1e-6)
