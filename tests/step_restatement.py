@@ -73,6 +73,9 @@ class Row:
     aux_route: int = 0      # SaeEngine.aux_route() the row must report: 0 none, 2 the few-dead-latents kernels, 3 the dense algebra
     seed: int = 0           # fixed by tests/test_step_restatement_host_cpu.py: the input conditions hold at this seed
     bound: float = BOUND    # 2e-5, or 4 x the row's measured fp32-oracle error where that is larger (none is: DESIGN.md)
+    spread: float = 0.0     # BTK_SHAPES: batch row b is scaled by exp(spread * N(0, 1)), so the batch-wide select leaves rows of very different lengths
+    dead_bias: float = DEAD_BIAS  # b_enc of the row's dead latents
+    lengths: tuple | None = None  # BTK_SHAPES: (shortest row, longest row, empty rows) of the fp64 select, fixed by tests/test_batch_topk_restatement_host_cpu.py
 
     @property
     def id(self) -> str:
@@ -169,6 +172,104 @@ def input_conditions(row: Row, W_enc, b_enc, x, toks):
     assert int(dead.sum()) == row.n_dead
     assert not mask[:, dead].any(), f"{row.id}: a dead latent is among the top-k"
     if row.n_dead > row.k_aux:
+        td = h[:, dead].topk(row.k_aux + 1, dim=1).values
+        gap = (td[:, row.k_aux - 1] - td[:, row.k_aux]) / tol
+        worst[1] = gap.min().item()
+        assert worst[1] > 2.0, f"{row.id}: batch row {int(gap.argmin())}: the k_aux-th and (k_aux+1)-th dead pre-activation are {worst[1]:.2f} tol_b apart"
+    return mask, dead, worst
+
+
+# ------------------------------------------------------------------------------------------------
+# BatchTopK: the same step on rows of variable length (tests/test_gpu_batch_topk_geometry.py, tests/test_batch_topk_restatement_host_cpu.py)
+# ------------------------------------------------------------------------------------------------
+
+BTK_SPREAD = 0.5  # batch rows scaled by exp(0.5 N(0, 1)): the batch-wide select gives the quiet rows nothing and the loud ones hundreds of codes
+
+
+def btk_default_row_cap(row: Row) -> int:
+    """The slots per code row of a context created with row_cap = 0 (saev_create_batch_topk)."""
+    return min(row.s, (max(64, 4 * min(row.k, row.s)) + 63) // 64 * 64)
+
+
+# The classes of the BatchTopK step (DESIGN.md, "Parity": the BatchTopK class table).  A BatchTopK context sizes by row_cap what a TopK
+# context sizes by top_k, and its downstream kernels are the generic ones that skip idx < 0: decode_kernel / decode_matry_kernel, the
+# CSC build, gather_rows_accum, dw_rows, AuxK.  `lengths` = (shortest, longest, empty) batch rows of the fp64 select.
+BTK_SHAPES = (
+    # NV = 1 ragged (d_model % 32 != 0), k = 1: nearly every batch row is empty; S = one 256-latent tile + 4
+    Row(65, 36, 260, 1, seed=0, spread=BTK_SPREAD, lengths=(0, 25, 53)),
+    # NV = 1 ragged, S off every tile, vector-ALU AuxK (20 dead <= 40) over rows with idx = -1 slots
+    Row(200, 100, 1004, 8, n_dead=20, k_aux=64, aux_route=2, seed=0, spread=BTK_SPREAD, lengths=(0, 175, 123)),
+    # Matryoshka cuts at 1 and off every multiple of 4 over variable rows, d_model < 256: an empty row, and a row with no code below 7
+    Row(130, 96, 1000, 8, prefixes=(1, 7, 130, 1000), seed=0, spread=BTK_SPREAD, lengths=(0, 141, 79)),
+    # NV = 2; S = 1024 + 4: a second CSC scan block that holds 4 latents
+    Row(257, 512, 1028, 16, seed=1, spread=BTK_SPREAD, lengths=(0, 307, 124)),
+    # NV = 6 with the few-dead-latents AuxK route it takes (20 dead of k_aux 64)
+    Row(130, 1536, 1000, 32, n_dead=20, k_aux=64, aux_route=2, seed=3, dead_bias=-12.0, spread=BTK_SPREAD, lengths=(0, 290, 30)),
+    # the NV = 8 templates at 7, two prefixes
+    Row(70, 1664, 516, 32, prefixes=(100, 516), seed=0, spread=BTK_SPREAD, lengths=(0, 147, 14)),
+    # NV = 8 full; dense AuxK (200 dead of k_aux 64) with three prefixes
+    Row(130, 2048, 1000, 32, prefixes=(100, 300, 1000), n_dead=200, k_aux=64, aux_route=3, seed=7, dead_bias=-12.0, spread=BTK_SPREAD, lengths=(0, 201, 32)),
+    # the NV = 12 templates at 10; dense AuxK (140 dead of k_aux 128)
+    Row(66, 2560, 260, 16, n_dead=140, k_aux=128, aux_route=3, seed=7, dead_bias=-12.0, spread=BTK_SPREAD, lengths=(0, 46, 5)),
+    # NV = 16 ragged in its last float4
+    Row(130, 4092, 260, 8, seed=2, spread=BTK_SPREAD, lengths=(0, 72, 55)),
+    # ragged everything, rows past 1024 codes (a 17th 64-slot chunk of a row), dense AuxK selecting 128 of 300
+    Row(300, 772, 5004, 64, n_dead=300, k_aux=128, aux_route=3, seed=54, dead_bias=-12.0, spread=BTK_SPREAD, lengths=(0, 1086, 135)),
+    # top_k >= d_sae: every entry kept, row_cap == d_sae, no padding anywhere
+    Row(5, 16, 24, 64, seed=0, spread=BTK_SPREAD, lengths=(24, 24, 0)),
+    # one row only: the batch-wide select is that row's top-k
+    Row(1, 20, 36, 4, seed=0, spread=BTK_SPREAD, lengths=(4, 4, 0)),
+    # MAX_PREFIXES cuts (the first = 1) on variable rows
+    Row(150, 512, 1000, 16, prefixes=_P16, seed=0, spread=BTK_SPREAD, lengths=(0, 185, 54)),
+    # aux_small_fused (<= 8 dead, d_model % 256 == 0) on variable rows
+    Row(97, 256, 260, 16, n_dead=3, k_aux=16, aux_route=2, seed=0, spread=BTK_SPREAD, lengths=(0, 69, 22)),
+)
+
+
+def btk_row_inputs(row: Row):
+    """(params, x, toks) of a BTK_SHAPES row: row_inputs with every batch row scaled by exp(row.spread * N(0, 1))."""
+    from test_gpu_parity import rand_params
+
+    p = rand_params(row.d, row.s, seed=row.seed)
+    g = torch.Generator().manual_seed(row.seed + 1)
+    x = torch.randn(row.n, row.d, generator=g)
+    x = x * torch.exp(row.spread * torch.randn(row.n, 1, generator=g))
+    toks = torch.zeros(row.s, dtype=torch.int64)
+    if row.n_dead:
+        dead = torch.randperm(row.s, generator=torch.Generator().manual_seed(row.seed + 2))[:row.n_dead]
+        toks[dead] = DEAD_THR
+        p["b_enc"][dead] = row.dead_bias
+    return p, x, toks
+
+
+def btk_tol(x, W_enc) -> float:
+    """tol_b of tests/topk_exactness.py at the batch's largest row: two fp32 evaluations of any pre-activation of the batch differ by
+    at most 2 of it."""
+    return float(8.0 * 2.0 ** -24 * x.double().norm(dim=1).max() * W_enc.double().norm(dim=0).max())
+
+
+def btk_input_conditions(row: Row, W_enc, b_enc, x, toks):
+    """Asserts what makes the fp32 and the fp64 BATCH-WIDE selections of a row's inputs the same set: the fp64 (n k)-th and
+    (n k + 1)-th largest pre-activation of the whole batch lie more than 2 tol_b apart (tol_b at the batch's largest row), no dead
+    latent is selected, and for n_dead > k_aux the per-row gap of `input_conditions` between the k_aux-th and (k_aux+1)-th DEAD
+    pre-activation.  Returns (mask of the fp64 batch top-(n k) as bool, dead mask, [cut gap / tol_b, smallest dead gap / tol_b])."""
+    h = x.double() @ W_enc.double() + b_enc.double()
+    tol_b = btk_tol(x, W_enc)
+    t = row.n * min(row.k, row.s)
+    worst = [float("inf"), float("inf")]
+    if t < h.numel():
+        top = h.flatten().topk(t + 1).values
+        worst[0] = ((top[t - 1] - top[t]) / tol_b).item()
+        assert worst[0] > 2.0, f"{row.id}: the (n k)-th and (n k + 1)-th pre-activation of the batch are {worst[0]:.2f} tol_b apart"
+        mask = h >= top[t - 1]
+    else:
+        mask = torch.ones_like(h, dtype=torch.bool)
+    assert int(mask.sum()) == t
+    dead = toks >= DEAD_THR
+    assert int(dead.sum()) == row.n_dead
+    assert not mask[:, dead].any(), f"{row.id}: a dead latent is selected"
+    if row.n_dead > row.k_aux:
+        tol = 8.0 * 2.0 ** -24 * x.double().norm(dim=1) * W_enc.double().norm(dim=0).max()
         td = h[:, dead].topk(row.k_aux + 1, dim=1).values
         gap = (td[:, row.k_aux - 1] - td[:, row.k_aux]) / tol
         worst[1] = gap.min().item()
