@@ -566,6 +566,38 @@ int saev_batch_stats(const float* x, const float* x_hat, const int32_t* idx, con
  * 256-byte aligned. */
 #define SAEV_ROW_NORM_WORKSPACE_BYTES 8192
 int saev_row_norm_mean(const float* W, int64_t S, int64_t D, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+/* LATENT TOP-K (the reference's saev.helpers.csr_topk(arr, k=..., axis=0) over token_acts.npz, as a streaming update that rides
+ * along the inference pass), context-free: for every latent j the k largest codes seen so far and the rows they sit in.
+ * State is the caller's device memory, latent-major, ZERO-INITIALISED by the caller before the first update:
+ *   top_val (S x k fp32), top_row (S x k int64), top_cnt (S int32; entries held, at most k)
+ * After every update latent j's first top_cnt[j] slots hold its best entries in the order (value descending, row ascending) --
+ * the TIE RULE: among equal values the lower row wins, whatever order the batches arrive in; the later slots are never written
+ * (they keep the caller's zeros, which is how the reference pads).  1 <= k <= 64 (anything else is SAEV_UNSUPPORTED).
+ * One update consumes one batch of n rows in ONE of two forms (both or neither is SAEV_INVALID_ARG):
+ *   padded rows  idx (n x cap int32), val (n x cap fp32), row_nnz (n int32, may be NULL: every slot is an entry; a count above cap
+ *                reads as cap)
+ *   CSR          row_ptr (n + 1 int64, absolute positions into indices / data, non-decreasing), indices (int32), data (fp32), and
+ *                nnz = row_ptr[n] - row_ptr[0] given by the host (nothing is read back)
+ * keep (n bytes, may be NULL): rows with keep[b] == 0 contribute nothing.  The row id of local row b is row_base + b.
+ * An ENTRY is a slot with val != 0 (zeros of both signs are none) whose latent lies in [0, S); negatives and +-Inf are entries;
+ * NaN is outside the contract, and so is more than one entry per (row, latent).
+ * Exact and BIT-REPRODUCIBLE: integer atomics only (candidate counts and placement), the lists ordered by a total order on
+ * (value, row).  No n x S temporary, nothing read back, nothing synchronises.  n = 0 returns SAEV_OK and writes nothing.
+ * workspace: saev_latent_topk_workspace_bytes(n_entries, S) bytes of device memory, 256-byte aligned, n_entries = n cap or nnz
+ * (at most 2^31 - 1 per update; -1: unsupported).  Arguments are checked before the device is touched; a refused call leaves its
+ * message with saev_last_error(NULL). */
+typedef struct {
+    int32_t struct_size;   /* sizeof(saev_latent_topk_state) of the caller (fields past it read as 0) */
+    int32_t k;
+    float* top_val;
+    int64_t* top_row;
+    int32_t* top_cnt;
+} saev_latent_topk_state;
+int64_t saev_latent_topk_workspace_bytes(int64_t n_entries, int64_t S);
+int saev_latent_topk_update(const int32_t* idx, const float* val, const int32_t* row_nnz, int64_t cap, const int64_t* row_ptr,
+                            const int32_t* indices, const float* data, int64_t nnz, const uint8_t* keep, int64_t n, int64_t S,
+                            int64_t row_base, const saev_latent_topk_state* state, void* workspace, int64_t workspace_bytes,
+                            void* stream);
 /* PARAMETER OWNERSHIP.  With the f16r encoder the context keeps, from one call to the next, what its forward needs of W_enc
  * (fp16 operand images, a slice-major fp32 transpose, bias and norm shares: written by the Adam launch of saev_train_step, or by
  * the last forward that prepared them itself) and uses it for as long as only the library has written the parameter buffer.  A

@@ -68,6 +68,12 @@ class SaevBatchTopKCfg(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class SaevLatentTopKState(C.Structure):
+    """include/saev_amd.h: saev_latent_topk_state (the caller's per-latent lists; zero-initialised before the first update)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("k", C.c_int32), ("top_val", C.c_void_p), ("top_row", C.c_void_p), ("top_cnt", C.c_void_p)]
+
+
 ACT_TOPK, ACT_RELU, ACT_BATCHTOPK = 0, 1, 2
 ROW_OVERFLOW = -7  # saev_status SAEV_ROW_OVERFLOW
 BATCH_OVERWRITE = 1
@@ -152,6 +158,9 @@ _SIGNATURES = {
     "saev_batch_stats_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "saev_batch_stats": (C.c_int, [P, P, P, P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(SaevBatchAcc), P, C.c_int64, P]),
     "saev_row_norm_mean": (C.c_int, [P, C.c_int64, C.c_int64, P, P, C.c_int64, P]),
+    "saev_latent_topk_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "saev_latent_topk_update": (C.c_int, [P, P, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int64,
+                                          C.POINTER(SaevLatentTopKState), P, C.c_int64, P]),
     "saev_comm_unique_id": (C.c_int, [P]),
     "saev_comm_init": (C.c_int, [P, P, C.c_int32, C.c_int32]),
     "saev_comm_world": (C.c_int, [P]),

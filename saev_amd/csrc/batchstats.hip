@@ -215,6 +215,7 @@ int refuse(int code, const std::string& msg) {
 }  // namespace
 
 const char* free_error() { return g_free_err.empty() ? "null context" : g_free_err.c_str(); }
+int free_refuse(int code, const char* msg) { return refuse(code, msg); }
 
 int64_t saev_batch_stats_workspace_bytes(int64_t n, int64_t D) {
     if (n < 0 || n > 0x7fffffffLL || D < 4 || D > 4096 || D % 4 != 0) return -1;

@@ -784,3 +784,5 @@ hipError_t launch_coherence(const float* W, int S, int D, int route, uint8_t* ws
 // ---- Batch statistics (batchstats.hip: kernels and their C entries) ---------------------------------------------------------
 // message of the last refused context-free call on this thread ("null context" before any): what saev_last_error(NULL) returns
 const char* free_error();
+// leaves `msg` there and returns `code`: how a context-free entry of another file refuses a call (latenttopk.hip)
+int free_refuse(int code, const char* msg);

@@ -320,6 +320,113 @@ class BatchStats:
                               n_pos=part["n_pos"], value_sum=part["value_sum"], live=part["live"])
 
 
+@dataclasses.dataclass(frozen=True)
+class LatentTopKHost:
+    """What ``LatentTopK.read()`` brings back (CPU tensors): ``values`` / ``indices`` as the reference's
+    ``csr_topk(axis=0)`` shapes and pads them, and how many slots of each column are real."""
+
+    values: torch.Tensor   # (k, S) float32, descending in each column, 0 past the latent's count
+    indices: torch.Tensor  # (k, S) int64 row ids, 0 past the latent's count
+    counts: torch.Tensor   # (S) int64
+
+
+class LatentTopK:
+    """Per-latent top-k activating rows over a stream of batches (include/saev_amd.h: LATENT TOP-K): the device
+    state of saev_latent_topk_update -- ``top_val`` (S, k) float32, ``top_row`` (S, k) int64, ``top_cnt`` (S) int32 -- and its
+    workspace.  ``add`` takes padded code rows, ``add_csr`` a CSR block; ``read`` is the only device-to-host copy.  Entries order
+    by (value descending, row ascending), so the result does not depend on the order the batches arrive in."""
+
+    MAX_K = 64
+
+    def __init__(self, d_sae: int, k: int, device):
+        if not 1 <= k <= self.MAX_K:
+            raise ValueError(f"LatentTopK: unsupported k {k} (1 <= k <= {self.MAX_K})")
+        if d_sae < 1 or d_sae >= 2**31:
+            raise ValueError(f"LatentTopK: unsupported d_sae {d_sae}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("LatentTopK runs on a HIP device only (there is no CPU path)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = _lib.load()
+        self.d_sae, self.k = d_sae, k
+        self.top_val = torch.zeros(d_sae, k, device=self.device, dtype=torch.float32)
+        self.top_row = torch.zeros(d_sae, k, device=self.device, dtype=torch.int64)
+        self.top_cnt = torch.zeros(d_sae, device=self.device, dtype=torch.int32)
+        self._ws = None
+        self._state = _lib.SaevLatentTopKState(struct_size=C.sizeof(_lib.SaevLatentTopKState), k=k, top_val=_ptr(self.top_val),
+                                               top_row=_ptr(self.top_row), top_cnt=_ptr(self.top_cnt))
+
+    def zero_(self) -> "LatentTopK":
+        for t in (self.top_val, self.top_row, self.top_cnt):
+            t.zero_()
+        return self
+
+    def _workspace(self, n_entries: int):
+        need = int(self.lib.saev_latent_topk_workspace_bytes(n_entries, self.d_sae))
+        if need < 0:
+            raise _lib.SaevError(f"saev_latent_topk_update: {n_entries} entries in one batch (at most 2^31 - 1)")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        return self._ws
+
+    def _chk(self, t, dtype, shape, what):
+        if t is None:
+            return None
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device:
+            raise ValueError(f"{what} must be {dtype} of shape {shape} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.contiguous()
+
+    def _keep(self, keep, n: int):
+        if keep is None:
+            return None
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        if keep.dtype != torch.uint8 or keep.shape != (n,) or keep.device != self.device or not keep.is_contiguous():
+            raise ValueError(f"keep must be a contiguous bool / uint8 vector of {n} rows on {self.device}")
+        return keep
+
+    def _update(self, idx, val, row_nnz, cap: int, row_ptr, indices, data, nnz: int, keep, n: int, row_base: int) -> None:
+        if row_base < 0:
+            raise ValueError(f"row_base must be >= 0, got {row_base}")
+        ws = self._workspace(n * cap if row_ptr is None else nnz)
+        with torch.cuda.device(self.device):
+            rc = self.lib.saev_latent_topk_update(idx, val, row_nnz, cap, row_ptr, indices, data, nnz, _ptr(self._keep(keep, n)), n,
+                                                  self.d_sae, row_base, C.byref(self._state), _ptr(ws), ws.numel(), _stream())
+        _lib.check(self.lib, None, rc, "saev_latent_topk_update")
+
+    def add(self, idx: torch.Tensor, val: torch.Tensor, row_nnz: torch.Tensor | None = None, keep: torch.Tensor | None = None, *,
+            row_base: int) -> None:
+        """One batch of padded code rows: idx (n, cap) int32, val (n, cap) float32, row_nnz (n) int32 (None: full rows), keep (n)
+        bool; local row b is row ``row_base + b``."""
+        if idx.ndim != 2:
+            raise ValueError(f"idx must be (n, cap), got {tuple(idx.shape)}")
+        n, cap = idx.shape
+        idx = self._chk(idx, torch.int32, (n, cap), "idx")
+        val = self._chk(val, torch.float32, (n, cap), "val")
+        row_nnz = self._chk(row_nnz, torch.int32, (n,), "row_nnz")
+        if n == 0 or cap == 0:
+            return
+        self._update(_ptr(idx), _ptr(val), _ptr(row_nnz), cap, None, None, None, 0, keep, n, row_base)
+
+    def add_csr(self, indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, keep: torch.Tensor | None = None, *,
+                row_base: int) -> None:
+        """One CSR block on the device: indptr (n + 1) int64 starting at 0, indices (nnz) int32, data (nnz) float32."""
+        if indptr.ndim != 1 or indptr.numel() < 1:
+            raise ValueError(f"indptr must be a vector of n + 1 offsets, got {tuple(indptr.shape)}")
+        n, nnz = indptr.numel() - 1, indices.numel()
+        indptr = self._chk(indptr, torch.int64, (n + 1,), "indptr")
+        indices = self._chk(indices, torch.int32, (nnz,), "indices")
+        data = self._chk(data, torch.float32, (nnz,), "data")
+        if n == 0 or nnz == 0:
+            return
+        self._update(None, None, None, 0, _ptr(indptr), _ptr(indices), _ptr(data), nnz, keep, n, row_base)
+
+    def read(self) -> LatentTopKHost:
+        return LatentTopKHost(values=self.top_val.t().contiguous().cpu(), indices=self.top_row.t().contiguous().cpu(),
+                              counts=self.top_cnt.to(torch.int64).cpu())
+
+
 @dataclasses.dataclass
 class StepStats:
     mse: float
@@ -966,6 +1073,18 @@ class SaeEngine:
         p = lambda v: C.c_void_p(v)  # noqa: E731
         acc._add_ptrs(_ptr(x), p(self.lib.saev_last_x_hat(self.ctx)) if x_hat else None, p(self.lib.saev_last_idx(self.ctx)),
                       p(self.lib.saev_last_val(self.ctx)), None, keep, x.shape[0], self._code_width(), overwrite, scalars)
+
+    def add_latent_topk(self, acc: LatentTopK, keep: torch.Tensor | None = None, *, row_base: int) -> None:
+        """Feed the codes of the last ``step_forward`` to ``acc`` straight from the context (saev_last_idx / _val): no copy is
+        made.  TopK rows are full; BatchTopK rows are padded with idx = -1, which the kernel ignores."""
+        self._trains("add_latent_topk")
+        if self._last_n == 0:
+            raise _lib.SaevError("add_latent_topk: no step_forward to take codes from")
+        if acc.d_sae != self.cfg.d_sae or acc.device != self.device:
+            raise _lib.SaevError("add_latent_topk: the accumulator was made for another shape or device")
+        p = lambda v: C.c_void_p(v)  # noqa: E731
+        acc._update(p(self.lib.saev_last_idx(self.ctx)), p(self.lib.saev_last_val(self.ctx)), None, self._code_width(), None, None, None, 0,
+                    keep, self._last_n, row_base)
 
     def _code_width(self) -> int:
         """Columns of the context's code rows: top_k, or the row capacity of a BatchTopK engine."""

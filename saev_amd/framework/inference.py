@@ -9,6 +9,9 @@ Writes under ``<run>/inference/<metadata hash>/``:
     mean_values.pt     (d_sae,) sum of activations / number of tokens with f > 0   (save=True only)
     sparsity.pt        (d_sae,) fraction of tokens with f > 0                      (save=True only)
     distributions.pt   (n_tokens, n_dists), rows written at ``example_idx``        (save=True only)
+    top_tokens.pt      {"values" (k, d_sae) float32, "indices" (k, d_sae) int64, "counts" (d_sae,) int64}: per latent the k largest
+                       activations and the global token rows (rows of token_acts.npz) they sit in, what the reference's
+                       ``helpers.csr_topk(token_acts, k=k, axis=0)`` returns   (``worker_fn(cfg, top_k_tokens=k)`` only)
 
 The reference materialises the dense (B, d_sae) ``f_x`` per batch, copies it to the host and lets scipy compress it
 (inference.py:189-246).  Here the codes never leave their sparse form: the HIP encoder returns (idx, val) with
@@ -30,9 +33,9 @@ import numpy as np
 import scipy.sparse
 import torch
 
-from .. import disk, nn
+from .. import disk, helpers, nn
 from ..data import Metadata, OrderedConfig, OrderedDataLoader
-from ..engine import BatchStats
+from ..engine import BatchStats, LatentTopK
 from ..metrics import Metrics
 
 logger = logging.getLogger("inference.py")
@@ -105,14 +108,47 @@ def _jsonable(o):
     return o
 
 
+TOP_TOKENS = "top_tokens.pt"
+
+
+def _save_top_tokens(path: pathlib.Path, values, indices, counts) -> None:
+    torch.save({"values": values, "indices": indices, "counts": counts}, path)
+
+
+def _top_tokens_current(path: pathlib.Path, k: int, d_sae: int) -> bool:
+    """Whether ``path`` holds lists of this k for this many latents (a file of another k is rebuilt, never handed out as k's)."""
+    if not path.exists():
+        return False
+    values = torch.load(path)["values"]
+    return tuple(values.shape) == (k, d_sae)
+
+
 @torch.inference_mode()
-def worker_fn(cfg: Config):
+def worker_fn(cfg: Config, *, top_k_tokens: int = 0):
+    """``top_k_tokens`` = k > 0 also keeps, per latent, the k largest activations of the pass and their global token rows
+    (engine.LatentTopK, fed from the codes on the device) and writes them as ``top_tokens.pt``.  When the pass is up to date, a
+    ``top_tokens.pt`` that is missing or holds another k is rebuilt from ``token_acts.npz``.  0 keeps no lists; a pass that rewrites
+    ``token_acts.npz`` without them removes a ``top_tokens.pt`` left by an earlier pass, which would no longer describe it."""
+    if top_k_tokens < 0 or top_k_tokens > LatentTopK.MAX_K:
+        raise ValueError(f"top_k_tokens must lie in [0, {LatentTopK.MAX_K}], got {top_k_tokens}")
     run = disk.Run(cfg.run)
     md = Metadata.load(_shards_dir(cfg))
     root = run.inference / md.hash
     do, reason, fpaths = need_compute(cfg)
     logger.info(reason)
     if not do:
+        if top_k_tokens > 0 and fpaths.token_acts.exists():
+            # the pass is up to date; lists that are missing, or were kept for another k, are selected from the saved codes
+            token_acts = scipy.sparse.load_npz(fpaths.token_acts).tocsr()
+            if _top_tokens_current(root / TOP_TOKENS, top_k_tokens, token_acts.shape[1]):
+                return
+            device = torch.device(cfg.device)
+            if device.type != "cuda":
+                raise RuntimeError("saev_amd inference runs on a HIP device only (there is no CPU path)")
+            got = helpers._topk_axis0(token_acts, top_k_tokens, 1024, device)
+            counts = np.minimum(np.bincount(token_acts.indices[token_acts.data != 0], minlength=token_acts.shape[1]), top_k_tokens)
+            _save_top_tokens(root / TOP_TOKENS, torch.from_numpy(got.values.astype(np.float32)), torch.from_numpy(got.indices),
+                             torch.from_numpy(counts.astype(np.int64)))
         return
     with open(root / "config.json", "w") as fd:
         json.dump(_jsonable(cfg), fd)
@@ -133,6 +169,7 @@ def worker_fn(cfg: Config):
     # every sum of the pass -- column sums of x, sum x^2 and sum (x - x_hat)^2 over the kept rows in fp64, per-latent positive
     # counts and value sums -- from one kernel per batch, TopK or ReLU, masked or not (engine.BatchStats)
     acc = BatchStats(D, S, device, want=("scalars", "col_sum", "n_pos", "value_sum") if cfg.save else ("scalars", "col_sum"))
+    top = LatentTopK(S, top_k_tokens, device) if top_k_tokens > 0 else None
     if cfg.save:
         distributions = np.zeros((loader.n_samples, cfg.n_dists), dtype=np.float32)
         csr_data: list[np.ndarray] = []
@@ -169,6 +206,12 @@ def worker_fn(cfg: Config):
                 eng.add_batch_stats(acc, x, x_hat=False, scalars=False)
             else:
                 eng.add_batch_stats(acc, x, mask)
+            if top is not None:  # the batch's first global token index: the rows of token_acts.npz
+                row_base = int(batch["example_idx"][0]) * T + int(batch["token_idx"][0])
+                if relu:
+                    top.add(idx, val, row_nnz, mask, row_base=row_base)
+                else:
+                    eng.add_latent_topk(top, mask, row_base=row_base)
         if not cfg.save:
             continue
         if not relu:
@@ -194,6 +237,11 @@ def worker_fn(cfg: Config):
         distributions[batch["example_idx"][keep_host].numpy()] = head.cpu().numpy()[keep_host.numpy()]
 
     got = acc.read()
+    if top is not None:
+        lists = top.read()
+        _save_top_tokens(root / TOP_TOKENS, lists.values, lists.indices, lists.counts)
+    elif cfg.save:
+        (root / TOP_TOKENS).unlink(missing_ok=True)  # lists of an earlier pass do not describe the token_acts.npz written below
     if cfg.save:
         counts = np.concatenate(csr_counts) if csr_counts else np.zeros(0, dtype=np.int64)
         indptr = np.zeros(counts.shape[0] + 1, dtype=np.int64)
@@ -221,7 +269,7 @@ def worker_fn(cfg: Config):
     return metrics
 
 
-def main(cfgs: Config | list[Config]) -> int:
+def main(cfgs: Config | list[Config], *, top_k_tokens: int = 0) -> int:
     """Run the configs one after another in this process (the reference can also submit them to Slurm,
     inference.py:288-364; cluster submission is outside this package)."""
     cfgs = [cfgs] if isinstance(cfgs, Config) else list(cfgs)
@@ -229,6 +277,6 @@ def main(cfgs: Config | list[Config]) -> int:
         if c.slurm_acct:
             raise NotImplementedError("Slurm submission is not part of saev_amd; run worker_fn on the node directly")
         logger.info("Running config %d/%d locally.", i, len(cfgs))
-        worker_fn(c)
+        worker_fn(c, top_k_tokens=top_k_tokens)
     logger.info("Jobs done.")
     return 0
