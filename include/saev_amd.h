@@ -1,5 +1,5 @@
 /*
- * saev_amd.h — C ABI of libsaev_amd.so: the MI355X (gfx950) TopK / BatchTopK SAE train-step path and the ReLU forward.
+ * saev_amd.h — C ABI of libsaev_amd.so: the MI355X (gfx950) TopK / BatchTopK / ReLU SAE train-step path and the ReLU forward.
  *
  * This is the drop-in boundary for the hot path of OSU-NLP-Group/saev.  The reference has no FFI of
  * its own (it is pure PyTorch); each entry point below names the reference code it replaces
@@ -79,10 +79,11 @@ typedef struct {
                                       copies and partial rows -- the forward's buffers (candidate lists, dense fallback,
                                       AuxK, ...) stay at max_batch, which is then the LOCAL batch.                      */
     int32_t activation;            /* SAEV_ACT_TOPK (0), SAEV_ACT_RELU or SAEV_ACT_BATCHTOPK (BATCHTOPK below).  A ReLU context (nn/modeling.py:111-113 Relu, :150-156
-                                      ReluActivation) ignores top_k and needs k_aux = 0; it runs the forward entries only:
-                                      saev_encode_relu, saev_decode_rows, saev_scatter_rows and the single ops, while the
-                                      step entries and saev_encode_topk return SAEV_UNSUPPORTED (training a ReLU SAE is not
-                                      on this path).                                                                 */
+                                      ReluActivation) ignores top_k and needs k_aux = 0.  Made by saev_create / saev_create_ex it
+                                      runs the forward entries only: saev_encode_relu, saev_decode_rows, saev_scatter_rows and the
+                                      single ops, while the step entries and saev_encode_topk return SAEV_UNSUPPORTED -- it
+                                      allocates none of a step's scratch.  TRAINING a ReLU SAE takes a context kind of its own,
+                                      made by saev_create_relu_train (RELU TRAINING below).                              */
 } saev_cfg;
 
 #define SAEV_ACT_TOPK 0
@@ -243,6 +244,38 @@ int saev_batch_topk_state(saev_ctx* ctx, float* cut, int64_t* n_above, int64_t* 
 /* row_nnz (n_rows int32) of the last saev_step_forward of a BatchTopK context, copied like saev_copy_last copies the padded rows
  * (idx / val there are n_rows x row_cap). */
 int saev_copy_last_row_nnz(saev_ctx* ctx, int32_t n_rows, int32_t* row_nnz_out, void* stream);
+
+/* RELU TRAINING (nn/modeling.py:109-117 Relu, :150-156 ReluActivation; nn/objectives.py:101-156 with L1Sparsity / NoSparsity):
+ * a dense step on the matrix cores.  For h = x W_enc + b_enc (n x S), f = max(h, 0), x_hat = f W_dec + b_dec:
+ *     loss = mse(x_hat, x) + l1_coeff * mean_b sum_s f[b, s]          (the rescaled mse of objectives.py:224-237, mean over n D)
+ * With b_enc = 0 about half of the latents fire in every row, so the codes are not sparse and the step is four dense contractions
+ * whose cost does not depend on the density: x_hat = f W_dec, dA = g W_dec^T, dW_dec = f^T g, dW_enc = x^T dH with
+ * g = dL/dx_hat and dH = (dA + l1_coeff / n) where f > 0, else 0 -- all on the split-fp16 MFMA kernel (fp32-accurate), h from the
+ * context's exact dense encoder (as saev_encode_dense).  Every sum has a fixed order: the same inputs give the same bits.
+ * saev_create_relu_train makes the context: cfg->activation must be SAEV_ACT_RELU and cfg->k_aux 0 (anything else is
+ * SAEV_INVALID_ARG, before the device is touched); encoder_mode BF16 and shard_world > 1 are SAEV_UNSUPPORTED.  It serves what a
+ * forward-only ReLU context serves (saev_encode_relu, saev_decode_rows, saev_scatter_rows, the single ops) and saev_step_forward /
+ * _dead / _backward / _tail, saev_muon_tail and saev_train_step (= the four phases back to back).  saev_step_stats: mse, l0 (mean
+ * count of f > 0 per row), l1 (mean sum of f per row), sse, sum_sq, upper, n_dead, grad_norm; aux = 0, saev_last_aux_route = 0.
+ * TWO LIMITS.  (1) The plain objective only: saev_set_prefixes with more than one prefix is SAEV_UNSUPPORTED (nested prefixes over
+ * dense contractions are one contraction per prefix block -- a piece of work of its own).  (2) One GPU, one piece: n_rows_global
+ * must equal n_rows; saev_train_step_dp, saev_train_step_gather, saev_share_x (either side), saev_backward_begin / _rows / _end
+ * (the backward runs whole: saev_step_backward), saev_backward_override and saev_copy_step_state are SAEV_UNSUPPORTED.
+ * saev_last_idx / _val mean nothing on such a context (its codes are the dense f): saev_copy_last_rows compacts them. */
+typedef struct {
+    int32_t struct_size;   /* sizeof(saev_relu_train_cfg) of the caller (fields past it read as 0)                           */
+    int32_t reserved;
+    double l1_coeff;       /* L1Sparsity.coeff as the reference's Python float (0: NoSparsity); the kernels use float(l1_coeff / n) */
+} saev_relu_train_cfg;
+/* rt NULL: l1_coeff = 0 */
+int saev_create_relu_train(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_relu_train_cfg* rt, int device, saev_ctx** out);
+/* The codes of the last saev_step_forward of a ReLU training context as PADDED ROWS, compacted from its dense f into the caller's
+ * buffers: idx_out / val_out (n_rows x row_cap), row b's entries (f > 0) in its first row_nnz_out[b] slots in ascending latent
+ * order, the other slots idx = -1, val = 0.  row_nnz_out[b] is exact also past row_cap; *overflow_out (a device int32) = 0 when
+ * every row fit, else the largest count -- the caller reads it back and repeats the call with row_cap >= that count, as after
+ * saev_encode_relu (a row is never silently truncated).  n_rows must equal the batch of that forward. */
+int saev_copy_last_rows(saev_ctx* ctx, int32_t n_rows, int32_t row_cap, int32_t* row_nnz_out, int32_t* idx_out, float* val_out,
+                        int32_t* overflow_out, void* stream);
 
 /* Borrow the caller's flat buffers (see layout above).  grads/adam_m/adam_v may be NULL for a
  * forward-only context.  Pointers must stay valid until re-bound or destroy. */

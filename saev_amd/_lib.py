@@ -68,6 +68,12 @@ class SaevBatchTopKCfg(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class SaevReluTrainCfg(C.Structure):
+    """include/saev_amd.h: saev_relu_train_cfg (settings of a ReLU training context beside saev_cfg)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("l1_coeff", C.c_double)]
+
+
 class SaevLatentTopKState(C.Structure):
     """include/saev_amd.h: saev_latent_topk_state (the caller's per-latent lists; zero-initialised before the first update)."""
 
@@ -92,6 +98,8 @@ _SIGNATURES = {
     "saev_create": (C.c_int, [C.POINTER(SaevCfg), C.c_int, C.POINTER(P)]),
     "saev_create_ex": (C.c_int, [C.POINTER(SaevCfg), C.POINTER(SaevDebugCfg), C.c_int, C.POINTER(P)]),
     "saev_create_batch_topk": (C.c_int, [C.POINTER(SaevCfg), C.POINTER(SaevDebugCfg), C.POINTER(SaevBatchTopKCfg), C.c_int, C.POINTER(P)]),
+    "saev_create_relu_train": (C.c_int, [C.POINTER(SaevCfg), C.POINTER(SaevDebugCfg), C.POINTER(SaevReluTrainCfg), C.c_int, C.POINTER(P)]),
+    "saev_copy_last_rows": (C.c_int, [P, C.c_int32, C.c_int32, P, P, P, P, P]),
     "saev_bind_threshold": (C.c_int, [P, P]),
     "saev_threshold_device": (P, [P]),
     "saev_row_cap": (C.c_int32, [P]),

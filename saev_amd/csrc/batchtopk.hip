@@ -301,6 +301,17 @@ __global__ void btk_ema_kernel(const uint32_t* st, const int32_t* overflow, floa
 
 }  // namespace
 
+// the eval-mode compaction alone (h > max(*threshold, 0)) into rows of any capacity: a.training must be 0, a.st / a.row_ties are not read
+hipError_t launch_threshold_compact(const BtkCompactArgs& a, hipStream_t s) {
+    if (a.n_rows <= 0) return hipSuccess;
+    if (a.training != 0) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(a.overflow, 0, sizeof(int32_t), s);
+    if (e != hipSuccess) return e;
+    const int row_blocks = (a.n_rows + BTK_THREADS / 64 - 1) / (BTK_THREADS / 64);
+    hipLaunchKernelGGL(btk_compact_kernel, dim3(row_blocks), dim3(BTK_THREADS), 0, s, a);
+    return hipGetLastError();
+}
+
 size_t btk_workspace_words(int max_rows) { return (size_t)BTK_ST_WORDS + 3 * BTK_BINS + BTK_LIST_CAP + 2 * (size_t)max_rows; }
 
 hipError_t launch_batch_topk(const BtkArgs& a, hipStream_t s) {

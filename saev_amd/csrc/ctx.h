@@ -246,6 +246,19 @@ struct saev_ctx {
     uint32_t* btk_ws = nullptr;       // select state, histograms, key list, per-row tie counters (btk_workspace_words)
     int32_t *row_nnz = nullptr, *btk_over = nullptr;  // of the last forward; the overflow word
     int btk_need = 0;                 // after SAEV_ROW_OVERFLOW: the largest row count met
+    // ReLU training (include/saev_amd.h: RELU TRAINING; ctx_relu_train.hip, kernels in relu_train.hip): a context kind of its own
+    // (saev_create_relu_train) with cfg.activation = SAEV_ACT_RELU.  f lives in h_dense, dH in rt_dA after the backward.
+    bool relu_train = false;
+    bool rt_fwd_live = false;         // a training forward's f images are in place: cleared by the backward, which overwrites them with dH's
+    double rt_l1 = 0.0;               // the L1 coefficient (objectives.py: sparsity = coeff * l1)
+    float* rt_dA = nullptr;           // (max_batch x d_sae) g W_dec^T, then dH in place
+    float *rt_parts = nullptr, *rt_colpart = nullptr;  // per-workgroup maxima; column sums of dH per block of rows
+    float* rt_scales = nullptr;       // operand scales {2^e, 1}: [0] f, [2] g, [4] dH, [6] x
+    int rt_Sp = 0, rt_kpad = 0;       // d_sae rounded up to 32; the batch axis padded for the split-K weight gradients
+    _Float16 *rt_xsF = nullptr, *rt_xsG = nullptr;    // row-operand images of f (k = d_sae) and of g (k = d_model)
+    _Float16 *rt_wsR = nullptr, *rt_wsK = nullptr;    // W_dec as "encoder" of dA (rows = latents) and of x_hat (rows = d_model columns)
+    _Float16 *rt_kF = nullptr, *rt_kG = nullptr, *rt_kX = nullptr;  // k-major images (k = batch) of f / dH, of g and of x
+    float* rt_wparts = nullptr;       // split-K partial products of a weight gradient
     // state of the step in flight
     const float* x_last = nullptr;
     int n_last = 0;
@@ -330,7 +343,24 @@ inline int encoder_splits(int n_rows, int S, int tile_rows, int tile_latents, in
 
 inline bool fused_supported(const saev_cfg& c) { return c.top_k <= 64; }
 
+// slices and padded length of the batch-long contraction of an R x C weight gradient on the split-fp16 kernel (a single slice would
+// leave most CUs idle when R x C is only a few tiles): the k-major images of its operands are laid out for them
+inline void ksplit_shape(int R, int C, int K, int* n_split_out, int* Kp_out) {
+    const int R256 = (R + 255) / 256 * 256, C256 = (C + 255) / 256 * 256;
+    const int tiles = (R256 / 256) * (C256 / 256);
+    int n_split = 1;
+    while (n_split < AUX_KSPLIT_MAX && tiles * n_split < 256) n_split *= 2;
+    *n_split_out = n_split;
+    *Kp_out = (K + 16 * n_split - 1) / (16 * n_split) * (16 * n_split);
+}
+
 // internal functions that cross a unit boundary
+int create_context(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_batch_topk_cfg* bt, const saev_relu_train_cfg* rt, int device,
+                   saev_ctx** out);             // ctx.hip: what every saev_create_* ends in
+int encode_dense_h(saev_ctx* c, const float* x, int n, hipStream_t s);  // ctx_forward.hip: h = x W_enc + b_enc into h_dense, exact fp32 (BatchTopK and ReLU steps)
+int relu_train_alloc(saev_ctx* c);              // ctx_relu_train.hip: the dense step's scratch (create_context)
+int relu_train_forward(saev_ctx* c, const float* x, int n, int64_t n_rows_global, int training, hipStream_t s);  // (saev_step_forward)
+int relu_train_backward(saev_ctx* c, hipStream_t s);                                                              // (saev_step_backward)
 int alloc_aux_buffers(saev_ctx* c, int cap);    // ctx_auxk.hip: the dead-set buffers (saev_create_*, and saev_step_dead grows them)
 int auxk_backward(saev_ctx* c, hipStream_t s);  // ctx_auxk.hip: gradients of the auxiliary loss (saev_backward_begin)
 int muon_cfg_check(const saev_muon_cfg& m, std::string* why);  // ctx.hip (saev_muon_newton_schulz, saev_muon_tail)

@@ -38,6 +38,25 @@ int saev_create_ex(const saev_cfg* cfg, const saev_debug_cfg* dbg, int device, s
 }
 
 int saev_create_batch_topk(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_batch_topk_cfg* bt_in, int device, saev_ctx** out) {
+    return create_context(cfg, dbg, bt_in, nullptr, device, out);
+}
+
+int saev_create_relu_train(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_relu_train_cfg* rt, int device, saev_ctx** out) {
+    if (!cfg || !out) return SAEV_INVALID_ARG;
+    *out = nullptr;
+    if (cfg->activation != SAEV_ACT_RELU || cfg->k_aux != 0) return SAEV_INVALID_ARG;
+    saev_relu_train_cfg r{};
+    if (rt != nullptr && rt->struct_size > 0) std::memcpy(&r, rt, std::min((size_t)rt->struct_size, sizeof(r)));
+    if (!(r.l1_coeff >= 0.0) || !std::isfinite(r.l1_coeff)) return SAEV_INVALID_ARG;
+    if (cfg->encoder_mode == SAEV_ENCODER_BF16 || cfg->shard_world > 1 || cfg->max_backward_rows > cfg->max_batch) return SAEV_UNSUPPORTED;
+    r.struct_size = (int32_t)sizeof(r);
+    return create_context(cfg, dbg, nullptr, &r, device, out);
+}
+
+}  // extern "C"
+
+int create_context(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_batch_topk_cfg* bt_in, const saev_relu_train_cfg* rt, int device,
+                   saev_ctx** out) {
     if (!cfg || !out) return SAEV_INVALID_ARG;
     *out = nullptr;
     if (cfg->activation != SAEV_ACT_TOPK && cfg->activation != SAEV_ACT_RELU && cfg->activation != SAEV_ACT_BATCHTOPK) return SAEV_INVALID_ARG;
@@ -83,6 +102,8 @@ int saev_create_batch_topk(const saev_cfg* cfg, const saev_debug_cfg* dbg, const
         std::memcpy(&c->dbg, dbg, std::min((size_t)dbg->struct_size, sizeof(saev_debug_cfg)));
     c->device = device;
     c->btk = btk; c->btk_k = btk_k; c->btk_momentum = bt.batch_momentum; c->btk_list_cap = bt.list_cap;
+    c->relu_train = rt != nullptr;
+    c->rt_l1 = rt != nullptr ? rt->l1_coeff : 0.0;
     if (hipSetDevice(device) != hipSuccess) {
         delete c;
         return SAEV_HIP_ERROR;
@@ -150,7 +171,7 @@ int saev_create_batch_topk(const saev_cfg* cfg, const saev_debug_cfg* dbg, const
     }
     A(colsum_partials, ((MBB + 63) / 64) * D);
     A(sumsq_partials, 2 * 1024 + (S + 3) / 4 + 8 + transpose_blocks((int)S, (int)D)); A(sumsq_total, 1);
-    if (c->cfg.encoder_mode != SAEV_ENCODER_F32 || KA > 0) {  // (the f32 encoder needs the image geometry for AuxK only)
+    if (c->cfg.encoder_mode != SAEV_ENCODER_F32 || KA > 0 || c->relu_train) {  // (the f32 encoder needs the image geometry for AuxK and the dense ReLU step only)
         c->Dp = (int)((D + 31) / 32 * 32);
         c->S_pad = (int)((S + 255) / 256 * 256);
         c->MB_pad = (int)((MB + 255) / 256 * 256);
@@ -175,6 +196,7 @@ int saev_create_batch_topk(const saev_cfg* cfg, const saev_debug_cfg* dbg, const
     A(tau_max, MB); A(heur_state, 8); A(stats_scratch, STATS_SCRATCH_DOUBLES); A(tickets, 8); A(db_aux, D);
     if (btk) { A(btk_ws, btk_workspace_words((int)MB)); A(row_nnz, MB); A(btk_over, 1); A(threshold_own, 1); }
 #undef A
+    if (rc == SAEV_OK && c->relu_train) rc = relu_train_alloc(c);
     if (rc != SAEV_OK) {
         // keep the context so the caller can read the message, but report failure
         for (void* p : c->allocs) hipFree(p);
@@ -248,6 +270,8 @@ int saev_create_batch_topk(const saev_cfg* cfg, const saev_debug_cfg* dbg, const
     return SAEV_OK;
 }
 
+extern "C" {
+
 // c stops following its leader (which forgets it, or is going away: the caller takes c off its list)
 static void detach_follower(saev_ctx* c) {
     c->leader = nullptr;
@@ -320,6 +344,7 @@ int saev_set_prefixes(saev_ctx* c, const int64_t* prefixes_host, int32_t n) {
         c->P = 1;
         return SAEV_OK;
     }
+    REQUIRE(c, !c->relu_train, SAEV_UNSUPPORTED, "saev_set_prefixes: the dense ReLU step implements the plain objective only (n_prefixes = 1)");
     REQUIRE(c, n <= MAX_PREFIXES, SAEV_UNSUPPORTED, "at most 16 Matryoshka prefixes are supported");
     REQUIRE(c, prefixes_host[0] >= 1 && prefixes_host[n - 1] == S, SAEV_INVALID_ARG,
             "prefixes must start at >= 1 and end at d_sae");
@@ -364,6 +389,7 @@ int saev_share_x(saev_ctx* c, saev_ctx* leader) {
     if (!c) return SAEV_INVALID_ARG;
     if (leader == nullptr || leader == c) { unlink_from_leader(c); return SAEV_OK; }
     REQUIRE(c, !c->btk && !leader->btk, SAEV_UNSUPPORTED, "saev_share_x: a BatchTopK context neither lends nor borrows");
+    REQUIRE(c, !c->relu_train && !leader->relu_train, SAEV_UNSUPPORTED, "saev_share_x: a ReLU training context neither lends nor borrows (its step derives nothing but max |x| from x alone)");
     REQUIRE(c, leader->device == c->device && leader->cfg.d_model == c->cfg.d_model && leader->cfg.encoder_mode == c->cfg.encoder_mode,
             SAEV_INVALID_ARG, "saev_share_x: both contexts must live on one device with the same d_model and encoder mode");
     REQUIRE(c, leader->leader == nullptr, SAEV_INVALID_ARG, "saev_share_x: the leader must build its own x-derived buffers");

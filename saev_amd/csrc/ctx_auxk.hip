@@ -78,15 +78,7 @@ int dense_f16x3(saev_ctx* c, const _Float16* xs, const _Float16* ws, const float
 // P (K x R), Q (K x C): the AuxK weight gradients.  Both are split into hi/lo fp16 images of their transposes
 // (split_wT), the contraction is cut into n_split slices that run as one batched launch of the encoder kernel (a single
 // slice would leave most CUs idle: R x C is only a few tiles), and the slices are added in a fixed order.
-// (slices and padded length of the batch-long contraction of an R x C weight gradient: the images of its operands are laid out for them)
-void ksplit_shape(int R, int C, int K, int* n_split_out, int* Kp_out) {
-    const int R256 = (R + 255) / 256 * 256, C256 = (C + 255) / 256 * 256;
-    const int tiles = (R256 / 256) * (C256 / 256);
-    int n_split = 1;
-    while (n_split < AUX_KSPLIT_MAX && tiles * n_split < 256) n_split *= 2;
-    *n_split_out = n_split;
-    *Kp_out = (K + 16 * n_split - 1) / (16 * n_split) * (16 * n_split);  // <= aux_kpad
-}
+// (ksplit_shape -- ctx.h -- gives the slices and the padded length, <= aux_kpad)
 // imgP / imgQ: the operand's k-major images if somebody has written them already (split_both_kernel, with THIS Kp), else NULL
 int ksplit_f16x3(saev_ctx* c, const float* P, const float* sP, int R, const float* Q, const float* sQ, int C, int K,
                  float* out, hipStream_t s, const _Float16* imgP = nullptr, const _Float16* imgQ = nullptr) {

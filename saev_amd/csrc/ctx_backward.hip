@@ -7,6 +7,7 @@ extern "C" {
 
 int saev_backward_begin(saev_ctx* c, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, !c->relu_train, SAEV_UNSUPPORTED, "saev_backward_begin: a ReLU training context runs its dense backward in one piece (saev_step_backward)");
     REQUIRE(c, c->x_last && c->training_last, SAEV_INVALID_ARG, "saev_backward_begin: no training forward in flight");
     REQUIRE(c, c->grads, SAEV_NOT_BOUND, "gradient buffer not bound");
     hipStream_t s = (hipStream_t)stream;
@@ -72,6 +73,7 @@ int saev_backward_rows(saev_ctx* c, int32_t lat_lo, int32_t lat_hi, void* stream
 
 int saev_backward_rows_part(saev_ctx* c, int32_t lat_lo, int32_t lat_hi, int32_t part, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, !c->relu_train, SAEV_UNSUPPORTED, "saev_backward_rows: a ReLU training context runs its dense backward in one piece, over all latents (saev_step_backward)");
     REQUIRE(c, part >= 0 && part <= 2, SAEV_INVALID_ARG, "saev_backward_rows_part: part must be 0 (both), 1 (decoder) or 2 (encoder)");
     REQUIRE(c, c->x_last && c->training_last && c->grads, SAEV_INVALID_ARG, "saev_backward_rows: call saev_backward_begin first");
     const int S = c->cfg.d_sae, D = c->cfg.d_model, K = c->cfg.top_k;
@@ -159,6 +161,7 @@ int saev_bind_w_enc_t(saev_ctx* c, float* scratch) {
 int saev_copy_step_state(saev_ctx* c, int32_t n_rows, float* g_out, int32_t* idx_out, float* val_out, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
     REQUIRE(c, !c->btk, SAEV_UNSUPPORTED, "saev_copy_step_state: not for a BatchTopK context (no sparse-state exchange)");
+    REQUIRE(c, !c->relu_train, SAEV_UNSUPPORTED, "saev_copy_step_state: not for a ReLU training context (its step state is dense: no sparse-state exchange)");
     REQUIRE(c, c->n_last > 0 && c->training_last && n_rows == c->n_last, SAEV_INVALID_ARG,
             "saev_copy_step_state: n_rows must be the row count of the training forward in flight");
     hipStream_t s = (hipStream_t)stream;
@@ -175,6 +178,7 @@ int saev_backward_override(saev_ctx* c, const float* x_all, const float* g_all, 
     if (!c) return SAEV_INVALID_ARG;
     if (x_all == nullptr) { c->ov_x = nullptr; c->ov_n = 0; return SAEV_OK; }
     REQUIRE(c, !c->btk, SAEV_UNSUPPORTED, "saev_backward_override: not for a BatchTopK context (a batch-wide top-k over ranks needs a distributed select)");
+    REQUIRE(c, !c->relu_train, SAEV_UNSUPPORTED, "saev_backward_override: not for a ReLU training context (one GPU: the dense backward runs over its own rows)");
     REQUIRE(c, g_all && idx_all && val_all && n_all > 0, SAEV_INVALID_ARG, "saev_backward_override: NULL buffer");
     REQUIRE(c, n_all <= c->back_rows, SAEV_INVALID_ARG,
             "saev_backward_override: the gathered row count exceeds saev_cfg.max_backward_rows (set it to the GLOBAL batch)");
@@ -221,6 +225,7 @@ int saev_trust_gradients(saev_ctx* c, int32_t on) {
 
 int saev_backward_end(saev_ctx* c, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, !c->relu_train, SAEV_UNSUPPORTED, "saev_backward_end: a ReLU training context runs its dense backward in one piece (saev_step_backward)");
     REQUIRE(c, c->grads, SAEV_NOT_BOUND, "gradient buffer not bound");
     // (the per-tile squares land behind the tail's other partial sums: [2 nb + ceil(S / 4), ...))
     double* sq = c->sumsq_partials + 2 * sumsq_blocks() + (c->cfg.d_sae + 3) / 4;
@@ -230,6 +235,7 @@ int saev_backward_end(saev_ctx* c, void* stream) {
 }
 
 int saev_step_backward(saev_ctx* c, void* stream) {
+    if (c && c->relu_train) return relu_train_backward(c, (hipStream_t)stream);
     int rc = saev_backward_begin(c, stream);
     if (rc != SAEV_OK) return rc;
     rc = saev_backward_rows(c, 0, c->cfg.d_sae, stream);

@@ -99,6 +99,7 @@ int saev_comm_destroy(saev_ctx* c) {
 
 int saev_train_step_dp(saev_ctx* c, const float* x_local, int32_t n_local, float lr, float max_norm, int64_t adam_step, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    REQUIRE(c, !c->relu_train, SAEV_UNSUPPORTED, "saev_train_step_dp: a ReLU training context runs on one GPU (its dense step has no data-parallel form: the loss terms and dH divide by the local row count)");
     REQUIRE(c, c->cfg.activation == SAEV_ACT_TOPK, SAEV_UNSUPPORTED, "saev_train_step_dp: a TopK context only (ReLU runs the forward entries, BatchTopK one GPU)");
     REQUIRE(c, c->comm != nullptr, SAEV_INVALID_ARG, "saev_train_step_dp: no communicator (saev_comm_init)");
     REQUIRE(c, c->grads != nullptr, SAEV_NOT_BOUND, "saev_train_step_dp: no gradient buffer bound");

@@ -406,8 +406,12 @@ int btk_codes(saev_ctx* c, const float* h, int n, int training, int32_t* row_nnz
     HIPCHK(c, launch_batch_topk(a, s));
     return SAEV_OK;
 }
+}  // namespace
+
+}  // extern "C"
+
 // h = x W_enc + b_enc into the context's dense buffer: the exact fp32 kernel in the f32 and f16r modes, the split-fp16 one in f16x3
-int btk_dense_h(saev_ctx* c, const float* x, int n, hipStream_t s) {
+int encode_dense_h(saev_ctx* c, const float* x, int n, hipStream_t s) {
     if (c->cfg.encoder_mode != SAEV_ENCODER_F16R) {
         int rc = prepare_encoder(c, x, n, nullptr, s);
         if (rc != SAEV_OK) return rc;
@@ -417,7 +421,8 @@ int btk_dense_h(saev_ctx* c, const float* x, int n, hipStream_t s) {
     }
     return run_encoder(c, x, n, EPI_DENSE, c->h_dense, nullptr, 0, s);
 }
-}  // namespace
+
+extern "C" {
 
 int saev_batch_topk_dense(saev_ctx* c, const float* h, int32_t n, int32_t training, int32_t* row_nnz_out, int32_t* idx_out,
                           float* val_out, int32_t* overflow_out, void* stream) {
@@ -440,7 +445,7 @@ int saev_encode_batch_topk(saev_ctx* c, const float* x, int32_t n, int32_t train
     hipStream_t s = (hipStream_t)stream;
     bind_x_sources(c, x, n, false);
     c->xprep_x = nullptr;
-    int rc = btk_dense_h(c, x, n, s);
+    int rc = encode_dense_h(c, x, n, s);
     if (rc != SAEV_OK) return rc;
     return btk_codes(c, c->h_dense, n, training, row_nnz_out, idx_out, val_out, overflow_out, s);
 }
@@ -522,6 +527,7 @@ int saev_gather_rows(saev_ctx* c, const float* pool, const int64_t* rows, int32_
 int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_global, int32_t training,
                       void* stream) {
     if (!c) return SAEV_INVALID_ARG;
+    if (c->relu_train) return relu_train_forward(c, x, n, n_rows_global, training, (hipStream_t)stream);
     REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU, SAEV_UNSUPPORTED, "saev_step_forward: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params, SAEV_NOT_BOUND, "parameters not bound");
     REQUIRE(c, x && n > 0 && n <= c->cfg.max_batch, SAEV_INVALID_ARG,
@@ -599,7 +605,7 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
     (void)n_rows_global;
     int rc;
     if (btk) {
-        rc = btk_dense_h(c, x, n, s);
+        rc = encode_dense_h(c, x, n, s);
         if (rc == SAEV_OK) rc = btk_codes(c, c->h_dense, n, training, c->row_nnz, c->idx, c->val, c->btk_over, s);
         if (rc == SAEV_OK) {
             // the step's one read-back: no row may be truncated, and nothing downstream can be sized on the device

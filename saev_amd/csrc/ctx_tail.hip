@@ -50,7 +50,7 @@ int saev_wdec_ready_event(saev_ctx* c, void* event) {
 
 int saev_tail_prepare(saev_ctx* c, int32_t shard_rank, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU, SAEV_UNSUPPORTED, "saev_tail_prepare: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU || c->relu_train, SAEV_UNSUPPORTED, "saev_tail_prepare: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params && c->grads, SAEV_NOT_BOUND, "saev_tail_prepare: params/grads not bound");
     TailRanges r;
     int rc = tail_ranges(c, shard_rank, &r);
@@ -102,7 +102,7 @@ int saev_tail_prepare(saev_ctx* c, int32_t shard_rank, void* stream) {
 int saev_tail_apply(saev_ctx* c, float lr, float max_norm, float grad_scale, int64_t adam_step, int32_t shard_rank,
                     void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU, SAEV_UNSUPPORTED, "saev_tail_apply: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU || c->relu_train, SAEV_UNSUPPORTED, "saev_tail_apply: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params && c->grads && c->adam_m && c->adam_v, SAEV_NOT_BOUND,
             "saev_tail_apply: params/grads/adam state not bound");
     REQUIRE(c, adam_step >= 1, SAEV_INVALID_ARG, "adam_step is 1-based");
@@ -191,6 +191,7 @@ int saev_train_step_gather(saev_ctx* c, const float* pool, const int64_t* rows, 
     if (!c) return SAEV_INVALID_ARG;
     REQUIRE(c, pool && rows && x_out, SAEV_INVALID_ARG, "saev_train_step_gather: NULL buffer");
     REQUIRE(c, !c->btk, SAEV_UNSUPPORTED, "saev_train_step_gather: not for a BatchTopK context (draw the batch first: saev_gather_rows)");
+    REQUIRE(c, !c->relu_train, SAEV_UNSUPPORTED, "saev_train_step_gather: not for a ReLU training context (draw the batch first: saev_gather_rows)");
     c->gather_pool = pool; c->gather_rows = rows;
     const int rc = saev_train_step(c, x_out, n, lr, max_norm, adam_step, stream);
     c->gather_pool = nullptr; c->gather_rows = nullptr;
@@ -214,7 +215,7 @@ double muon_dec(float f) {
 
 int saev_muon_tail(saev_ctx* c, float lr, float max_norm, float grad_scale, int64_t adam_step, const saev_muon_cfg* cfg, void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU, SAEV_UNSUPPORTED, "saev_muon_tail: a ReLU context runs the forward entries only");
+    REQUIRE(c, c->cfg.activation != SAEV_ACT_RELU || c->relu_train, SAEV_UNSUPPORTED, "saev_muon_tail: a ReLU context runs the forward entries only");
     REQUIRE(c, c->params && c->grads && c->adam_m && c->adam_v, SAEV_NOT_BOUND, "saev_muon_tail: params/grads/adam state not bound");
     REQUIRE(c, adam_step >= 1, SAEV_INVALID_ARG, "adam_step is 1-based");
     REQUIRE(c, !c->wenc_t_pending, SAEV_INVALID_ARG, "saev_muon_tail: runs after the phases, not inside saev_train_step");
@@ -275,7 +276,7 @@ int saev_muon_tail(saev_ctx* c, float lr, float max_norm, float grad_scale, int6
 int saev_train_step(saev_ctx* c, const float* x, int32_t n, float lr, float max_norm, int64_t adam_step,
                     void* stream) {
     if (!c) return SAEV_INVALID_ARG;
-    if (c->btk) {  // the four phases back to back: nothing of the fused tail applies
+    if (c->btk || c->relu_train) {  // the four phases back to back: nothing of the fused tail applies
         int rcb = saev_step_forward(c, x, n, n, 1, stream);
         if (rcb == SAEV_OK) rcb = saev_step_dead(c, n, stream);
         if (rcb == SAEV_OK) rcb = saev_step_backward(c, stream);

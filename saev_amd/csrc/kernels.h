@@ -700,6 +700,23 @@ hipError_t launch_relu_decode(const ReluDecodeArgs& a, hipStream_t stream);
 hipError_t launch_relu_scatter(const int32_t* idx, const float* val, const int32_t* row_nnz, int row_cap, int n_rows, int S,
                                float* f_out, hipStream_t stream);
 
+// ---- ReLU train step (relu_train.hip): the element-wise passes between the step's dense contractions ------------------------
+// Each leaves the maximum of what it wrote per workgroup in `part` and, by one small launch, the power-of-two operand scale
+// {2^e, 1} of the fp16 split that follows in `pair` (2^e max in [2^13, 2^14)).
+int relu_act_parts(int n_rows);          // floats of `part` launch_relu_act / launch_relu_mse write
+int relu_dact_row_blocks(int n_rows);    // row blocks of launch_relu_dact: colpart holds that many x S floats
+int relu_dact_parts(int n_rows, int S);  // floats of `part` launch_relu_dact writes
+// h (n_rows x S, 16-byte aligned, S % 4 == 0) -> f = max(h, 0) in place; rowstats[b].l0 / .l1 (count and sum of the row's positive
+// entries, formed in fp64); training: fired[s] = 1 where some row has f > 0
+hipError_t launch_relu_act(float* h, int n_rows, int S, int training, int32_t* fired, RowStats* rowstats, float* part, float* pair,
+                           hipStream_t stream);
+// rowstats[b].sse_scaled / .sse64 / .sumsq64 (.aux_sse = 0) and g = gscale (x_hat - x) with the rescale of objectives.py:224-237
+hipError_t launch_relu_mse(const float* x, const float* x_hat, int n_rows, int D, const float* upper, float gscale, float* g,
+                           RowStats* rowstats, float* part, float* pair, hipStream_t stream);
+// dA (n_rows x S) -> dH = (dA + l1c) where f > 0, else 0, in place; db_enc[s] = column sums of dH, added in row order
+hipError_t launch_relu_dact(float* dA, const float* f, int n_rows, int S, float l1c, float* colpart, float* db_enc, float* part,
+                            float* pair, hipStream_t stream);
+
 // ---- BatchTopK activation (batchtopk.hip) -----------------------------------------------------------------------------------
 constexpr int BTK_BINS = 4096;            // bins of a select level (12 key bits; the last level uses 256 of them)
 constexpr int BTK_LIST_CAP = 1 << 20;     // keys of the cut bin the second pass can list; more: the later levels re-read h
@@ -736,6 +753,8 @@ struct BtkCompactArgs {
     int32_t* idx_out; float* val_out; int32_t* row_nnz_out; int32_t* row_ties; int32_t* overflow;
 };
 hipError_t launch_batch_topk(const BtkArgs& a, hipStream_t stream);
+// the threshold compaction alone (a.training = 0: h > max(*a.threshold, 0) into rows of a.row_cap slots; a.st / a.row_ties unused)
+hipError_t launch_threshold_compact(const BtkCompactArgs& a, hipStream_t stream);
 
 // ---- Muon (muon.hip) ---------------------------------------------------------------------------------------------------
 // Rounding contract of the Newton-Schulz GEMMs: fp32 accumulation of bf16 products, the fp32 epilogue alpha * acc + beta * Cin,

@@ -72,6 +72,9 @@ class EngineConfig:
     aux_wide_route: int = dataclasses.field(default_factory=lambda: int(os.environ.get("SAEV_AMD_AUX_WIDE", "0")))
     # "topk" (default), or "relu": a forward-only context for a ReLU SAE (top_k is ignored, k_aux must be 0): encode_relu,
     # decode_rows, scatter_rows and the single ops run; the step entries raise NotImplementedError.
+    # "relu_train" (include/saev_amd.h: RELU TRAINING): a ReLU SAE that TRAINS -- a context kind of its own, whose dense step runs on
+    # the matrix cores: everything the "relu" engine runs, plus the phases, train_step (= the phases) and muon_tail with the
+    # plain objective (no Matryoshka prefixes), one GPU, no share_x; last_codes compacts the dense f into padded rows.
     # "batch_topk" (include/saev_amd.h: BATCHTOPK): top_k codes per row ON AVERAGE, chosen over the whole batch in training mode
     # and by the learned threshold in eval mode; codes are padded rows of row_cap slots.  The phases, train_step (= the phases),
     # muon_tail, encode_batch_topk and batch_topk_dense run; one GPU, no share_x, no deferred gather.
@@ -80,6 +83,7 @@ class EngineConfig:
                                  # meets a longer row rebuilds the context with the needed capacity (rounded up to 64) and repeats
     batch_momentum: float = 0.1  # batch_topk: EMA weight of the threshold update
     select_list_cap: int = 0     # batch_topk route switch for tests: capacity of the select's key list (0 = default; same results)
+    l1_coeff: float = 0.0        # relu_train: L1Sparsity.coeff (0 = NoSparsity)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -485,13 +489,19 @@ class SaeEngine:
             raise ValueError(f"EngineConfig.bounds (SAEV_AMD_BOUNDS) must be 'guaranteed' or 'predicted', got {cfg.bounds!r}")
         if cfg.encoder not in ("f32", "f16x3", "bf16", "f16r"):
             raise ValueError(f"EngineConfig.encoder (SAEV_AMD_ENCODER) must be one of f32, f16x3, bf16, f16r, got {cfg.encoder!r}")
-        if cfg.activation not in ("topk", "relu", "batch_topk"):
-            raise ValueError(f"EngineConfig.activation must be 'topk', 'relu' or 'batch_topk', got {cfg.activation!r}")
+        if cfg.activation not in ("topk", "relu", "batch_topk", "relu_train"):
+            raise ValueError(f"EngineConfig.activation must be 'topk', 'relu', 'batch_topk' or 'relu_train', got {cfg.activation!r}")
+        if cfg.activation == "relu_train" and cfg.encoder == "bf16":
+            raise NotImplementedError("the bf16 encoder is not available for ReLU SAEs: use f32, f16x3 or f16r")
+        if cfg.activation == "relu_train" and (cfg.shard_world > 1 or cfg.max_backward_rows > cfg.max_batch):
+            raise NotImplementedError("a ReLU training engine runs on one GPU (world > 1 is not on this path)")
+        if cfg.activation == "relu_train" and not (cfg.l1_coeff >= 0.0 and math.isfinite(cfg.l1_coeff)):
+            raise ValueError(f"EngineConfig.l1_coeff must be a finite number >= 0, got {cfg.l1_coeff!r}")
         if cfg.activation == "batch_topk" and cfg.encoder == "bf16":
             raise NotImplementedError("the bf16 encoder is not available for BatchTopK SAEs: use f32, f16x3 or f16r")
         if cfg.activation == "batch_topk" and (cfg.shard_world > 1 or cfg.max_backward_rows > cfg.max_batch):
             raise NotImplementedError("a BatchTopK engine runs on one GPU (a batch-wide top-k over ranks needs a distributed select)")
-        if cfg.activation == "relu" and cfg.k_aux != 0:
+        if cfg.activation in ("relu", "relu_train") and cfg.k_aux != 0:
             raise ValueError("a ReLU engine has no auxiliary loss: k_aux must be 0")
         with torch.cuda.device(self.device):
             self.params = torch.zeros(self.n_params, device=self.device, dtype=torch.float32)
@@ -533,7 +543,7 @@ class SaeEngine:
             max_batch=cfg.max_batch, encoder_mode={"f32": 0, "f16x3": 1, "bf16": 2, "f16r": 3}[cfg.encoder],
             aux_dead_cap=cfg.aux_dead_cap, shard_world=cfg.shard_world,
             bound_mode={"guaranteed": 0, "predicted": 1}[cfg.bounds], max_backward_rows=cfg.max_backward_rows,
-            activation={"topk": _lib.ACT_TOPK, "relu": _lib.ACT_RELU, "batch_topk": _lib.ACT_BATCHTOPK}[cfg.activation],
+            activation={"topk": _lib.ACT_TOPK, "relu": _lib.ACT_RELU, "batch_topk": _lib.ACT_BATCHTOPK, "relu_train": _lib.ACT_RELU}[cfg.activation],
         )
         dbg = _lib.SaevDebugCfg(
             struct_size=C.sizeof(_lib.SaevDebugCfg), dw_route={"slices": 0, "rows": 1, "slices_a": 2}[cfg.dw_route],
@@ -545,6 +555,9 @@ class SaeEngine:
             bt = _lib.SaevBatchTopKCfg(struct_size=C.sizeof(_lib.SaevBatchTopKCfg), row_cap=cfg.row_cap, batch_momentum=cfg.batch_momentum,
                                        list_cap=cfg.select_list_cap)
             rc = self.lib.saev_create_batch_topk(C.byref(ccfg), C.byref(dbg), C.byref(bt), self.device.index, C.byref(ctx))
+        elif cfg.activation == "relu_train":
+            rt = _lib.SaevReluTrainCfg(struct_size=C.sizeof(_lib.SaevReluTrainCfg), l1_coeff=float(cfg.l1_coeff))
+            rc = self.lib.saev_create_relu_train(C.byref(ccfg), C.byref(dbg), C.byref(rt), self.device.index, C.byref(ctx))
         else:
             rc = self.lib.saev_create_ex(C.byref(ccfg), C.byref(dbg), self.device.index, C.byref(ctx))
         if rc != 0:
@@ -583,12 +596,15 @@ class SaeEngine:
     def _topk_only(self, what: str):
         if self.cfg.activation == "batch_topk":
             raise NotImplementedError(f"{what} is not available for a BatchTopK SAE (one GPU, the phases or train_step, encode_batch_topk)")
+        if self.cfg.activation == "relu_train":
+            raise NotImplementedError(f"{what} is not available for a ReLU training engine (one GPU, the phases in one piece or train_step, "
+                                      "encode_relu)")
         if self.cfg.activation != "topk":
             raise NotImplementedError(f"{what}: training and the TopK forward are not on the HIP path for a {self.cfg.activation} SAE "
                                       "(only its forward is: encode_relu / decode_rows)")
 
     def _trains(self, what: str):
-        """TopK and BatchTopK engines run the step entries; a ReLU engine its forward only."""
+        """TopK, BatchTopK and ReLU training engines run the step entries; a ReLU engine its forward only."""
         if self.cfg.activation == "relu":
             self._topk_only(what)
 
@@ -626,6 +642,8 @@ class SaeEngine:
 
     def set_prefixes(self, prefixes) -> None:
         """Matryoshka cut points for the following steps (ascending, last == d_sae); None / one entry = plain."""
+        if self.cfg.activation == "relu_train" and prefixes is not None and len(list(prefixes)) > 1:
+            raise NotImplementedError("set_prefixes: the dense ReLU step implements the plain objective only (n_prefixes = 1)")
         if prefixes is None:
             self._n_prefixes = 1
             self._prefixes = None
@@ -642,6 +660,8 @@ class SaeEngine:
         just run its forward on the same batch tensor: several SAEs on the same batches (train()'s parallel groups)."""
         if leader is not None and "batch_topk" in (self.cfg.activation, leader.cfg.activation):
             raise NotImplementedError("share_x: a BatchTopK engine neither lends nor borrows what a step derives from x")
+        if leader is not None and "relu_train" in (self.cfg.activation, leader.cfg.activation):
+            raise NotImplementedError("share_x: a ReLU training engine neither lends nor borrows what a step derives from x")
         self._leader = leader  # keeps it alive for as long as the link exists
         self._chk(self.lib.saev_share_x(self.ctx, leader.ctx if leader is not None else None), "saev_share_x")
 
@@ -751,8 +771,8 @@ class SaeEngine:
         row_nnz[b] slots in ascending latent order (slots past it are unspecified).  ``cap`` starts at ``row_cap`` (default: the
         engine's ``relu_row_cap``); when a row has more positives the call reads the largest count back and runs the encoder
         once more with that capacity, so no row is truncated.  Without ``row_cap`` the engine's capacity then grows to it."""
-        if self.cfg.activation != "relu":
-            raise _lib.SaevError("encode_relu needs an engine created with activation='relu'")
+        if self.cfg.activation not in ("relu", "relu_train"):
+            raise _lib.SaevError("encode_relu needs an engine created with activation='relu' (or 'relu_train')")
         if self.cfg.encoder == "bf16":
             raise NotImplementedError("the bf16 encoder is not available for ReLU SAEs: use f32, f16x3 or f16r")
         x = self._check_x(x)
@@ -855,6 +875,8 @@ class SaeEngine:
         self._x_keepalive = x
         self._note_param_writes()
         n = x.shape[0]
+        if self.cfg.activation == "relu_train" and (n_rows_global or n) != n:
+            raise NotImplementedError("step_forward: a ReLU training engine runs on one GPU (n_rows_global must equal the batch)")
         rc = self.lib.saev_step_forward(self.ctx, _ptr(x), n, n_rows_global or n, int(training), _stream())
         if rc == _lib.ROW_OVERFLOW:
             # BatchTopK: nothing was decoded and the threshold has not moved; larger rows, then the same forward again
@@ -887,9 +909,13 @@ class SaeEngine:
     def backward_rows(self, lo: int, hi: int, part: int = 0):
         """Gradient rows of the latents [lo, hi).  part 0: both matrices in one pass; 1: the decoder's only (after it the
         decoder half of the gradient -- W_dec and b_dec -- is final); 2: the encoder's (needs part 1 first)."""
+        if self.cfg.activation == "relu_train":
+            self._topk_only("backward_rows")
         self._chk(self.lib.saev_backward_rows_part(self.ctx, lo, hi, part, _stream()), "saev_backward_rows_part")
 
     def backward_end(self):
+        if self.cfg.activation == "relu_train":
+            self._topk_only("backward_end")
         self._chk(self.lib.saev_backward_end(self.ctx, _stream()), "saev_backward_end")
 
     def step_tail(self, lr: float, max_norm: float = 1.0, grad_scale: float = 1.0, *, trusted: bool = False):
@@ -939,10 +965,14 @@ class SaeEngine:
 
     def copy_step_state(self, n_rows: int, g_out: torch.Tensor, idx_out: torch.Tensor, val_out: torch.Tensor):
         """This rank's rows of dL/dx_hat and of the codes of the training forward in flight, into caller tensors."""
+        if self.cfg.activation == "relu_train":
+            self._topk_only("copy_step_state")
         self._chk(self.lib.saev_copy_step_state(self.ctx, n_rows, _ptr(g_out), _ptr(idx_out), _ptr(val_out), _stream()), "saev_copy_step_state")
 
     def backward_begin_gathered(self, x_all: torch.Tensor, g_all: torch.Tensor, idx_all: torch.Tensor, val_all: torch.Tensor):
         """``backward_begin`` over the rows of ALL ranks (rank-major); the following ``backward_rows`` cover them too."""
+        if self.cfg.activation == "relu_train":
+            self._topk_only("backward_begin_gathered")
         assert x_all.is_contiguous() and g_all.is_contiguous() and idx_all.is_contiguous() and val_all.is_contiguous()
         self._gather_keepalive = (x_all, g_all, idx_all, val_all)
         self._chk(self.lib.saev_backward_override(self.ctx, _ptr(x_all), _ptr(g_all), _ptr(idx_all), _ptr(val_all), x_all.shape[0]),
@@ -995,7 +1025,9 @@ class SaeEngine:
 
         ``grad_views()`` is NOT a valid gradient afterwards: the W_enc gradient stays in the transposed scratch and the
         dW_dec rows are stored un-projected (the fused Adam projects them as it reads).  To look at gradients run the phases
-        (``step_forward`` / ``step_dead`` / ``step_backward`` / ``step_tail``), as the log steps of ``train()`` do."""
+        (``step_forward`` / ``step_dead`` / ``step_backward`` / ``step_tail``), as the log steps of ``train()`` do.
+        (BatchTopK and ReLU training engines run the four phases back to back here: their ``grad_views()`` IS the step's
+        gradient afterwards, projected by the tail.)"""
         self._trains("train_step")
         x = self._check_x(x)
         self._x_keepalive = x
@@ -1065,6 +1097,8 @@ class SaeEngine:
         context's own codes and reconstruction (saev_last_idx / _val / _x_hat): no copy of either is made.  ``x_hat=False``
         leaves the reconstruction unread (the residual sums then add 0); ``scalars=False`` leaves the scalar sums out."""
         self._trains("add_batch_stats")  # (BatchTopK rows are padded with idx = -1, which the kernel ignores: no row_nnz needed)
+        if self.cfg.activation == "relu_train":
+            raise NotImplementedError("add_batch_stats: a ReLU training engine keeps no padded rows (compact them with last_codes and call BatchStats.add)")
         x = self._check_x(x)
         if self._last_n == 0 or x.shape[0] != self._last_n:
             raise _lib.SaevError(f"add_batch_stats: x has {x.shape[0]} rows, the last step_forward had {self._last_n or 'none'}")
@@ -1078,6 +1112,8 @@ class SaeEngine:
         """Feed the codes of the last ``step_forward`` to ``acc`` straight from the context (saev_last_idx / _val): no copy is
         made.  TopK rows are full; BatchTopK rows are padded with idx = -1, which the kernel ignores."""
         self._trains("add_latent_topk")
+        if self.cfg.activation == "relu_train":
+            raise NotImplementedError("add_latent_topk: a ReLU training engine keeps no padded rows (compact them with last_codes and call LatentTopK.add)")
         if self._last_n == 0:
             raise _lib.SaevError("add_latent_topk: no step_forward to take codes from")
         if acc.d_sae != self.cfg.d_sae or acc.device != self.device:
@@ -1092,7 +1128,11 @@ class SaeEngine:
 
     def last_codes(self, n_rows: int, *, x_hat: bool = True, row_nnz: bool = False):
         """Copies of the last forward's codes and (unless ``x_hat=False``: None then) reconstruction.  A BatchTopK engine's codes
-        are its padded rows (n_rows, row_cap); ``row_nnz=True`` appends their counts: ``(idx, val, x_hat, row_nnz)``."""
+        are its padded rows (n_rows, row_cap); ``row_nnz=True`` appends their counts: ``(idx, val, x_hat, row_nnz)``.  A ReLU
+        training engine's codes are compacted from the dense f of its last forward (saev_copy_last_rows) into rows of the capacity
+        ``encode_relu`` keeps, which grows to the longest row met (one read-back, a second launch when a row did not fit)."""
+        if self.cfg.activation == "relu_train":
+            return self._relu_last_rows(n_rows, x_hat, row_nnz)
         k = self._code_width()
         idx = torch.empty(n_rows, k, device=self.device, dtype=torch.int32)
         val = torch.empty(n_rows, k, device=self.device, dtype=torch.float32)
@@ -1103,6 +1143,30 @@ class SaeEngine:
         nnz = torch.empty(n_rows, device=self.device, dtype=torch.int32)
         self._chk(self.lib.saev_copy_last_row_nnz(self.ctx, n_rows, _ptr(nnz), _stream()), "saev_copy_last_row_nnz")
         return idx, val, x_hat, nnz
+
+    def _relu_last_rows(self, n_rows: int, x_hat: bool, row_nnz: bool):
+        S = self.cfg.d_sae
+        cap = max(1, min(S, self.relu_row_cap))
+        over = torch.empty(1, device=self.device, dtype=torch.int32)
+        nnz = torch.empty(n_rows, device=self.device, dtype=torch.int32)
+        for attempt in range(2):
+            idx = torch.empty(n_rows, cap, device=self.device, dtype=torch.int32)
+            val = torch.empty(n_rows, cap, device=self.device, dtype=torch.float32)
+            self._chk(self.lib.saev_copy_last_rows(self.ctx, n_rows, cap, _ptr(nnz), _ptr(idx), _ptr(val), _ptr(over), _stream()),
+                      "saev_copy_last_rows")
+            need = int(over.item())  # the call's one read-back: 0, or the largest row count when a row overflowed
+            if need == 0:
+                break
+            if attempt == 1:
+                raise _lib.SaevError(f"saev_copy_last_rows overflowed a capacity of {cap} sized from its own count {need}")
+            cap = need
+            self.relu_second_launches += 1
+            self.relu_row_cap = max(self.relu_row_cap, min(S, (need + 63) // 64 * 64))
+        xh = None
+        if x_hat:
+            xh = torch.empty(n_rows, self.cfg.d_model, device=self.device, dtype=torch.float32)
+            self._chk(self.lib.saev_copy_last(self.ctx, n_rows, None, None, _ptr(xh), _stream()), "saev_copy_last")
+        return (idx, val, xh, nnz) if row_nnz else (idx, val, xh)
 
     def aux_route(self) -> int:
         """What the last step_dead did for the auxiliary loss: 0 nothing, 1 few-dead-latents kernels without reading

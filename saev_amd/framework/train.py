@@ -184,17 +184,28 @@ def _make_loader(cfg_data, device, rank, world, pool=None):
     return saev_data.ShuffledDataLoader(cfg_data, device=device, rank=rank, world_size=world, pool=pool)
 
 
-def _require_topk(cfgs: list[Config], what: str) -> None:
-    """TopK and BatchTopK SAEs train on the HIP path; a ReLU SAE runs its forward (nn.modeling, framework.inference) only."""
+def _require_trainable(cfgs: list[Config], what: str) -> None:
+    """TopK and BatchTopK SAEs train on the HIP path with any objective; a Relu SAE with the plain objective (n_prefixes = 1) and
+    no auxiliary loss (objectives.require_supported)."""
     for c in cfgs:
-        act = c.sae.activation
-        if not isinstance(act, (modeling.TopK, modeling.BatchTopK)):
-            raise NotImplementedError(f"{what}: {type(act).__name__} SAEs are not trained on the HIP path (TopK and BatchTopK only; a "
-                                      "Relu SAE's forward runs through nn.SparseAutoencoder and framework.inference)")
+        try:
+            objectives.require_supported(c.sae, c.objective)
+        except NotImplementedError as err:
+            raise NotImplementedError(f"{what}: {err}") from None
 
 
 def _is_batch_topk(cfg: Config) -> bool:
     return isinstance(cfg.sae.activation, modeling.BatchTopK)
+
+
+def _is_relu(cfg: Config) -> bool:
+    return isinstance(cfg.sae.activation, modeling.Relu)
+
+
+def _own_x(cfg: Config) -> bool:
+    """BatchTopK and ReLU engines work from their own dense pre-activations: they neither lend nor borrow what a step derives
+    from x (share_x), and their steps do not draw the batch themselves (no deferred gather)."""
+    return _is_batch_topk(cfg) or _is_relu(cfg)
 
 
 def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=None) -> tuple[torch.nn.ModuleList, torch.nn.ModuleList, RunLog, int]:
@@ -202,7 +213,9 @@ def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=No
 
     ``train_pool`` optionally supplies an in-memory (n, d_model) activation pool instead of a shard dir; ``train_feed`` a
     ready loader-shaped object (e.g. data.ExtractionFeed: activations straight out of a transformer's forward hooks)."""
-    _require_topk(cfgs, "train")
+    _require_trainable(cfgs, "train")
+    if any(_is_relu(c) for c in cfgs) and _dist()[2] > 1:
+        raise NotImplementedError("Relu SAEs train on one GPU: world > 1 is not on the HIP path for the dense ReLU step (DESIGN.md 3.15)")
     if any(_is_batch_topk(c) for c in cfgs) and _dist()[2] > 1:
         raise NotImplementedError("BatchTopK SAEs train on one GPU: a batch-wide top-k over the shards of several ranks needs a "
                                   "distributed select (DESIGN.md 3.13)")
@@ -257,9 +270,9 @@ def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=No
         if world > 1:  # identical replicas: rank 0's initial parameters everywhere
             dist.broadcast(eng.params, src=0)
         # one batch feeds every SAE of the group (train.py:334-348): the first TopK engine's x statistics, centring and operand
-        # images serve the other TopK members (a BatchTopK engine works from its own dense pre-activations: nothing to share)
-        lender = next((s.engine for s, sc in zip(steppers, cfgs) if not _is_batch_topk(sc)), None)
-        if lender is not None and not _is_batch_topk(c):
+        # images serve the other TopK members (a BatchTopK or ReLU engine works from its own dense pre-activations: nothing to share)
+        lender = next((s.engine for s, sc in zip(steppers, cfgs) if not _own_x(sc)), None)
+        if lender is not None and not _own_x(c):
             eng.share_x(lender)
         steppers.append(DataParallelStepper(eng, dist, world, tail=tail_mode, exchange=exchange, muon=mu))
         scheds.append(scheduling.WarmupCosine(0.0, c.n_lr_warmup, c.lr, len(limiter), 0.0))
@@ -267,7 +280,7 @@ def train(cfgs: list[Config], *, train_pool: Tensor | None = None, train_feed=No
     dataloader.engine = steppers[0].engine
     # One rank, a resident pool: the loader hands over (pool, row indices) and the first SAE's step draws the batch in its own
     # first kernel (SaeEngine.train_step_gather) -- no gather pass, and for a single SAE the streamed preparation of the step.
-    if world == 1 and hasattr(dataloader, "defer_gather") and muons[0] is None and not _is_batch_topk(cfgs[0]):
+    if world == 1 and hasattr(dataloader, "defer_gather") and muons[0] is None and not _own_x(cfgs[0]):
         dataloader.defer_gather = True
 
     global_step, n_patches_seen = 0, 0
@@ -356,7 +369,7 @@ def _log_metrics(sae, eng, x: Tensor, lr: float, n_patches_seen: int, cfg: Confi
     if acc is None:
         acc = eng._log_acc = BatchStats(D, sae.cfg.d_sae, x.device, want=("scalars", "col_sum", "live"), live_eps=1e-12)
     acc.zero_()
-    eng.add_batch_stats(acc, x)
+    _add_step_stats(eng, acc, x)
     own = [st.sse, st.sum_sq, st.mse * n, st.aux * n, st.l0 * n, st.l1 * n, float(n)]
     if dist is not None:  # the step's own scalars ride in the accumulator's caller slots: one SUM, one MAX
         acc.extra[:7].copy_(torch.tensor(own, dtype=torch.float64))
@@ -371,9 +384,12 @@ def _log_metrics(sae, eng, x: Tensor, lr: float, n_patches_seen: int, cfg: Confi
     m = n_all * D
     explained = 1 - ((h.sum_rr - h.sum_r * h.sum_r / m) / (m - 1)) / ((h.sum_xx - h.sum_x * h.sum_x / m) / (m - 1))
     mse, aux = mse_n / n_all, aux_n / n_all
+    sp = sae.cfg.activation.sparsity
+    # (sparsity = coeff * l1 as the reference forms it, modeling.py:42-43: fp32 l1 times a Python float; only a Relu SAE has one here)
+    sparsity = (torch.tensor(l1_n / n_all, dtype=torch.float32) * sp.coeff).item() if isinstance(sp, modeling.L1Sparsity) else 0.0
     fill = dataloader.reservoir.fill() if getattr(dataloader, "reservoir", None) is not None else 1.0
     return {
-        "loss/loss": mse + aux, "loss/mse": mse, "loss/l0": l0_n / n_all, "loss/l1": l1_n / n_all, "loss/sparsity": 0.0,
+        "loss/loss": mse + sparsity + aux, "loss/mse": mse, "loss/l0": l0_n / n_all, "loss/l1": l1_n / n_all, "loss/sparsity": sparsity,
         "loss/aux": aux, "loss/n_dead": st.n_dead,
         "progress/n_patches_seen": n_patches_seen, "progress/learning_rate": lr,
         "metrics/explained_variance": explained,
@@ -384,6 +400,16 @@ def _log_metrics(sae, eng, x: Tensor, lr: float, n_patches_seen: int, cfg: Confi
         "loader/buffer_fill": fill,
         **pre,
     }
+
+
+def _add_step_stats(eng, acc: BatchStats, x: Tensor, *, x_hat: bool = True) -> None:
+    """The last forward's batch into ``acc``: straight from the context's codes and reconstruction -- or, for a ReLU training
+    engine, whose step keeps a dense f, from the padded rows ``last_codes`` compacts (saev_copy_last_rows)."""
+    if eng.cfg.activation == "relu_train":
+        idx, val, xh, row_nnz = eng.last_codes(x.shape[0], x_hat=x_hat, row_nnz=True)
+        acc.add(x, xh, idx, val, row_nnz)
+    else:
+        eng.add_batch_stats(acc, x, x_hat=x_hat)
 
 
 def _coherence(W: Tensor) -> float:
@@ -427,7 +453,7 @@ def evaluate(cfgs: list[Config], saes: torch.nn.ModuleList, objs: torch.nn.Modul
              val_pool: Tensor | None = None) -> list[EvalMetrics]:
     """Eval-mode pass over the validation feed (train.py:510-618): fp64 baseline sums, SAE SSE, per-latent
     firing counts (f > 0) and value sums, dead / almost-dead (<1e-7) / dense (>1e-2) counts."""
-    _require_topk(cfgs, "evaluate")
+    _require_trainable(cfgs, "evaluate")
     if len(split_cfgs(cfgs)) != 1:
         raise ValueError(f"Configs are not parallelizeable: {cfgs}.")
     saes.eval()
@@ -456,7 +482,7 @@ def evaluate(cfgs: list[Config], saes: torch.nn.ModuleList, objs: torch.nn.Modul
             st = eng.read_stats()
             if i == 0:
                 sum_sq += st.sum_sq
-            eng.add_batch_stats(stats[i], x, x_hat=False)
+            _add_step_stats(eng, stats[i], x, x_hat=False)
             acc[i] += torch.tensor([st.l0 * b, st.l1 * b, st.mse * b, st.sse], dtype=torch.float64)
     if dist is not None:
         host = torch.cat([acc.reshape(-1), sum_sq.reshape(1), torch.tensor([float(n_tokens)], dtype=torch.float64)]).to(device)

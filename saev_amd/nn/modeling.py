@@ -14,7 +14,8 @@ What differs: every compute method runs hand-written HIP kernels through libsaev
 module's parameters, which are views into one flat device buffer owned by ``saev_amd.engine.SaeEngine``.
 There is no CPU implementation: calling a compute method on CPU tensors raises.  TopK and BatchTopK SAEs
 train and run on the accelerated path (BASELINE.json north_star; BatchTopK on one GPU, DESIGN.md 3.13);
-``Relu`` SAEs run their forward (``encode / decode / forward``, the inference pass) but do not train.
+``Relu`` SAEs run their forward (``encode / decode / forward``, the inference pass) and train with the plain objective
+(``Matryoshka(n_prefixes=1)``, L1 or no sparsity penalty, no AuxK) on a dense step of their own.
 A BatchTopK module carries the reference's ``activation.threshold`` buffer, so its ``sae.pt`` files move
 between the two code bases in both directions.
 """
@@ -266,8 +267,22 @@ class SparseAutoencoder(torch.nn.Module):
     # ---- engine binding ---------------------------------------------------------------------
     def _engine_cfg(self, max_batch: int, objective_cfg=None) -> EngineConfig:
         act = self.cfg.activation
+        if isinstance(act, Relu) and self.__dict__.get("_relu_trains", False):
+            # an objective has bound the module: the training context (a kind of its own), with the L1 coefficient of act.sparsity
+            if isinstance(act.aux, AuxK):
+                raise NotImplementedError("Relu(aux=AuxK(...)) does not train on the HIP path: the dense ReLU step has no auxiliary loss "
+                                          "(use aux=NoAux())")
+            if getattr(self, "_shard_world", 1) > 1 or getattr(self, "_max_backward_rows", 0) > 0:
+                raise NotImplementedError("a Relu SAE trains on one GPU (world > 1 is not on the HIP path)")
+            return EngineConfig(
+                d_model=self.cfg.d_model, d_sae=self.cfg.d_sae, k_aux=0, alpha=0.0,
+                dead_threshold_tokens=getattr(self, "_dead_threshold_tokens", 10_000_000), normalize_w_dec=self.cfg.normalize_w_dec,
+                remove_parallel_grads=self.cfg.remove_parallel_grads, max_batch=max_batch, activation="relu_train",
+                l1_coeff=float(act.sparsity.coeff) if isinstance(act.sparsity, L1Sparsity) else 0.0,
+            )
         if isinstance(act, Relu):
-            # forward only; the L1 coefficient of act.sparsity plays no part in it.  The engine's step entries raise.
+            # forward only (until an objective binds the module); the L1 coefficient of act.sparsity plays no part in it.  The
+            # engine's step entries raise.
             return EngineConfig(
                 d_model=self.cfg.d_model, d_sae=self.cfg.d_sae, k_aux=0, alpha=0.0,
                 dead_threshold_tokens=getattr(self, "_dead_threshold_tokens", 10_000_000), normalize_w_dec=self.cfg.normalize_w_dec,
@@ -311,6 +326,7 @@ class SparseAutoencoder(torch.nn.Module):
             or eng.cfg.dead_threshold_tokens != getattr(self, "_dead_threshold_tokens", eng.cfg.dead_threshold_tokens)
             or eng.cfg.shard_world != getattr(self, "_shard_world", eng.cfg.shard_world)
             or max(eng.cfg.max_batch, eng.cfg.max_backward_rows) < getattr(self, "_max_backward_rows", 0)
+            or (eng.cfg.activation == "relu" and self.__dict__.get("_relu_trains", False))  # (an objective has bound the module since)
             or any(getattr(self, n).data_ptr() != eng.view(n).data_ptr() for n in eng.offsets)
         )
         if stale:
@@ -321,6 +337,8 @@ class SparseAutoencoder(torch.nn.Module):
                 ecfg = dataclasses.replace(ecfg, row_cap=max(ecfg.row_cap, old.row_cap))
             eng = SaeEngine(ecfg, dev)
             eng.load_params(values)
+            if old is not None:
+                eng.relu_row_cap = max(eng.relu_row_cap, old.relu_row_cap)
             if old is not None and old.device == dev:
                 eng.set_tracker(old.toks_since_active)
                 # per tensor: the padded layout of a sharded tail (shard_world > 1) has other offsets and another length
@@ -553,7 +571,7 @@ def load(fpath: pathlib.Path | str, *, device="cpu") -> SparseAutoencoder:
     """Read an ``sae.pt``: schema 5 (what ``dump`` here and the reference's ``nn.dump`` write, modeling.py:548-574) and every
     older layout the reference's loader still reads (modeling.py:586-645; table above ``_config_fields``).  TopK and
     BatchTopK checkpoints train on the HIP path (a BatchTopK one brings its ``activation.threshold``), ReLU ones run their
-    forward."""
+    forward and train with the plain objective."""
     with open(fpath, "rb") as fd:
         first_line = fd.readline()
         payload = io.BytesIO(fd.read())

@@ -1,8 +1,9 @@
 """saev.nn.objectives' public surface (reference: src/saev/nn/objectives.py) over the HIP engine.
 
 ``get_objective(Matryoshka(...))`` returns a module whose ``forward(sae, x)`` gives
-``(MatryoshkaLoss, Output)`` like the reference (objectives.py:92-156): encode + TopK / BatchTopK, dead-latent
-tracking, decode, MSE with the max|x| rescale (objectives.py:223-237), AuxK (modeling.py:75-103).
+``(MatryoshkaLoss, Output)`` like the reference (objectives.py:92-156): encode + TopK / BatchTopK / ReLU, dead-latent
+tracking, decode, MSE with the max|x| rescale (objectives.py:223-237), AuxK (modeling.py:75-103), the L1 penalty of a ReLU SAE
+(modeling.py:36-43; plain objective only).
 All of it runs in libsaev_amd.so; ``loss.loss.backward()`` runs the HIP sparse backward and leaves the
 four parameter gradients in ``param.grad`` (views of the engine's flat gradient buffer).
 
@@ -118,6 +119,9 @@ class MatryoshkaObjective(Objective):
 
     def _bind(self, sae: modeling.SparseAutoencoder, n_rows: int):
         sae.__dict__["_dead_threshold_tokens"] = self.cfg.dead_threshold_tokens
+        if isinstance(sae.cfg.activation, modeling.Relu):
+            require_supported(sae.cfg, self.cfg)
+            sae.__dict__["_relu_trains"] = True  # (from here on the module builds the training engine: modeling._engine_cfg)
         eng = sae._eng(n_rows)
         if self.__dict__["_eng_ref"] is not eng:
             self.__dict__["_eng_ref"] = eng
@@ -142,21 +146,44 @@ class MatryoshkaObjective(Objective):
         st = eng.read_stats()
         dev = eng.device
         t = lambda v: torch.tensor(v, device=dev, dtype=torch.float32)  # noqa: E731
-        total = t(st.mse + st.aux)
+        sparsity = torch.tensor(0.0)
+        sp_cfg = sae.cfg.activation.sparsity
+        if isinstance(sae.cfg.activation, modeling.Relu) and isinstance(sp_cfg, modeling.L1Sparsity):
+            sparsity = t(st.l1) * sp_cfg.coeff  # (an fp32 tensor times a Python float, as modeling.py:42-43 forms it)
+            total = t(st.mse) + sparsity + t(st.aux)
+        else:
+            total = t(st.mse + st.aux)
         if self.training and torch.is_grad_enabled():
             total = _HipStep.apply(total, eng, sae.W_dec, sae.b_dec, sae.W_enc, sae.b_enc)
         loss = MatryoshkaLoss(
-            mse=t(st.mse), sparsity=torch.tensor(0.0), l0=t(st.l0), l1=t(st.l1), aux=t(st.aux),
+            mse=t(st.mse), sparsity=sparsity, l0=t(st.l0), l1=t(st.l1), aux=t(st.aux),
             n_dead=torch.tensor(st.n_dead, device=dev) if self.training else torch.tensor(0), total=total,
         )
-        if isinstance(sae.cfg.activation, modeling.BatchTopK):
-            # padded rows (the batch-wide select in training, the threshold in eval: saev_step_forward's `training` picks it)
+        if isinstance(sae.cfg.activation, (modeling.BatchTopK, modeling.Relu)):
+            # padded rows (BatchTopK: the batch-wide select in training, the threshold in eval: saev_step_forward's `training` picks
+            # it; ReLU: compacted from the step's dense f)
             idx, val, x_hat, row_nnz = eng.last_codes(n, row_nnz=True)
         else:
             (idx, val, x_hat), row_nnz = eng.last_codes(n), None
         if self.cfg.n_prefixes > 1:
             return loss, modeling.Output(sae, x, idx, val, None, prefixes=prefixes, row_nnz=row_nnz)
         return loss, modeling.Output(sae, x, idx, val, x_hat[:, None, :], row_nnz=row_nnz)
+
+
+def require_supported(sae_cfg: modeling.SparseAutoencoderConfig, objective_cfg: Matryoshka) -> None:
+    """What the HIP path does not train, refused before anything else runs (train() / evaluate() call this first).  TopK and
+    BatchTopK SAEs train with any number of prefixes; a Relu SAE trains on the dense step, which implements the
+    plain objective only and has no auxiliary loss."""
+    act = sae_cfg.activation
+    if not isinstance(act, (modeling.TopK, modeling.BatchTopK, modeling.Relu)):
+        raise NotImplementedError(f"{type(act).__name__} activation is not on the HIP path (TopK, BatchTopK and Relu are)")
+    if isinstance(act, modeling.Relu):
+        if objective_cfg.n_prefixes > 1:
+            raise NotImplementedError(f"a Relu SAE trains with the plain objective only: n_prefixes = {objective_cfg.n_prefixes} needs "
+                                      "Matryoshka(n_prefixes=1) (nested prefixes over the dense ReLU step are not on the HIP path)")
+        if isinstance(act.aux, modeling.AuxK):
+            raise NotImplementedError("Relu(aux=AuxK(...)) does not train on the HIP path: the dense ReLU step has no auxiliary loss "
+                                      "(use aux=NoAux())")
 
 
 @functools.lru_cache(maxsize=8)
