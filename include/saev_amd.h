@@ -556,6 +556,37 @@ int saev_muon_newton_schulz(const void* x_in, int64_t rows, int64_t cols, void* 
 int64_t saev_coherence_workspace_bytes(int64_t S, int64_t D);
 int saev_dictionary_coherence(const float* W, int64_t S, int64_t D, int32_t route, void* workspace, int64_t workspace_bytes,
                               float* out_value, int32_t* out_pair, int32_t* out_info, void* stream);
+/* DICTIONARY MATCH (the per-row form of COHERENCE: "mean max cosine similarity" between two dictionaries), context-free.  A is
+ * (Sa, D) and B is (Sb, D), fp32 row-major, 16-byte aligned, 1 <= Sa, Sb <= 2^20, 4 <= D <= 4096, D % 4 == 0.  With a^_i = a_i / ||a_i||
+ * and b^_j likewise (each row divided in fp32 by its fp32 norm, exactly as COHERENCE does it), c_ij = <a^_i, b^_j> and the score
+ * s_ij = c_ij (absolute == 0) or |c_ij| (absolute != 0):
+ *     out_value[i] = max_j s_ij,   out_index[i] = the smallest j that attains it among the exactly recomputed values
+ * over the admissible j.  SELF MODE (B == NULL, Sb == Sa): B = A and the pair j == i is not admissible; Sa == 1 then gives 0.0 and
+ * index -1.  If a^_i is not finite (a zero row, an inf or NaN entry) row i is NaN with the smallest admissible j; otherwise, if some
+ * b^_j is not finite, row i is NaN with the smallest such j -- as torch's max propagates NaN.
+ * route SAEV_MATCH_AUTO: COHERENCE's scheme with the bound made per row.  An fp16 MFMA pass over all tiles of the Sa x Sb rectangle
+ * gives per pair c~_ij and the same E_ij >= |c~_ij - c_ij|, hence s~_ij with |s~_ij - s_ij| <= E_ij in both score modes.  With
+ * L_i = max_j (s~_ij - E_ij), every pair with s~_ij + E_ij >= L_i is a candidate of row i: a maximiser p of row i has
+ * s~_p + E_p >= s_p >= s_q >= s~_q - E_q for every q of the row, so it (and every pair tied with it) is always one.  A second pass
+ * over the tiles that can hold a candidate writes the list; each candidate is recomputed exactly (the fp32 dot product of the fp32
+ * rows a^_i and b^_j in a fixed k order) and raised into its row's result by an integer max on (value, ~j).  Value and index are
+ * bit-reproducible from call to call.  List capacity: min(Sa Sb, max(4096, 8 Sa)) pairs.  OVERFLOW is never silent: if more pairs
+ * qualify, every row is answered on the exact route instead.  route SAEV_MATCH_EXACT forces that route: fp32 MFMA
+ * (v_mfma_f32_32x32x2_f32) of the rows a^ and b^ over every tile, the same tie rule.
+ * max_i out_value[i] of the self mode with absolute != 0 is the coherence of A to within the fp32 tolerance of either (not bit for
+ * bit: the two calls refine different candidates).
+ * Results are written on the device, nothing is read back: out_value[Sa], out_index[Sa], out_info[4] = {route taken
+ * (SAEV_MATCH_FILTERED / _EXACT / _OVERFLOW), candidates found (may exceed the capacity), tiles the second pass recomputed,
+ * capacity}.  workspace: saev_dictionary_match_workspace_bytes(Sa, Sb, D) bytes of device memory, 256-byte aligned (-1: unsupported
+ * shape); it holds both fp16 images and Sa x ceil(Sb / 128) floats, never Sa x Sb. */
+#define SAEV_MATCH_AUTO 0
+#define SAEV_MATCH_EXACT 1
+#define SAEV_MATCH_FILTERED 0   /* route taken: fp16 filter and exact refinement */
+#define SAEV_MATCH_OVERFLOW 2   /* route taken: the list overflowed, the exact route answered */
+int64_t saev_dictionary_match_workspace_bytes(int64_t Sa, int64_t Sb, int64_t D);
+int saev_dictionary_match(const float* A, int64_t Sa, const float* B, int64_t Sb, int64_t D, int32_t absolute, int32_t route,
+                          void* workspace, int64_t workspace_bytes, float* out_value, int32_t* out_index, int32_t* out_info,
+                          void* stream);
 /* BATCH STATISTICS (the log block, train.py:365-442; evaluate, train.py:510-618; the inference pass, inference.py), context-free:
  * one call per batch leaves every sum those three form, with no n x D or n x k temporary.  Inputs: x (n x D fp32) and its
  * reconstruction x_hat (n x D fp32, may be NULL), both 16-byte aligned; the codes as padded rows, idx (n x cap int32), val

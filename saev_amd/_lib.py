@@ -163,6 +163,8 @@ _SIGNATURES = {
     "saev_muon_newton_schulz": (C.c_int, [P, C.c_int64, C.c_int64, P, C.POINTER(SaevMuonCfg), C.c_int32, P, C.c_int64, P]),
     "saev_coherence_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "saev_dictionary_coherence": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int32, P, C.c_int64, P, P, P, P]),
+    "saev_dictionary_match_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "saev_dictionary_match": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64, P, P, P, P]),
     "saev_batch_stats_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "saev_batch_stats": (C.c_int, [P, P, P, P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(SaevBatchAcc), P, C.c_int64, P]),
     "saev_row_norm_mean": (C.c_int, [P, C.c_int64, C.c_int64, P, P, C.c_int64, P]),

@@ -23,13 +23,13 @@ namespace {
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int CT = 128;               // tile edge: 128 rows of W on each side of a tile
-constexpr int CK = 64;                // k per LDS stage of the fp16 filter
+constexpr int CT = COH_TILE;          // tile edge: 128 rows of W on each side of a tile
+constexpr int CK = COH_KSTAGE;        // k per LDS stage of the fp16 filter (64)
 constexpr int CLDS = CK + 8;          // (+8 fp16 of padding: row pitch 144 B, ds_read_b128 conflict-free)
 constexpr int XK = 32;                // k per LDS stage of the fp32 exact route
 constexpr int XLDS = XK + 4;          // (row pitch 144 B)
 constexpr float IMG_SCALE = 8192.f;   // 2^13: |w / n| <= 1 puts the largest element of a row in [2^13 / sqrt(D), 2^13]
-constexpr float IMG_UNSCALE = 1.4901161193847656e-08f;  // 2^-26, both operands' scales
+constexpr float IMG_UNSCALE = COH_IMG_UNSCALE;          // 2^-26, both operands' scales
 constexpr float F16_MIN_NORMAL = 6.103515625e-05f;      // 2^-14
 
 // control words (uint32) at the start of the workspace
@@ -75,13 +75,6 @@ __device__ __forceinline__ void tile_ij(long t, int* I, int* J) {
     while ((j + 1) * (j + 2) / 2 <= t) ++j;
     *J = (int)j;
     *I = (int)(t - j * (j + 1) / 2);
-}
-
-// E_ij >= |c~_ij - r_ij|, r_ij the refined fp32 value: Cauchy-Schwarz on the rounding errors of the images plus the fp32
-// accumulation of both the MFMA sum and the refinement (gam = 2 * 1.05 Dp 2^-22), with 2 % for the fp32 evaluation of the bound
-__device__ __forceinline__ float pair_bound(float2 a, float2 b, float gam) {
-#pragma clang fp contract(off)
-    return 1.02f * ((a.y * b.x + a.x * b.y + a.y * b.y) + gam * (a.x + a.y) * (b.x + b.y)) + 1e-30f;
 }
 
 // one wave per row of the padded image; rows past S are written as zeros
@@ -216,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void coh_filter_kernel(CohDev a) {
                         const int gi = I * CT + m, gj = J * CT + n;
                         if (gi < gj && gj < a.S) {
                             const float c = fabsf(acc[i][j][r]) * IMG_UNSCALE;
-                            const float e = pair_bound(rI[m], rJ[n], a.gam);
+                            const float e = coh_pair_bound(rI[m], rJ[n], a.gam);
                             lo = fmaxf(lo, c - e);
                             hi = fmaxf(hi, c + e);
                         }
@@ -246,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void coh_filter_kernel(CohDev a) {
                         const int gi = I * CT + m, gj = J * CT + n;
                         if (gi < gj && gj < a.S) {
                             const float c = fabsf(acc[i][j][r]) * IMG_UNSCALE;
-                            if (c + pair_bound(rI[m], rJ[n], a.gam) >= L) { keep |= 1ull << (16 * (2 * i + j) + r); ++cnt; }
+                            if (c + coh_pair_bound(rI[m], rJ[n], a.gam) >= L) { keep |= 1ull << (16 * (2 * i + j) + r); ++cnt; }
                         }
                     }
             int incl = cnt;
@@ -507,11 +500,18 @@ CohLayout coherence_layout(int S, int D) {
     return L;
 }
 
+hipError_t launch_coh_prepare(const float* W, int S, int D, int Sp, int Dp, float* nrm, float2* rn, uint16_t* img, uint32_t* nan_word,
+                              hipStream_t s) {
+    static_assert(CTL_NAN == 0, "coh_prepare_kernel raises ctl[CTL_NAN]: the word it is given");
+    hipLaunchKernelGGL(coh_prepare_kernel, dim3(Sp / 4), dim3(256), 0, s, W, S, D, Dp, nrm, rn, img, nan_word);
+    return hipGetLastError();
+}
+
 hipError_t launch_coherence(const float* W, int S, int D, int route, uint8_t* ws, const CohLayout& L, float* out_value,
                             int32_t* out_pair, int32_t* out_info, hipStream_t s) {
     CohDev a{};
     a.W = W; a.S = S; a.D = D; a.Dp = L.Dp; a.cap = L.cap; a.route = route; a.ntiles = L.ntiles;
-    a.gam = 2.0f * 1.05f * (float)L.Dp * 2.384185791015625e-07f;  // 2 x 1.05 Dp 2^-22
+    a.gam = coh_gamma(L.Dp);
     a.nrm = reinterpret_cast<float*>(ws + L.off_nrm);
     a.rn = reinterpret_cast<float2*>(ws + L.off_rn);
     a.img = reinterpret_cast<uint16_t*>(ws + L.off_img);
@@ -523,7 +523,8 @@ hipError_t launch_coherence(const float* W, int S, int D, int route, uint8_t* ws
     hipError_t e = hipMemsetAsync(a.ctl, 0, 64, s);
     if (e != hipSuccess) return e;
     if (S >= 2) {
-        hipLaunchKernelGGL(coh_prepare_kernel, dim3(L.Sp / 4), dim3(256), 0, s, W, S, D, L.Dp, a.nrm, a.rn, a.img, a.ctl);
+        e = launch_coh_prepare(W, S, D, L.Sp, L.Dp, a.nrm, a.rn, a.img, a.ctl + CTL_NAN, s);
+        if (e != hipSuccess) return e;
         const int grid = persistent_grid(L.ntiles);
         if (route == SAEV_COH_AUTO) {
             hipLaunchKernelGGL(coh_filter_kernel<1>, dim3(grid), dim3(256), 0, s, a);

@@ -575,4 +575,27 @@ int saev_dictionary_coherence(const float* W, int64_t S, int64_t D, int32_t rout
     return SAEV_OK;
 }
 
+// ---- dictionary match (include/saev_amd.h: DICTIONARY MATCH; kernels in dictmatch.hip) --------------------------------------
+int64_t saev_dictionary_match_workspace_bytes(int64_t Sa, int64_t Sb, int64_t D) {
+    const int64_t smax = (int64_t)1 << 20;
+    if (Sa < 1 || Sa > smax || Sb < 1 || Sb > smax || D < 4 || D > 4096 || D % 4 != 0) return -1;
+    return (int64_t)dictmatch_layout(Sa, Sb, (int)D).bytes;
+}
+
+int saev_dictionary_match(const float* A, int64_t Sa, const float* B, int64_t Sb, int64_t D, int32_t absolute, int32_t route,
+                          void* workspace, int64_t workspace_bytes, float* out_value, int32_t* out_index, int32_t* out_info,
+                          void* stream) {
+    const int64_t need = saev_dictionary_match_workspace_bytes(Sa, Sb, D);
+    if (need < 0 || (route != SAEV_MATCH_AUTO && route != SAEV_MATCH_EXACT)) return SAEV_INVALID_ARG;
+    if (!B && Sb != Sa) return SAEV_INVALID_ARG;  // self mode: Sb repeats Sa
+    if (!A || !workspace || !out_value || !out_index || !out_info) return SAEV_INVALID_ARG;
+    if (workspace_bytes < need || ((uintptr_t)workspace & 255) != 0 || ((uintptr_t)A & 15) != 0 || ((uintptr_t)B & 15) != 0)
+        return SAEV_INVALID_ARG;
+    const DmLayout L = dictmatch_layout(Sa, Sb, (int)D);
+    if (launch_dictmatch(A, (int)Sa, B, (int)Sb, (int)D, absolute, route, static_cast<uint8_t*>(workspace), L, out_value, out_index,
+                         out_info, (hipStream_t)stream) != hipSuccess)
+        return SAEV_HIP_ERROR;
+    return SAEV_OK;
+}
+
 }  // extern "C"

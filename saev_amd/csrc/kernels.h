@@ -799,6 +799,38 @@ CohLayout coherence_layout(int S, int D);
 // route: SAEV_COH_AUTO / SAEV_COH_EXACT; results written on the device, nothing read back
 hipError_t launch_coherence(const float* W, int S, int D, int route, uint8_t* ws, const CohLayout& L, float* out_value,
                             int32_t* out_pair, int32_t* out_info, hipStream_t stream);
+// What the per-row form (dictmatch.hip) shares with it.  The prepare pass of an (S, D) matrix, coh_prepare_kernel: nrm (S) the fp32
+// row norms; rn (S) {||w^_i||, ||d_i||}, both rounded up (not finite when the row's normalised form is not); img (Sp, Dp) the fp16
+// image h = fp16(2^13 w^) with subnormals flushed, zero past S rows and D columns, Sp and Dp multiples of (COH_TILE, COH_KSTAGE);
+// *nan_word (zeroed by the caller) is raised to ~(first row whose normalised form is not finite)
+constexpr int COH_TILE = 128;    // tile edge of the filters: rows per side
+constexpr int COH_KSTAGE = 64;   // k per LDS stage of the fp16 filters
+constexpr float COH_IMG_UNSCALE = 1.4901161193847656e-08f;  // 2^-26: both operands' image scales
+hipError_t launch_coh_prepare(const float* W, int S, int D, int Sp, int Dp, float* nrm, float2* rn, uint16_t* img, uint32_t* nan_word,
+                              hipStream_t stream);
+// accumulation term of the bound for images padded to Dp (the filter's MFMA sum and the refinement together): 2 x 1.05 Dp 2^-22
+inline float coh_gamma(int Dp) { return 2.0f * 1.05f * (float)Dp * 2.384185791015625e-07f; }
+// E_ij >= |c~_ij - r_ij|, r_ij the refined fp32 value: Cauchy-Schwarz on the rounding errors of the images plus the fp32
+// accumulation of both the MFMA sum and the refinement (gam = coh_gamma), with 2 % for the fp32 evaluation of the bound
+__device__ __forceinline__ float coh_pair_bound(float2 a, float2 b, float gam) {
+#pragma clang fp contract(off)
+    return 1.02f * ((a.y * b.x + a.x * b.y + a.y * b.y) + gam * (a.x + a.y) * (b.x + b.y)) + 1e-30f;
+}
+
+// ---- Dictionary match (dictmatch.hip): per-row nearest neighbour across two dictionaries ----------------------------------------
+constexpr long DM_CAND_PER_ROW = 8;      // list capacity: min(admissible pairs, max(DM_CAND_MIN, this x Sa))
+constexpr long DM_CAND_MIN = 4096;
+struct DmLayout {        // one workspace for A (Sa, D) against B (Sb, D); in self mode the B parts stay unused
+    int Sap, Sbp, Dp, nTA, nTB, cap;
+    long ntiles;         // nTA x nTB
+    size_t off_ctl, off_L, off_best, zero_bytes;  // control words, per-row bounds and results: one memset
+    size_t off_nrmA, off_rnA, off_imgA, off_nrmB, off_rnB, off_imgB, off_hi, off_cand, bytes;
+};
+DmLayout dictmatch_layout(long Sa, long Sb, int D);
+// B == nullptr: self mode (Sb is ignored, pair j == i excluded).  route: SAEV_MATCH_AUTO / SAEV_MATCH_EXACT; results written on
+// the device, nothing read back
+hipError_t launch_dictmatch(const float* A, int Sa, const float* B, int Sb, int D, int absolute, int route, uint8_t* ws,
+                            const DmLayout& L, float* out_value, int32_t* out_index, int32_t* out_info, hipStream_t stream);
 
 // ---- Batch statistics (batchstats.hip: kernels and their C entries) ---------------------------------------------------------
 // message of the last refused context-free call on this thread ("null context" before any): what saev_last_error(NULL) returns

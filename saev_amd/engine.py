@@ -183,6 +183,75 @@ def dictionary_coherence(W: torch.Tensor, *, route: str = "auto") -> CoherenceRe
                            overflow=code == 2, tiles_refiltered=tiles)
 
 
+@dataclasses.dataclass(frozen=True)
+class MatchResult:
+    """Per row i of A its nearest neighbour among the rows of B: ``values[i]`` the largest cosine similarity (signed, or its
+    absolute value) and ``indices[i]`` the smallest j that attains it, both device tensors.  route: "filter" (fp16 filter + exact
+    fp32 refinement) or "exact" (fp32 over every pair: asked for, or ``overflow`` -- more candidates than the list holds,
+    ``candidates`` of ``capacity``)."""
+
+    values: torch.Tensor   # (Sa,) float32
+    indices: torch.Tensor  # (Sa,) int32
+    route: str
+    candidates: int = 0
+    capacity: int = 0
+    overflow: bool = False
+    tiles_refiltered: int = 0  # 128 x 128 tiles the filter's second pass recomputed
+
+    @property
+    def mmcs(self) -> float:
+        """Mean max cosine similarity: the fp64 mean of ``values`` (NaN if any row is NaN)."""
+        return self.values.double().mean().item()
+
+
+_MATCH_LIMITS = "1 <= Sa, Sb <= 2**20, 4 <= D <= 4096, D % 4 == 0"
+
+
+def dictionary_match(A: torch.Tensor, B: torch.Tensor | None = None, *, absolute: bool = False, route: str = "auto") -> MatchResult:
+    """Nearest neighbour of every row of A among the rows of B by cosine similarity, ``(A_n @ B_n.T).max(dim=1)`` with
+    ``X_n = X / X.norm(dim=1, keepdim=True)`` (``.abs()`` first if ``absolute``), on the HIP kernels of saev_dictionary_match
+    (include/saev_amd.h: DICTIONARY MATCH): no Sa x Sb matrix, one small read-back.  ``B=None`` matches A against itself with
+    the pair j == i excluded (one row: 0.0 and index -1).  A: (Sa, D), B: (Sb, D), float32 on one HIP device, D % 4 == 0,
+    D <= 4096.  A row that meets a zero or non-finite row is NaN.  ``route="exact"`` forces the fp32 route over every pair."""
+    if route not in _COHERENCE_ROUTES:
+        raise ValueError(f"route must be one of {sorted(_COHERENCE_ROUTES)}, got {route!r}")
+    if A.ndim != 2 or (B is not None and B.ndim != 2):
+        raise ValueError(f"dictionary_match takes (S, D) matrices, got shapes {tuple(A.shape)}"
+                         + ("" if B is None else f" and {tuple(B.shape)}"))
+    Sa, D = A.shape
+    Sb = Sa if B is None else B.shape[0]
+    if B is not None and B.shape[1] != D:
+        raise ValueError(f"dictionary_match: A and B must share D, got {D} and {B.shape[1]}")
+    lib = _lib.load()
+    nbytes = int(lib.saev_dictionary_match_workspace_bytes(Sa, Sb, D))
+    if nbytes < 0:
+        raise ValueError(f"dictionary_match: unsupported shape {(Sa, Sb, D)} ({_MATCH_LIMITS})")
+    for X in (A,) if B is None else (A, B):
+        if not X.is_cuda or X.dtype != torch.float32:
+            raise ValueError("dictionary_match takes float32 device matrices")
+    if B is not None and B.device != A.device:
+        raise ValueError(f"dictionary_match: A and B must share a device, got {A.device} and {B.device}")
+
+    def aligned(X):
+        X = X.contiguous()
+        return X.clone() if X.data_ptr() % 16 else X
+
+    A = aligned(A)
+    B = None if B is None else aligned(B)
+    ws = torch.empty(nbytes, device=A.device, dtype=torch.uint8)
+    values = torch.empty(Sa, device=A.device, dtype=torch.float32)
+    indices = torch.empty(Sa, device=A.device, dtype=torch.int32)
+    info = torch.empty(4, device=A.device, dtype=torch.int32)  # route, candidates, tiles, capacity
+    with torch.cuda.device(A.device):
+        rc = lib.saev_dictionary_match(_ptr(A), Sa, None if B is None else _ptr(B), Sb, D, int(bool(absolute)),
+                                       _COHERENCE_ROUTES[route], _ptr(ws), nbytes, _ptr(values), _ptr(indices), _ptr(info), _stream())
+    if rc != 0:
+        raise _lib.SaevError(f"saev_dictionary_match failed (status {rc})")
+    code, cand, tiles, cap = info.cpu().tolist()
+    return MatchResult(values=values, indices=indices, route="filter" if code == 0 else "exact", candidates=cand, capacity=cap,
+                       overflow=code == 2, tiles_refiltered=tiles)
+
+
 def row_norm_mean(W: torch.Tensor) -> float:
     """``W.norm(dim=1).mean()`` of an (S, D) float32 device matrix on the HIP kernels of saev_row_norm_mean (the log block's
     metrics/avg_decoder_row_norm): exact fp64 squares, each norm rounded once to fp32, every sum in a fixed order; one read-back
