@@ -662,6 +662,105 @@ int saev_latent_topk_update(const int32_t* idx, const float* val, const int32_t*
                             const int32_t* indices, const float* data, int64_t nnz, const uint8_t* keep, int64_t n, int64_t S,
                             int64_t row_base, const saev_latent_topk_state* state, void* workspace, int64_t workspace_bytes,
                             void* stream);
+/* PROBE1D (the reference's contrib/trait_discovery tdiscovery.probe1d.Sparse1DProbe: what writes probe1d_metrics.npz next to
+ * token_acts.npz), context-free: for each of the S x C (latent j, class c) pairs the two-parameter logistic regression
+ * y_c ~ sigma(b + w x_j) over N rows, fitted by damped Newton (Levenberg-Marquardt) steps, and its loss and confusion counts.
+ * x is CSR: row_ptr (N + 1 int64, absolute positions into indices / data, non-decreasing), indices (int32 in [0, S)), data (fp32),
+ * nnz = row_ptr[N] - row_ptr[0] given by the host.  1 <= N, S < 2^31, 0 <= nnz < 2^31, 1 <= C <= 4096 (else SAEV_UNSUPPORTED).
+ * EVENT RULE: an event of latent j is a STORED entry of column j -- an explicitly stored 0.0 counts (unlike LATENT TOP-K), values may
+ * be negative; more than one entry per (row, latent) is outside the contract.  n_j = events of j; qx_j = max(sqrt(sum v^2 / n_j),
+ * 1e-6), 1 when n_j = 0; the N - n_j other rows of latent j enter every formula in closed form.
+ * LABELS, one of three forms (none or several is SAEV_INVALID_ARG): class ids class_u8 (N uint8, C <= 256) or class_i32 (N int32), the
+ * one-hot matrix implied; or y_matrix (N x C bytes, each 0 or 1).  They are packed to ybits (N x ceil(C / 32) uint32, bit c % 32 of
+ * word c / 32) and counted per class (pos, C int64; pi_c = pos_c / N); both forms of the same labels give the same bits.
+ * prepare writes into the caller's workspace (byte offsets: saev_probe1d_layout_of): the events latent-major -- starts (S + 1 int64),
+ * row (nnz int32) and val (nnz fp32), inside a latent in ASCENDING ROW ORDER --, qx (S fp64), chunk_starts (S + 1 int32: latent j is
+ * cut into ceil(n_j / chunk) chunks of chunk = 512 events), ybits, pos, and err (int32[0]: 0, or the largest SAEV_PROBE1D_ERR_* met
+ * -- a class id outside [0, C), a latent outside [0, S), a label byte above 1 -- found on the device; the caller reads it when it
+ * next synchronises, and every later result of that workspace is void if it is not 0).
+ * ARITHMETIC: everything is fp64.  For an event with value v (fp32, widened) and label y of pair (b, w): z = b + w v (product and sum
+ * rounded separately), e = exp(-|z|), sigma(|z|) = 1 / (1 + e), sigma(-|z|) = e sigma(|z|); mu = sigma(z), 1 - mu = sigma(-z) and
+ * s = mu (1 - mu) = sigma(|z|) sigma(-|z|) are taken from these two (no cancellation); the seven EVENT SUMS of a pair, in this order
+ * (sums: S x 7 x C fp64), are  mu,  (mu - y) v,  s,  s v,  s v^2,  the BCE-with-logits loss max(z, 0) - y z + log1p(e)  and  y.
+ * ORDER: a latent's events in ascending row order; each sub-chunk of 64 events is summed from zero, the sub-chunks of a chunk are
+ * added in order, the chunk sums of a latent are added in chunk order.  The order does not depend on C, on the launch or on timing:
+ * the sums are BIT-REPRODUCIBLE, and those of a class computed alone equal those computed among others.  Integer atomics only
+ * (counts, placement cursors, the slab maximum as the bit pattern of a non-negative double); none touches a sum.
+ * SOLVER, per pair, as the reference's fit: start b = base_c = logit(clamp(pi_c, 1e-8, 1 - 1e-8)), w = 0, lam = lam_init, prev_pred =
+ * prev_loss = NaN.  Per iteration, with mu0 = clamp(sigma(b), 1e-8, 1 - 1e-8), s0 = mu0 (1 - mu0), zf = (N - n_j) / N:
+ *   g0 = sum_mu / N + zf mu0 - pi + ridge (b - base),  g1 = sum_g1 / N + ridge w,  h0 = sum_s / N + zf s0 + ridge,
+ *   h1 = sum_sv / N,  h2 = sum_svv / N + ridge;  pos_zero = min(max(pi - sum_y / N, 0), zf), neg_zero = zf - pos_zero,
+ *   loss = sum_loss / N - (pos_zero log mu0 + neg_zero log1p(-min(mu0, 1 - 1e-8))) + ridge / 2 (w^2 + (b - base)^2).
+ * If prev_pred and prev_loss are finite: rho = (prev_loss - loss) / max(prev_pred, 1e-18); lam *= lam_shrink when rho >= 0.75 and the
+ * previous step was not clipped; lam *= lam_grow when rho <= 0.25 or it was; lam clamped to [1e-12, 1e12].  A pair with
+ * max(|g0|, |g1|) <= tol takes no step.  Otherwise up to five tries: det = (h0 + lam)(h2 + lam qx^2) - h1^2, valid if |det| > 1e-18
+ * (else the try's step is 0); (db, dw) = ((h2 + lam qx^2) g0 - h1 g1, (h0 + lam) g1 - h1 g0) / det, scaled by delta_logit / (norm +
+ * 1e-18) when norm = |(db, qx dw)| > delta_logit (CLIPPED); pred = g0 db + g1 dw - (h0 db^2 + 2 h1 db dw + h2 dw^2) / 2; accepted if
+ * pred is finite and > 0, else lam = clamp(lam lam_grow).  After five failures: (db, dw) = -alpha (g0, g1), alpha = 1e-3 delta_logit /
+ * (|(g0, max(qx, 1e-12) g1)| + 1e-18), pred = NaN, clipped.  Then b -= db, w -= dw, prev_loss = loss, prev_pred = pred.  A latent without
+ * events keeps b = base, w = 0, lam = lam_init, prev_pred = NaN, not clipped (its prev_loss is set like any other).
+ * TERMINATION per SLAB of class_slab_size consecutive classes: a slab stops after the first iteration at which the largest
+ * max(|g0|, |g1 / max(qx, 1e-12)|) over its pairs is <= tol (that iteration's step is applied); its pairs are never touched again.
+ * n_iter of a class is its slab's count.  fit = init, then max_iter x (events, update) with stopped slabs skipped on the device; with
+ * poll_every > 0 the host reads the number of running slabs every poll_every iterations (the call's only synchronisation) and stops
+ * launching at 0 -- the results do not depend on it.  coef / intercept (S x C) are rounded once to out_dtype on the way out.
+ * evaluate(b, w: S x C fp64, threshold in (0, 1)): per pair the mean BCE loss, the events' share summed in the order above and the
+ * zero rows as pos_zero softplus(-b) + neg_zero softplus(b) with the COUNTS pos_zero = min(max(pos_c - pos_nz, 0), N - n_j); and
+ * tp / fp / tn / fn with prediction mu > threshold (sigma(b) > threshold on the zero rows): exact integers, stored in out_dtype.
+ * evaluate and stats use the workspace's sums and partials as scratch.  update (exposed for tests, as stats is) runs one solver
+ * iteration on the workspace's state from `sums` (NULL: the workspace's); step_out (S x C x 4 fp64: db, dw, pred, lam; may be NULL) and
+ * flags_out (S x C int32: SAEV_PROBE1D_STEP_* | tries << 8; may be NULL) tell which branch a pair took.
+ * Arguments are checked before the device is touched; a refused call leaves its message with saev_last_error(NULL).  Nothing is
+ * allocated and, the poll of fit aside, nothing synchronises.  workspace: saev_probe1d_workspace_bytes(N, S, C, nnz) bytes of device
+ * memory, 256-byte aligned (-1: unsupported shape); it holds prepare's outputs, the solver state and 56 bytes per pair and per
+ * (chunk, class) of sums -- never an (nnz, C) array. */
+#define SAEV_PROBE1D_ERR_CLASS 1
+#define SAEV_PROBE1D_ERR_LATENT 2
+#define SAEV_PROBE1D_ERR_LABEL 3
+#define SAEV_PROBE1D_F32 0
+#define SAEV_PROBE1D_F64 1
+#define SAEV_PROBE1D_STEP_INACTIVE 1
+#define SAEV_PROBE1D_STEP_CLIPPED 2
+#define SAEV_PROBE1D_STEP_SINGULAR 4   /* some try met |det| <= 1e-18 */
+#define SAEV_PROBE1D_STEP_FALLBACK 8
+#define SAEV_PROBE1D_STEP_EMPTY 16
+#define SAEV_PROBE1D_STEP_GROWN 32     /* the rho rule grew lam before the step */
+#define SAEV_PROBE1D_STEP_SHRUNK 64
+typedef struct {
+    int32_t struct_size;       /* sizeof(saev_probe1d_cfg) of the caller (fields past it read as 0) */
+    int32_t max_iter;
+    int32_t class_slab_size;
+    int32_t poll_every;        /* 0: the host never looks */
+    int32_t out_dtype;         /* SAEV_PROBE1D_F32 or SAEV_PROBE1D_F64 */
+    int32_t reserved;
+    double ridge, tol, lam_init, lam_shrink, lam_grow, delta_logit;
+} saev_probe1d_cfg;
+typedef struct {               /* byte offsets into the workspace (all multiples of 256) */
+    int32_t struct_size;
+    int32_t chunk;             /* events per chunk */
+    int64_t words;             /* ceil(C / 32) */
+    int64_t max_chunks;        /* bound of chunk_starts[S] */
+    int64_t parts;
+    int64_t total_bytes;
+    int64_t off_err, off_starts, off_chunk_starts, off_row, off_val, off_qx, off_ybits, off_pos, off_cnt, off_tot;
+    int64_t off_b, off_w, off_lam, off_prev_pred, off_prev_loss, off_clipped;   /* state: S x C fp64 each, clipped int32 */
+    int64_t off_sums, off_part, off_gmax, off_done, off_n_iter, off_active;     /* done, n_iter: per slab int32 */
+} saev_probe1d_layout;
+int64_t saev_probe1d_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t nnz);
+int saev_probe1d_layout_of(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_probe1d_layout* out);
+int saev_probe1d_prepare(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+                         const uint8_t* class_u8, const int32_t* class_i32, const uint8_t* y_matrix, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+int saev_probe1d_stats(int64_t N, int64_t S, int64_t C, int64_t nnz, const double* b, const double* w, double* sums_out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int saev_probe1d_init(int64_t N, int64_t S, int64_t C, int64_t nnz, const saev_probe1d_cfg* cfg, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+int saev_probe1d_update(int64_t N, int64_t S, int64_t C, int64_t nnz, const saev_probe1d_cfg* cfg, const double* sums, double* step_out,
+                        int32_t* flags_out, void* workspace, int64_t workspace_bytes, void* stream);
+int saev_probe1d_fit(int64_t N, int64_t S, int64_t C, int64_t nnz, const saev_probe1d_cfg* cfg, void* coef_out, void* intercept_out,
+                     int32_t* n_iter_out, void* workspace, int64_t workspace_bytes, void* stream);
+int saev_probe1d_evaluate(int64_t N, int64_t S, int64_t C, int64_t nnz, const double* b, const double* w, double threshold, int32_t out_dtype,
+                          void* loss, void* tp, void* fp, void* tn, void* fn, void* workspace, int64_t workspace_bytes, void* stream);
 /* PARAMETER OWNERSHIP.  With the f16r encoder the context keeps, from one call to the next, what its forward needs of W_enc
  * (fp16 operand images, a slice-major fp32 transpose, bias and norm shares: written by the Adam launch of saev_train_step, or by
  * the last forward that prepared them itself) and uses it for as long as only the library has written the parameter buffer.  A

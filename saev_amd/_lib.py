@@ -80,6 +80,23 @@ class SaevLatentTopKState(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("k", C.c_int32), ("top_val", C.c_void_p), ("top_row", C.c_void_p), ("top_cnt", C.c_void_p)]
 
 
+class SaevProbe1DCfg(C.Structure):
+    """include/saev_amd.h: saev_probe1d_cfg (the solver's hyper-parameters, the reference's names)."""
+
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "max_iter", "class_slab_size", "poll_every", "out_dtype", "reserved")] + \
+               [(n, C.c_double) for n in ("ridge", "tol", "lam_init", "lam_shrink", "lam_grow", "delta_logit")]
+
+
+class SaevProbe1DLayout(C.Structure):
+    """include/saev_amd.h: saev_probe1d_layout (byte offsets into the workspace of the probe1d entries)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("chunk", C.c_int32)] + \
+               [(n, C.c_int64) for n in ("words", "max_chunks", "parts", "total_bytes", "off_err", "off_starts", "off_chunk_starts", "off_row",
+                                         "off_val", "off_qx", "off_ybits", "off_pos", "off_cnt", "off_tot", "off_b", "off_w", "off_lam",
+                                         "off_prev_pred", "off_prev_loss", "off_clipped", "off_sums", "off_part", "off_gmax", "off_done",
+                                         "off_n_iter", "off_active")]
+
+
 ACT_TOPK, ACT_RELU, ACT_BATCHTOPK = 0, 1, 2
 ROW_OVERFLOW = -7  # saev_status SAEV_ROW_OVERFLOW
 BATCH_OVERWRITE = 1
@@ -171,6 +188,14 @@ _SIGNATURES = {
     "saev_latent_topk_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "saev_latent_topk_update": (C.c_int, [P, P, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(SaevLatentTopKState), P, C.c_int64, P]),
+    "saev_probe1d_workspace_bytes": (C.c_int64, [C.c_int64] * 4),
+    "saev_probe1d_layout_of": (C.c_int, [C.c_int64] * 4 + [C.POINTER(SaevProbe1DLayout)]),
+    "saev_probe1d_prepare": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, C.c_int64, P]),
+    "saev_probe1d_stats": (C.c_int, [C.c_int64] * 4 + [P, P, P, P, C.c_int64, P]),
+    "saev_probe1d_init": (C.c_int, [C.c_int64] * 4 + [C.POINTER(SaevProbe1DCfg), P, C.c_int64, P]),
+    "saev_probe1d_update": (C.c_int, [C.c_int64] * 4 + [C.POINTER(SaevProbe1DCfg), P, P, P, P, C.c_int64, P]),
+    "saev_probe1d_fit": (C.c_int, [C.c_int64] * 4 + [C.POINTER(SaevProbe1DCfg), P, P, P, P, C.c_int64, P]),
+    "saev_probe1d_evaluate": (C.c_int, [C.c_int64] * 4 + [P, P, C.c_double, C.c_int32, P, P, P, P, P, P, C.c_int64, P]),
     "saev_comm_unique_id": (C.c_int, [P]),
     "saev_comm_init": (C.c_int, [P, P, C.c_int32, C.c_int32]),
     "saev_comm_world": (C.c_int, [P]),

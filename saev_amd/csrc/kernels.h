@@ -837,3 +837,8 @@ hipError_t launch_dictmatch(const float* A, int Sa, const float* B, int Sb, int 
 const char* free_error();
 // leaves `msg` there and returns `code`: how a context-free entry of another file refuses a call (latenttopk.hip)
 int free_refuse(int code, const char* msg);
+
+// ---- Per-latent logistic probes (probe1d.hip: kernels and their C entries; include/saev_amd.h: PROBE1D) ------------------------
+// events per work item of the hot kernel: a latent firing on every one of 5 M rows is ~10 000 waves' worth, not one wave's
+constexpr int P1_CHUNK = 512;
+constexpr int P1_PARTS = 1024;  // at most this many contiguous parts of the CSR entries in the stable counting sort of prepare

@@ -500,6 +500,170 @@ class LatentTopK:
                               counts=self.top_cnt.to(torch.int64).cpu())
 
 
+@dataclasses.dataclass(frozen=True)
+class Probe1DHyper:
+    """The reference's Sparse1DProbe hyper-parameters (include/saev_amd.h: saev_probe1d_cfg)."""
+
+    ridge: float = 1e-8
+    tol: float = 1e-6
+    max_iter: int = 200
+    lam_init: float = 1e-3
+    lam_shrink: float = 0.1
+    lam_grow: float = 10.0
+    delta_logit: float = 6.0
+    class_slab_size: int = 8
+
+
+class Probe1D:
+    """Per-latent logistic probes on one prepared split (include/saev_amd.h: PROBE1D): the workspace of the
+    saev_probe1d_* entries for a CSR matrix x (N, S) and labels over C classes, and views of what ``prepare`` leaves in it.
+    ``prepare`` sorts the stored entries latent-major and packs the labels; ``stats`` gives the seven event sums of every pair at
+    given (b, w); ``fit`` runs the solver on the device; ``evaluate`` gives loss and confusion counts at given (b, w).  All sums are
+    fp64 in a fixed order: two runs give the same bits."""
+
+    CHUNK = 512
+    MAX_CLASSES = 4096
+    _DTYPES = {torch.float32: 0, torch.float64: 1}
+    _ERRORS = {1: "a class id lies outside [0, n_classes)", 2: "a column index lies outside [0, n_latents)", 3: "a label is neither 0 nor 1"}
+
+    def __init__(self, n_rows: int, n_latents: int, n_classes: int, nnz: int, device):
+        for name, v, hi in (("n_rows", n_rows, 2**31), ("n_latents", n_latents, 2**31), ("n_classes", n_classes, self.MAX_CLASSES + 1)):
+            if not 1 <= v < hi:
+                raise ValueError(f"Probe1D: unsupported {name} {v} (1 <= {name} < {hi})")
+        if not 0 <= nnz < 2**31:
+            raise ValueError(f"Probe1D: unsupported nnz {nnz} (0 <= nnz < 2^31)")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("Probe1D runs on a HIP device only (there is no CPU path)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = _lib.load()
+        self.shape = (n_rows, n_latents, n_classes, nnz)
+        self.layout = _lib.SaevProbe1DLayout()
+        _lib.check(self.lib, None, self.lib.saev_probe1d_layout_of(*self.shape, C.byref(self.layout)), "saev_probe1d_layout_of")
+        self._ws = torch.empty(self.layout.total_bytes, device=self.device, dtype=torch.uint8)
+        self.prepared = False
+
+    def _view(self, off: int, dtype, *shape):
+        n = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
+        return self._ws[off:off + n].view(dtype).view(*shape)
+
+    # what prepare leaves, and the solver state (views into the workspace)
+    starts = property(lambda self: self._view(self.layout.off_starts, torch.int64, self.shape[1] + 1))
+    chunk_starts = property(lambda self: self._view(self.layout.off_chunk_starts, torch.int32, self.shape[1] + 1))
+    row = property(lambda self: self._view(self.layout.off_row, torch.int32, self.shape[3]))
+    val = property(lambda self: self._view(self.layout.off_val, torch.float32, self.shape[3]))
+    qx = property(lambda self: self._view(self.layout.off_qx, torch.float64, self.shape[1]))
+    ybits = property(lambda self: self._view(self.layout.off_ybits, torch.int32, self.shape[0], self.layout.words))
+    pos = property(lambda self: self._view(self.layout.off_pos, torch.int64, self.shape[2]))
+    err = property(lambda self: self._view(self.layout.off_err, torch.int32, 1))
+    done = property(lambda self: self._view(self.layout.off_done, torch.int32, self.shape[2]))
+
+    def state(self, name: str) -> torch.Tensor:
+        """b, w, lam, prev_pred, prev_loss (S, C) float64 or clipped (S, C) int32: the solver state, in place."""
+        off = getattr(self.layout, "off_" + name)
+        return self._view(off, torch.int32 if name == "clipped" else torch.float64, self.shape[1], self.shape[2])
+
+    def _call(self, name: str, *args) -> None:
+        with torch.cuda.device(self.device):
+            rc = getattr(self.lib, name)(*args, _ptr(self._ws), self._ws.numel(), _stream())
+        _lib.check(self.lib, None, rc, name)
+
+    def _on(self, t, dtype, shape, what):
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != self.device:
+            raise ValueError(f"{what} must be {dtype} of shape {tuple(shape)} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.contiguous()
+
+    def prepare(self, indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, *, labels: torch.Tensor | None = None,
+                y: torch.Tensor | None = None) -> "Probe1D":
+        """x as CSR on the device (indptr (N + 1) int64 from 0, indices (nnz) int32, data (nnz) float32) and the labels in ONE form:
+        ``labels`` (N) uint8 / int32 class ids, or ``y`` (N, C) bool / uint8 with entries 0 or 1.  Reads the error word back."""
+        n, s, c, nnz = self.shape
+        if (labels is None) == (y is None):
+            raise ValueError("Probe1D.prepare: give the labels as class ids (labels=) or as an N x C matrix (y=), one of the two")
+        indptr = self._on(indptr, torch.int64, (n + 1,), "indptr")
+        indices = self._on(indices, torch.int32, (nnz,), "indices")
+        data = self._on(data, torch.float32, (nnz,), "data")
+        u8 = i32 = mat = None
+        if labels is not None:
+            if labels.dtype == torch.uint8 and c <= 256:
+                u8 = self._on(labels, torch.uint8, (n,), "labels")
+            elif labels.dtype in (torch.uint8, torch.int32, torch.int64):
+                i32 = self._on(labels.to(torch.int32), torch.int32, (n,), "labels")
+            else:
+                raise ValueError(f"labels must be uint8, int32 or int64 class ids, got {labels.dtype}")
+        else:
+            if y.dtype == torch.bool:
+                y = y.view(torch.uint8)
+            mat = self._on(y, torch.uint8, (n, c), "y")
+        self._call("saev_probe1d_prepare", _ptr(indptr), _ptr(indices), _ptr(data), nnz, n, s, c, _ptr(u8), _ptr(i32), _ptr(mat))
+        code = int(self.err.item())
+        if code != 0:
+            raise ValueError(f"Probe1D.prepare: {self._ERRORS.get(code, code)} (found on the device)")
+        self.prepared = True
+        return self
+
+    def _cfg(self, hp: Probe1DHyper, dtype=torch.float32, poll_every: int = 0) -> "_lib.SaevProbe1DCfg":
+        if dtype not in self._DTYPES:
+            raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype}")
+        return _lib.SaevProbe1DCfg(struct_size=C.sizeof(_lib.SaevProbe1DCfg), max_iter=hp.max_iter, class_slab_size=hp.class_slab_size,
+                                   poll_every=poll_every, out_dtype=self._DTYPES[dtype], ridge=hp.ridge, tol=hp.tol, lam_init=hp.lam_init,
+                                   lam_shrink=hp.lam_shrink, lam_grow=hp.lam_grow, delta_logit=hp.delta_logit)
+
+    def _need(self):
+        if not self.prepared:
+            raise _lib.SaevError("Probe1D: prepare() first")
+
+    def stats(self, b: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+        """The event sums (S, 7, C) float64 of every pair at (b, w), each (S, C) float64: mu, (mu - y) v, s, s v, s v^2, loss, y."""
+        self._need()
+        n, s, c, nnz = self.shape
+        b, w = self._on(b, torch.float64, (s, c), "b"), self._on(w, torch.float64, (s, c), "w")
+        out = torch.empty(s, 7, c, device=self.device, dtype=torch.float64)
+        self._call("saev_probe1d_stats", n, s, c, nnz, _ptr(b), _ptr(w), _ptr(out))
+        return out
+
+    def init(self, hp: Probe1DHyper) -> None:
+        self._need()
+        self._call("saev_probe1d_init", *self.shape, C.byref(self._cfg(hp)))
+
+    def update(self, hp: Probe1DHyper, sums: torch.Tensor | None = None, *, debug: bool = False):
+        """One solver iteration on the state in the workspace from ``sums`` (None: the workspace's own).  With ``debug`` returns
+        (step (S, C, 4) float64: db, dw, pred, lam; flags (S, C) int32: SAEV_PROBE1D_STEP_* | tries << 8)."""
+        self._need()
+        n, s, c, nnz = self.shape
+        if sums is not None:
+            sums = self._on(sums, torch.float64, (s, 7, c), "sums")
+        step = torch.zeros(s, c, 4, device=self.device, dtype=torch.float64) if debug else None
+        flags = torch.zeros(s, c, device=self.device, dtype=torch.int32) if debug else None
+        self._call("saev_probe1d_update", n, s, c, nnz, C.byref(self._cfg(hp)), _ptr(sums), _ptr(step), _ptr(flags))
+        return (step, flags) if debug else None
+
+    def fit(self, hp: Probe1DHyper, *, dtype=torch.float32, poll_every: int = 1):
+        """(coef, intercept) (S, C) in ``dtype`` and n_iter (C) int32.  ``poll_every`` > 0: the host reads the number of running slabs
+        every that many iterations and stops launching at 0 (same results as 0 = never)."""
+        self._need()
+        n, s, c, nnz = self.shape
+        coef = torch.empty(s, c, device=self.device, dtype=dtype)
+        intercept = torch.empty(s, c, device=self.device, dtype=dtype)
+        n_iter = torch.empty(c, device=self.device, dtype=torch.int32)
+        self._call("saev_probe1d_fit", n, s, c, nnz, C.byref(self._cfg(hp, dtype, poll_every)), _ptr(coef), _ptr(intercept), _ptr(n_iter))
+        return coef, intercept, n_iter
+
+    def evaluate(self, b: torch.Tensor, w: torch.Tensor, threshold: float = 0.5, *, dtype=torch.float32):
+        """(loss, tp, fp, tn, fn), each (S, C) in ``dtype``, at (b, w) (S, C) float64."""
+        self._need()
+        if not 0.0 < threshold < 1.0:
+            raise ValueError("threshold must be between 0 and 1.")
+        if dtype not in self._DTYPES:
+            raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype}")
+        n, s, c, nnz = self.shape
+        b, w = self._on(b, torch.float64, (s, c), "b"), self._on(w, torch.float64, (s, c), "w")
+        outs = [torch.empty(s, c, device=self.device, dtype=dtype) for _ in range(5)]
+        self._call("saev_probe1d_evaluate", n, s, c, nnz, _ptr(b), _ptr(w), float(threshold), self._DTYPES[dtype], *map(_ptr, outs))
+        return tuple(outs)
+
+
 @dataclasses.dataclass
 class StepStats:
     mse: float
