@@ -587,6 +587,65 @@ int64_t saev_dictionary_match_workspace_bytes(int64_t Sa, int64_t Sb, int64_t D)
 int saev_dictionary_match(const float* A, int64_t Sa, const float* B, int64_t Sb, int64_t D, int32_t absolute, int32_t route,
                           void* workspace, int64_t workspace_bytes, float* out_value, int32_t* out_index, int32_t* out_info,
                           void* stream);
+/* K-MEANS (the reference's default baseline, contrib/trait_discovery tdiscovery/baselines.py MiniBatchKMeans.partial_fit),
+ * context-free: the four device stages of one mini-batch step, with no n x k or k x k distance matrix in memory.  Matrices are fp32
+ * row-major, 16-byte aligned: X (n, D) the batch, C (k, D) the centres, 1 <= n, k <= 2^20, 4 <= D <= 4096, D % 4 == 0.  Results are
+ * written on the device, nothing is read back, there are no floating-point atomics, and every output is bit-reproducible from
+ * call to call.
+ * THE REFINED VALUE.  r_ij = the fp32 sum over k = 0 .. D-1, in that order, of (x_ik - c_jk)^2: a subtraction, a product and an
+ * addition per k, each rounded once (no contraction), so r_ij depends on (i, j), X and C only.  One device function forms it
+ * wherever it is needed; the distance is sqrtf(r_ij).  |r_ij - ||x_i - c_j||^2| <= (D + 3) 2^-24 ||x_i - c_j||^2.
+ * ASSIGN.  farthest == 0: out_dist2[i] = min_j r_ij and out_index[i] = the smallest j attaining it among the exactly recomputed
+ * values; farthest != 0: the same with max (the re-seeding of collapsed centres).  route SAEV_KMEANS_AUTO is DICTIONARY MATCH's
+ * scheme with a bound for squared distances.  X and C are first centred on mu = the fp32 mean of the centres (distances do not
+ * depend on it, the bound does: it is proportional to ||x - mu|| ||c - mu||); COHERENCE's prepare pass gives the unit-row fp16 images
+ * of the centred rows x' = fl(x - mu), c' = fl(c - mu); an fp16 MFMA pass over all 128 x 128 tiles gives per pair the cosine c~ with
+ * COHERENCE's E_cos, hence s~_ij = ||x'||^2 + ||c'||^2 - 2 nx nc c~ (nx, nc the fp32 norms the images were divided by, the squares
+ * summed in fp64) and, evaluated in fp64,
+ *     E1 = 2 nx nc (E_cos + 1.25e-7 ||x^|| ||c^||) + 1e-12 (||x'||^2 + ||c'||^2),   up = sqrt(max(s~ + E1, 0)),
+ *     rho = 5.97e-8 (||x'|| + ||c'||),   dl = rho (2 up + rho),   E_ij = E1 + dl + 1.001 (D + 3) 2^-24 (up^2 + dl)  >= |s~_ij - r_ij|
+ * (DESIGN.md 3.18 derives each term: the images, the division by the fp32 norm, the centring's rounding, the fp32 difference form).
+ * With g = -s (nearest) or s (farthest) and L_i = max_j (g~_ij - E_ij), every pair with g~_ij + E_ij >= L_i is a candidate of row
+ * i: the row's optimum and every pair tied with it always are.  A second pass over the tiles that can hold a candidate writes the
+ * list; each candidate's r_ij is recomputed and raised into the row's result by an integer max on (key(value), ~j).  List
+ * capacity: min(n k, max(4096, 8 n)) pairs (collapsed: min(k (k - 1) / 2, max(4096, 8 k))).  OVERFLOW is never silent: if more pairs
+ * qualify -- or some centred row has no finite unit image: a row equal to mu, a norm outside fp32 -- every row is answered on the
+ * exact route and out_info says so.  route SAEV_KMEANS_EXACT forces that route: r_ij of every pair by the same device function,
+ * the same tie rule.  BOTH ROUTES RETURN THE SAME BITS.  k == 1 (the one centre is mu: nothing to filter) is answered on the exact
+ * route and reported as SAEV_KMEANS_EXACT, in ASSIGN and in COLLAPSED: OVERFLOW always means that the filter was tried and failed.
+ * out_info[4] = {route taken (SAEV_KMEANS_FILTERED / _EXACT / _OVERFLOW, or SAEV_KMEANS_NONFINITE: X or C holds an inf or a NaN --
+ * every out_index is then -1, which GROUP ignores, the other outputs are unspecified, every write stays in bounds), candidates found (may exceed the capacity), tiles the
+ * second pass recomputed, capacity}.  workspace: saev_kmeans_workspace_bytes(n, k, D) bytes of device memory, 256-byte aligned
+ * (-1: unsupported shape); it holds the centred fp32 copies, both fp16 images and n x ceil(k / 128) doubles, never n x k.
+ * GROUP.  From index[n] (entries outside [0, k) are ignored): counts[k] the rows per centre, starts[k + 1] their exclusive prefix
+ * sums, rows[n] the row ids grouped by centre and ASCENDING within each centre -- a stable counting sort's result: the placement
+ * uses integer atomics, then every centre's segment is put in order, so scheduling cannot show: a segment of up to 4096 rows is
+ * sorted in LDS, a longer one is written afresh as the stable compaction {i : index[i] == j} in one pass over index (at most
+ * n / 4096 centres are that long), so one centre may take the whole of the largest batch.
+ * UPDATE.  The reference's running-mean update, in place: sums_j = the fp32 sum of centre j's rows in ascending row order (a
+ * one-thread index_add_ into zeros); a centre with a batch count above zero becomes (c * prev + sums) / (prev + count) -- a
+ * multiply, an add and a correctly rounded divide, uncontracted -- and cluster_counts[j] (the reference's float32 vector) becomes
+ * prev + count.  repl_rows (may be NULL): 0 <= repl_rows[j] < n on a centre with no row of the batch is the reference's empty-cluster
+ * replacement, "this centre's batch is exactly that one row, with count 1".  out_inertia (one double, may be NULL): the fp64 mean of
+ * dist2[n] in a fixed order.
+ * COLLAPSED.  For every pair i < j of centres with sqrtf(r_ij) < tol the loser is i if cluster_counts[i] <= cluster_counts[j], else
+ * j; out_loser[k] (bytes) is the 0/1 mask of losers -- idempotent stores, no pair list leaves the call.  The same filter in self
+ * mode over the tiles I <= J: a pair is a candidate unless s~ - E >= tol^2 (then sqrt(r) > tol, and sqrtf is monotone).  The same
+ * overflow rule, exact route and out_info; workspace: saev_kmeans_workspace_bytes(k, k, D).  k == 1 or tol <= 0: no losers. */
+#define SAEV_KMEANS_AUTO 0
+#define SAEV_KMEANS_EXACT 1
+#define SAEV_KMEANS_FILTERED 0    /* route taken: fp16 filter and exact refinement */
+#define SAEV_KMEANS_OVERFLOW 2    /* route taken: the filter could not answer (list overflow, a row without an image): exact route */
+#define SAEV_KMEANS_NONFINITE (-1) /* X or C holds an inf or a NaN */
+int64_t saev_kmeans_workspace_bytes(int64_t n, int64_t k, int64_t D);
+int saev_kmeans_assign(const float* X, int64_t n, const float* C, int64_t k, int64_t D, int32_t farthest, int32_t route,
+                       void* workspace, int64_t workspace_bytes, float* out_dist2, int32_t* out_index, int32_t* out_info, void* stream);
+int saev_kmeans_group(const int32_t* index, int64_t n, int64_t k, int32_t* counts, int32_t* starts, int32_t* rows, void* stream);
+int saev_kmeans_update(const float* X, int64_t n, int64_t D, int64_t k, const int32_t* starts, const int32_t* rows,
+                       const int32_t* repl_rows, float* centers, float* cluster_counts, double* out_inertia, const float* dist2,
+                       void* stream);
+int saev_kmeans_collapsed(const float* C, int64_t k, int64_t D, float tol, const float* cluster_counts, int32_t route, void* workspace,
+                          int64_t workspace_bytes, uint8_t* out_loser, int32_t* out_info, void* stream);
 /* BATCH STATISTICS (the log block, train.py:365-442; evaluate, train.py:510-618; the inference pass, inference.py), context-free:
  * one call per batch leaves every sum those three form, with no n x D or n x k temporary.  Inputs: x (n x D fp32) and its
  * reconstruction x_hat (n x D fp32, may be NULL), both 16-byte aligned; the codes as padded rows, idx (n x cap int32), val

@@ -182,6 +182,11 @@ _SIGNATURES = {
     "saev_dictionary_coherence": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int32, P, C.c_int64, P, P, P, P]),
     "saev_dictionary_match_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
     "saev_dictionary_match": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64, P, P, P, P]),
+    "saev_kmeans_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "saev_kmeans_assign": (C.c_int, [P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, P, C.c_int64, P, P, P, P]),
+    "saev_kmeans_group": (C.c_int, [P, C.c_int64, C.c_int64, P, P, P, P]),
+    "saev_kmeans_update": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, P, P, P, P]),
+    "saev_kmeans_collapsed": (C.c_int, [P, C.c_int64, C.c_int64, C.c_float, P, C.c_int32, P, C.c_int64, P, P, P]),
     "saev_batch_stats_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "saev_batch_stats": (C.c_int, [P, P, P, P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(SaevBatchAcc), P, C.c_int64, P]),
     "saev_row_norm_mean": (C.c_int, [P, C.c_int64, C.c_int64, P, P, C.c_int64, P]),

@@ -832,6 +832,26 @@ DmLayout dictmatch_layout(long Sa, long Sb, int D);
 hipError_t launch_dictmatch(const float* A, int Sa, const float* B, int Sb, int D, int absolute, int route, uint8_t* ws,
                             const DmLayout& L, float* out_value, int32_t* out_index, int32_t* out_info, hipStream_t stream);
 
+// ---- Mini-batch k-means (kmeans.hip: kernels and their C entries; include/saev_amd.h: K-MEANS) ---------------------------------
+constexpr long KM_CAND_PER_ROW = 8;      // list capacity: min(n k, max(KM_CAND_MIN, this x n)) -- a guess until measured
+constexpr long KM_CAND_MIN = 4096;
+struct KmLayout {        // one workspace for X (n, D) against C (k, D); collapsed uses the X side of kmeans_layout(k, k, D)
+    int np, kp, Dp, nTX, nTC, cap;
+    long ntiles;         // nTX x nTC
+    size_t off_ctl, off_L, off_best, zero_bytes;  // control words, per-row bounds and results: one memset
+    size_t off_mu, off_part, off_Xc, off_rowX, off_nrmX, off_rnX, off_imgX, off_Cc, off_rowC, off_nrmC, off_rnC, off_imgC, off_hi,
+        off_cand, bytes;
+};
+KmLayout kmeans_layout(long n, long k, int D);
+// route: SAEV_KMEANS_AUTO / SAEV_KMEANS_EXACT; results written on the device, nothing read back
+hipError_t launch_kmeans_assign(const float* X, int n, const float* C, int k, int D, int farthest, int route, uint8_t* ws,
+                                const KmLayout& L, float* out_dist2, int32_t* out_index, int32_t* out_info, hipStream_t stream);
+hipError_t launch_kmeans_group(const int32_t* index, int n, int k, int32_t* counts, int32_t* starts, int32_t* rows, hipStream_t stream);
+hipError_t launch_kmeans_update(const float* X, int n, int D, int k, const int32_t* starts, const int32_t* rows, const int32_t* repl,
+                                float* centers, float* counts, double* out_inertia, const float* dist2, hipStream_t stream);
+hipError_t launch_kmeans_collapsed(const float* C, int k, int D, float tol, const float* counts, int route, uint8_t* ws,
+                                   const KmLayout& L, uint8_t* out_loser, int32_t* out_info, hipStream_t stream);
+
 // ---- Batch statistics (batchstats.hip: kernels and their C entries) ---------------------------------------------------------
 // message of the last refused context-free call on this thread ("null context" before any): what saev_last_error(NULL) returns
 const char* free_error();

@@ -252,6 +252,180 @@ def dictionary_match(A: torch.Tensor, B: torch.Tensor | None = None, *, absolute
                        overflow=code == 2, tiles_refiltered=tiles)
 
 
+@dataclasses.dataclass(frozen=True)
+class AssignResult:
+    """Per row i of X its nearest (or farthest) centre: ``dist2[i]`` the refined squared distance r_ij and ``indices[i]`` the smallest
+    j that attains it, both device tensors.  route: "filter" (fp16 filter + exact fp32 refinement) or "exact" (every pair: asked
+    for, or ``overflow`` -- the filter could not answer, ``candidates`` of ``capacity``)."""
+
+    dist2: torch.Tensor    # (n,) float32
+    indices: torch.Tensor  # (n,) int32
+    route: str
+    candidates: int = 0
+    capacity: int = 0
+    overflow: bool = False
+    tiles_refiltered: int = 0  # 128 x 128 tiles the filter's second pass recomputed
+
+
+@dataclasses.dataclass(frozen=True)
+class CollapsedResult:
+    """``losers``: (k,) bool device mask of the centres that lose a pair closer than the tolerance; the rest as AssignResult."""
+
+    losers: torch.Tensor
+    route: str
+    candidates: int = 0
+    capacity: int = 0
+    overflow: bool = False
+    tiles_refiltered: int = 0
+
+
+_KMEANS_LIMITS = "1 <= n, k <= 2**20, 4 <= D <= 4096, D % 4 == 0"
+KMEANS_NONFINITE = -1  # include/saev_amd.h: SAEV_KMEANS_NONFINITE
+
+
+def _kmeans_matrix(what: str, X: torch.Tensor) -> torch.Tensor:
+    if X.ndim != 2:
+        raise ValueError(f"{what} takes (rows, D) matrices, got shape {tuple(X.shape)}")
+    if not X.is_cuda or X.dtype != torch.float32:
+        raise ValueError(f"{what} takes float32 device matrices")
+    X = X.contiguous()
+    return X.clone() if X.data_ptr() % 16 else X
+
+
+def _kmeans_workspace(what: str, n: int, k: int, D: int, device) -> tuple[torch.Tensor, int]:
+    nbytes = int(_lib.load().saev_kmeans_workspace_bytes(n, k, D))
+    if nbytes < 0:
+        raise ValueError(f"{what}: unsupported shape {(n, k, D)} ({_KMEANS_LIMITS})")
+    return torch.empty(nbytes, device=device, dtype=torch.uint8), nbytes
+
+
+def _kmeans_info(what: str, info) -> dict:
+    code, cand, tiles, cap = info
+    if code == KMEANS_NONFINITE:
+        raise ValueError(f"{what}: the batch or the centres hold an inf or a NaN")
+    return dict(route="filter" if code == 0 else "exact", candidates=cand, capacity=cap, overflow=code == 2, tiles_refiltered=tiles)
+
+
+def kmeans_assign_device(X: torch.Tensor, C: torch.Tensor, *, farthest: bool = False, route: str = "auto",
+                         info: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """saev_kmeans_assign without a read-back: (dist2, indices, info), ``info`` the four int32 words of the C entry on the device
+    (written into the caller's tensor if one is given).  When word 0 reads KMEANS_NONFINITE every index is -1, which
+    kmeans_group ignores, so a step built on this call touches no state before its one read-back can raise."""
+    if route not in _COHERENCE_ROUTES:
+        raise ValueError(f"route must be one of {sorted(_COHERENCE_ROUTES)}, got {route!r}")
+    X, C = _kmeans_matrix("kmeans_assign", X), _kmeans_matrix("kmeans_assign", C)
+    if X.shape[1] != C.shape[1]:
+        raise ValueError(f"kmeans_assign: X and C must share D, got {X.shape[1]} and {C.shape[1]}")
+    if X.device != C.device:
+        raise ValueError(f"kmeans_assign: X and C must share a device, got {X.device} and {C.device}")
+    (n, D), k = X.shape, C.shape[0]
+    ws, nbytes = _kmeans_workspace("kmeans_assign", n, k, D, X.device)
+    dist2 = torch.empty(n, device=X.device, dtype=torch.float32)
+    indices = torch.empty(n, device=X.device, dtype=torch.int32)
+    if info is None:
+        info = torch.empty(4, device=X.device, dtype=torch.int32)
+    with torch.cuda.device(X.device):
+        rc = _lib.load().saev_kmeans_assign(_ptr(X), n, _ptr(C), k, D, int(bool(farthest)), _COHERENCE_ROUTES[route], _ptr(ws), nbytes,
+                                            _ptr(dist2), _ptr(indices), _ptr(info), _stream())
+    if rc != 0:
+        raise _lib.SaevError(f"saev_kmeans_assign failed (status {rc})")
+    return dist2, indices, info
+
+
+def kmeans_assign(X: torch.Tensor, C: torch.Tensor, *, farthest: bool = False, route: str = "auto") -> AssignResult:
+    """Nearest (``farthest``: farthest) centre of every row of X, ``torch.cdist(X, C).min(dim=1)`` squared, on the HIP kernels of
+    saev_kmeans_assign (include/saev_amd.h: K-MEANS): no n x k matrix, one small read-back.  ``dist2[i]`` is the fp32
+    difference-form sum of squares of the returned pair and ``indices[i]`` the smallest j attaining the optimum; both routes
+    give the same bits.  X: (n, D), C: (k, D), float32 on one HIP device, D % 4 == 0, D <= 4096.  An inf or a NaN in either
+    raises ValueError."""
+    dist2, indices, info = kmeans_assign_device(X, C, farthest=farthest, route=route)
+    return AssignResult(dist2=dist2, indices=indices, **_kmeans_info("kmeans_assign", info.cpu().tolist()))
+
+
+def kmeans_group(indices: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(counts (k,), starts (k + 1,), rows (n,)), int32 on the device: the rows of a batch grouped by their centre, ascending within
+    each centre -- a stable counting sort of ``indices`` (saev_kmeans_group).  Entries outside [0, k) are ignored."""
+    if indices.ndim != 1 or not indices.is_cuda or indices.dtype != torch.int32:
+        raise ValueError("kmeans_group takes a 1-D int32 device tensor")
+    n = indices.shape[0]
+    if not (1 <= n <= 2**20 and 1 <= k <= 2**20):
+        raise ValueError(f"kmeans_group: unsupported shape {(n, k)} (1 <= n, k <= 2**20)")
+    indices = indices.contiguous()
+    counts = torch.empty(k, device=indices.device, dtype=torch.int32)
+    starts = torch.empty(k + 1, device=indices.device, dtype=torch.int32)
+    rows = torch.empty(n, device=indices.device, dtype=torch.int32)
+    with torch.cuda.device(indices.device):
+        rc = _lib.load().saev_kmeans_group(_ptr(indices), n, k, _ptr(counts), _ptr(starts), _ptr(rows), _stream())
+    if rc != 0:
+        raise _lib.SaevError(f"saev_kmeans_group failed (status {rc})")
+    return counts, starts, rows
+
+
+def kmeans_update(X: torch.Tensor, starts: torch.Tensor, rows: torch.Tensor, centers: torch.Tensor, cluster_counts: torch.Tensor, *,
+                  repl_rows: torch.Tensor | None = None, dist2: torch.Tensor | None = None,
+                  out_inertia: torch.Tensor | None = None) -> torch.Tensor | None:
+    """The running-mean update of saev_kmeans_update, IN PLACE on ``centers`` (k, D) and ``cluster_counts`` (k,) float32: each
+    centre with rows in the batch becomes (c * prev + sums) / (prev + count), sums in ascending row order.  ``repl_rows`` (k,)
+    int32: >= 0 gives a centre without rows that one row with count 1.  With ``dist2`` the fp64 mean of it is returned as a
+    one-element float64 device tensor (``out_inertia`` if given), else None."""
+    X = _kmeans_matrix("kmeans_update", X)
+    n, D = X.shape
+    k = centers.shape[0]
+    if centers.ndim != 2 or centers.shape[1] != D or not centers.is_cuda or centers.dtype != torch.float32 or not centers.is_contiguous() \
+            or centers.data_ptr() % 16:
+        raise ValueError("kmeans_update: centers must be a contiguous, 16-byte aligned (k, D) float32 device matrix (it is updated in place)")
+    if cluster_counts.shape != (k,) or cluster_counts.dtype != torch.float32 or not cluster_counts.is_contiguous() \
+            or cluster_counts.device != X.device or centers.device != X.device:
+        raise ValueError("kmeans_update: cluster_counts must be a contiguous (k,) float32 tensor on the batch's device")
+    if not (1 <= n <= 2**20 and 1 <= k <= 2**20 and 4 <= D <= 4096 and D % 4 == 0):
+        raise ValueError(f"kmeans_update: unsupported shape {(n, k, D)} ({_KMEANS_LIMITS})")
+    for name, t, shape in (("starts", starts, (k + 1,)), ("rows", rows, (n,)), ("repl_rows", repl_rows, (k,))):
+        if t is not None and (t.shape != shape or t.dtype != torch.int32 or t.device != X.device or not t.is_contiguous()):
+            raise ValueError(f"kmeans_update: {name} must be a contiguous {shape} int32 tensor on the batch's device")
+    if dist2 is not None:
+        if dist2.shape != (n,) or dist2.dtype != torch.float32 or dist2.device != X.device or not dist2.is_contiguous():
+            raise ValueError("kmeans_update: dist2 must be a contiguous (n,) float32 tensor on the batch's device")
+        if out_inertia is None:
+            out_inertia = torch.empty(1, device=X.device, dtype=torch.float64)
+    with torch.cuda.device(X.device):
+        rc = _lib.load().saev_kmeans_update(_ptr(X), n, D, k, _ptr(starts), _ptr(rows), None if repl_rows is None else _ptr(repl_rows),
+                                            _ptr(centers), _ptr(cluster_counts), None if dist2 is None else _ptr(out_inertia),
+                                            None if dist2 is None else _ptr(dist2), _stream())
+    if rc != 0:
+        raise _lib.SaevError(f"saev_kmeans_update failed (status {rc})")
+    return out_inertia if dist2 is not None else None
+
+
+def kmeans_collapsed_device(C: torch.Tensor, cluster_counts: torch.Tensor, tol: float, *, route: str = "auto",
+                            info: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """saev_kmeans_collapsed without a read-back: (losers (k,) bool, info (4,) int32), both on the device."""
+    if route not in _COHERENCE_ROUTES:
+        raise ValueError(f"route must be one of {sorted(_COHERENCE_ROUTES)}, got {route!r}")
+    C = _kmeans_matrix("kmeans_collapsed", C)
+    k, D = C.shape
+    if cluster_counts.shape != (k,) or cluster_counts.dtype != torch.float32 or cluster_counts.device != C.device:
+        raise ValueError("kmeans_collapsed: cluster_counts must be a (k,) float32 tensor on the centres' device")
+    cluster_counts = cluster_counts.contiguous()
+    ws, nbytes = _kmeans_workspace("kmeans_collapsed", k, k, D, C.device)
+    losers = torch.empty(k, device=C.device, dtype=torch.uint8)
+    if info is None:
+        info = torch.empty(4, device=C.device, dtype=torch.int32)
+    with torch.cuda.device(C.device):
+        rc = _lib.load().saev_kmeans_collapsed(_ptr(C), k, D, float(tol), _ptr(cluster_counts), _COHERENCE_ROUTES[route], _ptr(ws),
+                                               nbytes, _ptr(losers), _ptr(info), _stream())
+    if rc != 0:
+        raise _lib.SaevError(f"saev_kmeans_collapsed failed (status {rc})")
+    return losers.view(torch.bool), info
+
+
+def kmeans_collapsed(C: torch.Tensor, cluster_counts: torch.Tensor, tol: float, *, route: str = "auto") -> CollapsedResult:
+    """The loser mask of the reference's collapsed-centre rule: for every pair i < j of centres closer than ``tol`` (the fp32
+    distance ``sqrt(r_ij)``), i if ``cluster_counts[i] <= cluster_counts[j]`` else j -- on the HIP kernels of
+    saev_kmeans_collapsed, no k x k matrix, one small read-back."""
+    losers, info = kmeans_collapsed_device(C, cluster_counts, tol, route=route)
+    return CollapsedResult(losers=losers, **_kmeans_info("kmeans_collapsed", info.cpu().tolist()))
+
+
 def row_norm_mean(W: torch.Tensor) -> float:
     """``W.norm(dim=1).mean()`` of an (S, D) float32 device matrix on the HIP kernels of saev_row_norm_mean (the log block's
     metrics/avg_decoder_row_norm): exact fp64 squares, each norm rounded once to fp32, every sum in a fixed order; one read-back
