@@ -4,7 +4,12 @@ Tolerance.  tol(D) = (D + 3) 2^-24, relative, on squared distances: one rounding
 per sum over non-negative terms.  Every dist2 lies within tol(D) of the fp64 row optimum, the fp64 value of the returned pair
 within 2 tol(D) of it, and the index equals the fp64 arg-optimum on the rows whose fp64 runner-up differs from the best by more than
 4 tol(D) times itself; a test that asserts equality for every row asserts that gap first.  Shapes are the smallest that reach each
-class of the 128 x 128 tile, of the 64-wide k stage and of the 64 x 64 exact tile."""
+class of the 128 x 128 tile, of the 64-wide k stage and of the 64 x 64 exact tile.
+
+Route.  Where the filter is expected to answer, the test says so: route == "filter", no overflow, and the number of candidates the
+device reports lies inside the bracket (sure, maybe) that the restated candidate rule gives for the same device tensors
+(kmeans_restatement.candidate_bracket; test_kmeans_host_cpu.py holds the same inputs below half the capacity on the CPU).  Without
+that, a filter that always fell back to the exact route would pass every comparison of the two routes."""
 
 import json
 
@@ -13,13 +18,14 @@ import pytest
 import scipy.sparse
 import torch
 
+import kmeans_cases as K
 import kmeans_restatement as R
 from conftest import GOLDEN
 
 pytestmark = [pytest.mark.gpu, pytest.mark.encoder_modes("f32")]
 
 DEV = "cuda:0"
-ASSIGN_SHAPES = [(1, 1, 4), (1, 300, 16), (300, 1, 16), (37, 129, 64), (129, 37, 68), (257, 1000, 128), (1000, 4097, 256), (300, 200, 4096)]
+ASSIGN_SHAPES = K.ASSIGN_SHAPES
 
 
 def tol(D):
@@ -57,15 +63,25 @@ def same_bits(a, b):
     return torch.equal(a.dist2.view(torch.int32), b.dist2.view(torch.int32)) and torch.equal(a.indices, b.indices)
 
 
+def check_filter(res, bracket, label=""):
+    """The filter answered, with a number of candidates inside the restated rule's bracket (assign and collapsed alike)."""
+    sure, maybe = bracket
+    print(f"{label}: route {res.route}, overflow {res.overflow}, candidates {res.candidates} in [{sure}, {maybe}] of {res.capacity}")
+    assert res.route == "filter" and not res.overflow
+    assert sure <= res.candidates <= maybe
+
+
 @pytest.mark.parametrize("n,k,D", ASSIGN_SHAPES)
 def test_assign_against_fp64_on_both_routes(n, k, D):
     from saev_amd.engine import kmeans_assign
 
-    g = torch.Generator().manual_seed(1000 * n + k + D)
-    X, C = torch.randn(n, D, generator=g).to(DEV), (torch.randn(k, D, generator=g) + 0.25).to(DEV)
+    X, C = (t.to(DEV) for t in K.gaussian(n, k, D))
+    brackets = R.candidate_brackets(X, C) if k > 1 else None
     for farthest in (False, True):
         auto = kmeans_assign(X, C, farthest=farthest)
         check_assign(auto, X, C, farthest, f"({n}, {k}, {D})")
+        if k > 1:
+            check_filter(auto, brackets[farthest], f"({n}, {k}, {D}) farthest={farthest}")
         exact = kmeans_assign(X, C, farthest=farthest, route="exact")
         assert exact.route == "exact" and not exact.overflow
         assert same_bits(auto, exact), "both routes return the same bits"
@@ -107,27 +123,26 @@ def test_assign_ties_go_to_the_smallest_index():
 def test_assign_identical_centres_overflow_to_the_exact_route():
     from saev_amd.engine import kmeans_assign
 
-    g = torch.Generator().manual_seed(9)
-    C = torch.randn(1, 32, generator=g).repeat(65, 1).to(DEV)
-    X = torch.randn(65, 32, generator=g).to(DEV)
+    X, C = (t.to(DEV) for t in K.identical_centres())
     res = kmeans_assign(X, C)
     assert res.overflow and res.route == "exact"
+    assert res.candidates > res.capacity, "overflow by count, not for want of a unit image"
     assert same_bits(res, kmeans_assign(X, C, route="exact"))
     assert res.indices.tolist() == [0] * 65
     check_assign(res, X, C, False, "identical centres")
 
 
 def test_assign_far_from_the_origin():
-    """Activations with a large mean: rows = 100 + 0.01 randn.  Correct whichever route it takes; the route and the candidates per
-    row are printed (the centring decides whether the filter is of any use here)."""
+    """Activations with a large mean: rows = 100 + 0.01 randn.  The centring on the mean of the centres is what lets the filter
+    answer here: it does, with the candidates the restated rule counts (about 1.03 per row)."""
     from saev_amd.engine import kmeans_assign
 
-    g = torch.Generator().manual_seed(11)
-    X = (100 + 0.01 * torch.randn(2000, 128, generator=g)).to(DEV)
-    C = (X[torch.randperm(2000, generator=g)[:300].to(DEV)] + 0.001 * torch.randn(300, 128, generator=g).to(DEV)).contiguous()
+    X, C = (t.to(DEV) for t in K.far_from_the_origin())
+    brackets = R.candidate_brackets(X, C)
     for farthest in (False, True):
         res = kmeans_assign(X, C, farthest=farthest)
         check_assign(res, X, C, farthest, "far from the origin")
+        check_filter(res, brackets[farthest], f"far from the origin farthest={farthest}")
         assert same_bits(res, kmeans_assign(X, C, farthest=farthest, route="exact"))
 
 
@@ -161,21 +176,37 @@ def _index_cases():
     yield "ragged", torch.randint(0, 40, (5000,), generator=g).to(torch.int32) ** 2 // 40, 40, 68
 
 
+def check_group(idx, k):
+    """counts, starts and the grouped rows against bincount, cumsum and a stable sort over the entries inside [0, k) -- the others
+    are ignored; (counts, starts, rows) of the device and the CPU's counts."""
+    from saev_amd.engine import kmeans_group
+
+    counts, starts, rows = kmeans_group(idx.to(DEV), k)
+    valid = torch.nonzero((idx >= 0) & (idx < k)).flatten()
+    want_counts = torch.bincount(idx[valid].long(), minlength=k)
+    assert torch.equal(counts.cpu().long(), want_counts)
+    assert torch.equal(starts.cpu().long(), torch.cat([torch.zeros(1, dtype=torch.long), want_counts.cumsum(0)]))
+    want_rows = valid[torch.sort(idx[valid].long(), stable=True).indices]
+    assert torch.equal(rows.cpu().long()[:valid.numel()], want_rows), "ascending within each centre"
+    assert torch.equal(rows[:valid.numel()], kmeans_group(idx.to(DEV), k)[2][:valid.numel()])
+    return counts, starts, rows, want_counts
+
+
 @pytest.mark.parametrize("name,idx,k,D", list(_index_cases()), ids=lambda v: v if isinstance(v, str) else None)
 def test_group_and_update_against_a_one_thread_index_add(name, idx, k, D):
-    from saev_amd.engine import kmeans_group, kmeans_update
+    check_group_and_update(name, idx, k, D)
+
+
+def check_group_and_update(name, idx, k, D):
+    from saev_amd.engine import kmeans_update
 
     n = idx.shape[0]
     g = torch.Generator().manual_seed(19 + k)
     X = torch.randn(n, D, generator=g) + 1
     centers = torch.randn(k, D, generator=g)
     prev = torch.randint(0, 4, (k,), generator=g).float() * torch.randint(1, 900, (k,), generator=g).float()  # zeros among them
-    counts, starts, rows = kmeans_group(idx.to(DEV), k)
-    want_counts = torch.bincount(idx.long(), minlength=k)
-    assert torch.equal(counts.cpu().long(), want_counts)
-    assert torch.equal(starts.cpu().long(), torch.cat([torch.zeros(1, dtype=torch.long), want_counts.cumsum(0)]))
-    assert torch.equal(rows.cpu().long(), torch.sort(idx.long(), stable=True).indices), "ascending within each centre"
-    assert torch.equal(rows, kmeans_group(idx.to(DEV), k)[2])
+    counts, starts, rows, want_counts = check_group(idx, k)
+    valid = (idx >= 0) & (idx < k)  # (the rows of the others contribute nothing)
 
     empty = torch.nonzero(want_counts == 0).flatten()
     repl = torch.full((k,), -1, dtype=torch.int32)
@@ -184,7 +215,7 @@ def test_group_and_update_against_a_one_thread_index_add(name, idx, k, D):
     threads = torch.get_num_threads()
     torch.set_num_threads(1)  # index_add_ on the CPU: one thread, one order
     try:
-        sums = torch.zeros(k, D).index_add_(0, idx.long(), X)
+        sums = torch.zeros(k, D).index_add_(0, idx[valid].long(), X[valid])
     finally:
         torch.set_num_threads(threads)
     batch = want_counts.float()
@@ -211,22 +242,10 @@ def test_group_and_update_against_a_one_thread_index_add(name, idx, k, D):
         assert torch.equal(c2, c_dev) and torch.equal(again.view(torch.int64), inertia.view(torch.int64))
 
 
-def _planted(k, D, tol_, seed):
-    """Random centres far apart, with planted pairs at tol (1 -+ 1e-3) and at distance 0, equal and unequal counts on each side."""
-    g = torch.Generator().manual_seed(seed)
-    C = 5 * torch.randn(k, D, generator=g)
-    counts = torch.randint(1, 50, (k,), generator=g).float()
-    if k >= 20:
-        u = torch.randn(8, D, generator=g)
-        u /= u.norm(dim=1, keepdim=True)
-        for p, (i, j, scale, ci, cj) in enumerate([(0, 1, 1 - 1e-3, 5, 5), (2, k - 1, 1 + 1e-3, 5, 5), (3, 7, 1 - 1e-3, 9, 2), (4, 9, 1 - 1e-3, 2, 9),
-                                                  (5, 11, 0.0, 3, 3), (6, 13, 0.0, 4, 1), (8, 15, 1 + 1e-3, 1, 4), (k - 2, 17, 1 - 1e-3, 0, 0)]):
-            C[j] = C[i] + u[p] * (tol_ * scale)
-            counts[i], counts[j] = ci, cj
-    return C, counts
+_planted = K.planted
 
 
-@pytest.mark.parametrize("k,D", [(1, 16), (129, 16), (129, 68), (1000, 68), (1000, 1024)])
+@pytest.mark.parametrize("k,D", K.COLLAPSED_SHAPES)
 def test_collapsed_against_fp64(k, D):
     from saev_amd.engine import kmeans_collapsed
 
@@ -251,6 +270,8 @@ def test_collapsed_against_fp64(k, D):
     assert auto.losers.dtype == torch.bool and exact.route == "exact"
     if k == 1:
         assert not auto.losers.any() and auto.route == "exact" and not auto.overflow
+    else:
+        check_filter(auto, R.collapsed_bracket(C.to(DEV), tol_), f"collapsed ({k}, {D})")
 
 
 def test_collapsed_identical_centres_overflow():

@@ -1,7 +1,11 @@
 """Host-side checks of the k-means baseline (include/saev_amd.h: K-MEANS; saev_amd/baselines.py) that need no GPU: the entries are
 declared, exported and bound with the header's types and refuse bad arguments before touching a device; the numpy restatement
 of the step's contract reproduces both G24 trajectories of the reference bit for bit; the reference's own checkpoint file loads
-on the CPU and ``dump`` writes the same format; the configs take the reference's field names; PCA and Semi-NMF raise."""
+on the CPU and ``dump`` writes the same format; the configs take the reference's field names; PCA and Semi-NMF raise.
+
+The last block runs the restated candidate rule of the fp16 filter (kmeans_restatement.filter_values / candidate_bracket) on the
+CPU: its bound E holds against the refined value for every pair of every input family the GPU tests use, and those inputs
+(kmeans_cases, same functions, same seeds) meet the conditions the GPU tests take for granted."""
 
 import ctypes as C
 import dataclasses
@@ -14,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import kmeans_cases as K
 import kmeans_restatement as R
 from conftest import GOLDEN, ROOT
 from saev_amd import baselines, disk
@@ -199,3 +204,140 @@ def test_draw_is_the_one_source_of_randomness(monkeypatch):
     centers, _ = m._initial_centers(torch.arange(8.0).reshape(2, 4))  # fewer rows than k: repeated, no draw
     assert len(seen) == 1 and torch.equal(centers[2], centers[0])
     assert m.cluster_centers_ is None and m.n_features_in_ is None, "seeding alone commits nothing"
+
+
+# ---- the restated candidate rule ------------------------------------------------------------------------------
+def _slices(make, n, k, scale=1.0):
+    X, C = make()
+    return X[:n] * scale, C[:k] * scale
+
+
+def _collapsed_pair(k, D):
+    C = K.collapsed_case(k, D)[0]
+    return C, C
+
+
+# every input family of the GPU tests at a few hundred rows (slices of the same tensors where the function has one size)
+BOUND_FAMILIES = {
+    "gaussian D=68": lambda: K.gaussian(129, 37, 68),
+    "gaussian D=128": lambda: K.gaussian(257, 300, 128),
+    "gaussian D=4096": lambda: K.gaussian(60, 50, 4096),
+    "grid D=16": lambda: K.gaussian(300, 300, 16),
+    "far from the origin": lambda: K.far_from_the_origin(400, 100),
+    "identical centres": K.identical_centres,
+    "three centres": lambda: K.three_centres(3000),
+    "many centres": lambda: K.many_centres(5000),
+    "tied tiles": lambda: (K.tied_tiles()[0], K.tied_tiles()[1][350:650]),
+    "mixed norms 10^U(-1, 1)": lambda: _slices(lambda: K.mixed_norms(1), 300, 400),
+    "mixed norms 10^U(-3, 3)": lambda: _slices(lambda: K.mixed_norms(3), 300, 400),
+    "scaled by 2^-40": lambda: _slices(lambda: K.gaussian(*K.SCALED_SHAPE), 200, 300, K.SCALES[0]),
+    "scaled by 2^50": lambda: _slices(lambda: K.gaussian(*K.SCALED_SHAPE), 200, 300, K.SCALES[1]),
+    "no image: a row of X": K.no_image_row_of_x,
+    "no image: a centre": K.no_image_centre,
+    "collapsed (129, 16)": lambda: _collapsed_pair(129, 16),
+    "collapsed (129, 68)": lambda: _collapsed_pair(129, 68),
+}
+
+
+def _bound_ratio(X, C):
+    """max |s~ - r| / E over the pairs whose rows both have a unit image, r the refined value bit for bit."""
+    st, E = R.filter_values(X, C)
+    r = torch.from_numpy(R.r_fp32(X.numpy(), C.numpy())).double()
+    mu = R.centring_vector(C)
+    live = R.filter_rows(X, mu).has_image[:, None] & R.filter_rows(C, mu).has_image[None, :]
+    assert bool(torch.isfinite(E[live]).all()) and bool((E[live] > 0).all())
+    return ((st - r).abs() / E)[live].max().item(), int(live.sum())
+
+
+@pytest.mark.parametrize("name", list(BOUND_FAMILIES))
+def test_the_restated_bound_holds_against_the_refined_value(name):
+    ratio, pairs = _bound_ratio(*BOUND_FAMILIES[name]())
+    print(f"{name}: max |s~ - r| / E = {ratio:.3f} over {pairs} pairs")
+    assert ratio <= 1.0
+
+
+def test_the_bound_test_fails_with_a_quarter_of_E():
+    """The sensitivity of the test above: with E divided by 4 it fails on Gaussian rows at D = 68 (largest ratio 0.26), and at D = 4
+    with E divided by 1.2 (0.88: few columns leave the Cauchy-Schwarz step of the bound little slack), so a constant of the bound that
+    is too small by such a factor cannot hide in it."""
+    assert 0.25 < _bound_ratio(*K.gaussian(129, 37, 68))[0] <= 1.0
+    assert 1 / 1.2 < _bound_ratio(*K.three_centres(3000))[0] <= 1.0
+
+
+def _scaled(s):
+    X, C = K.gaussian(*K.SCALED_SHAPE)
+    return X * s, C * s
+
+
+# every GPU assign test that asserts route == "filter" (in both directions): the same function, the same seed
+FILTER_CASES = {f"gaussian ({n}, {k}, {D})": (lambda n=n, k=k, D=D: K.gaussian(n, k, D)) for n, k, D in K.ASSIGN_SHAPES if k > 1}
+FILTER_CASES.update({
+    "far from the origin": K.far_from_the_origin,
+    "grid": lambda: K.gaussian(*K.GRID),
+    "many centres": K.many_centres,
+    "tied tiles": K.tied_tiles,
+    "mixed norms 10^U(-1, 1)": lambda: K.mixed_norms(1),
+    "scaled by 2^-40": lambda: _scaled(K.SCALES[0]),
+    "scaled by 2^50": lambda: _scaled(K.SCALES[1]),
+})
+
+
+@pytest.mark.parametrize("name", list(FILTER_CASES))
+def test_the_filter_can_answer_the_inputs_the_gpu_tests_expect_it_to(name):
+    X, C = FILTER_CASES[name]()
+    n, cap = X.shape[0], K.assign_capacity(X.shape[0], C.shape[0])
+    for farthest, (sure, maybe) in R.candidate_brackets(X, C).items():
+        print(f"{name} farthest={farthest}: sure {sure} maybe {maybe} ({maybe / n:.3f} per row) of {cap}")
+        assert n <= sure <= maybe <= cap // 2
+        if name == "tied tiles":
+            assert sure >= 2 * n, "every optimum and its exact copy"
+
+
+def test_the_largest_n_case_meets_its_conditions():
+    """n = 2^20 from a 2^17-row sample of the same distribution: the candidates per row stay below half the capacity per row
+    (capacity = n k = 3 n here), and the whole input has more candidates than the refinement has threads."""
+    X, C = K.three_centres(2 ** 17)
+    for farthest, (sure, maybe) in R.candidate_brackets(X, C).items():
+        print(f"three centres, 2^17 rows, farthest={farthest}: sure {sure} maybe {maybe} ({maybe / 2 ** 17:.4f} per row)")
+        assert 2 ** 17 <= sure <= maybe and 8 * maybe <= K.assign_capacity(2 ** 20, 3) // 2
+    r = R.r_fp32(X[:2000].numpy(), C.numpy())
+    assert np.array_equal(r[:, 0], r[:, 1]), "the first 2 000 rows tie centres 0 and 1 bit for bit"
+    sure = R.candidate_bracket(X[:2000], C, False)[0]
+    assert sure >= 2000 + int((r[:, 0] <= r[:, 2]).sum())
+    # every row keeps its optimum, the tied rows whose optimum is the tie keep both: 2^20 + these > 4 096 x 256 threads
+    assert 2 ** 20 + int((r[:, 0] <= r[:, 2]).sum()) > 4096 * 256
+    assert bool((X.abs() < 8).all())
+
+
+@pytest.mark.parametrize("k,D", [kd for kd in K.COLLAPSED_SHAPES if kd[0] > 1] + [K.GRID[1:]])
+def test_the_collapsed_filter_can_answer_the_planted_centres(k, D):
+    C, _ = K.collapsed_case(k, D)
+    sure, maybe = R.collapsed_bracket(C, K.COLLAPSED_TOL)
+    print(f"collapsed ({k}, {D}): sure {sure} maybe {maybe} of {K.collapsed_capacity(k)}")
+    assert 6 <= sure <= maybe <= K.collapsed_capacity(k) // 2  # (the six planted pairs below tol are candidates)
+
+
+def test_the_overflow_cases_overflow_by_count_and_the_no_image_cases_by_a_zero_row():
+    X, C = K.identical_centres()
+    assert R.candidate_bracket(X, C, False)[0] > K.assign_capacity(65, 65)
+    C300 = torch.randn(1, 68, generator=torch.Generator().manual_seed(29)).repeat(300, 1)
+    assert R.collapsed_bracket(C300, 0.5)[0] > K.collapsed_capacity(300)
+    assert R.candidate_bracket(*K.mixed_norms(3), False)[0] > K.assign_capacity(1000, 3000)
+
+    X, C = K.no_image_row_of_x()
+    mu = R.centring_vector(C)
+    x, c = R.filter_rows(X, mu), R.filter_rows(C, mu)
+    assert torch.equal(mu.double(), C.double().mean(dim=0)) and bool(c.has_image.all())
+    assert (~x.has_image).nonzero().flatten().tolist() == [K.NO_IMAGE_ROW] and bool((X[K.NO_IMAGE_ROW] == mu).all())
+    X, C = K.no_image_centre()
+    mu = R.centring_vector(C)
+    x, c = R.filter_rows(X, mu), R.filter_rows(C, mu)
+    assert torch.equal(mu, C[64]) and bool(x.has_image.all()) and (~c.has_image).nonzero().flatten().tolist() == [64]
+
+
+def test_group_edges_has_the_segments_it_names():
+    idx, k = K.group_edges()
+    valid = (idx >= 0) & (idx < k)
+    assert torch.bincount(idx[valid].long(), minlength=k).tolist() == [4096, 4097, 2, 1, 0]
+    assert idx.numel() % 4096 != 0 and int((~valid).sum()) == 300 and {-1, k, 2 ** 31 - 1} <= set(idx[~valid].tolist())
+    assert idx[:64].unique().numel() > 1, "interleaved"
