@@ -1,6 +1,6 @@
 """The per-latent logistic probes on the MI355X (include/saev_amd.h: PROBE1D): prepare, the event sums, one solver
 iteration, evaluate, the whole fit and worker_fn against the fp64 numpy restatement of the contract (tests/probe1d_restatement.py,
-itself held against the reference's recorded results on the CPU) and against fixture G23, recorded from the reference.
+itself held against the reference's recorded results on the CPU) and against fixtures G23 and G25, recorded from the reference.
 
 Bands.  Event sums: every term is formed in fp64 from exp, log1p and one division -- a dozen roundings of 2^-53 each -- and the sums
 add them in a fixed order, so a sum may differ from the restatement's by about 1e-15 of the sum of the terms' magnitudes; the band
@@ -17,10 +17,10 @@ import torch
 
 import probe1d_restatement as R
 from conftest import GOLDEN
+from probe1d_cases import CASES, CHUNK, make_design, make_labels
+from probe1d_cases import coefficients as _coefficients
 
 pytestmark = [pytest.mark.gpu, pytest.mark.encoder_modes("f32")]
-
-CHUNK = 512
 
 
 def _engine():
@@ -28,48 +28,6 @@ def _engine():
 
     assert engine.Probe1D.CHUNK == CHUNK
     return engine
-
-
-def make_design(n, s, seed, *, full=False, specials=True):
-    """A CSR matrix with signed values, one stored 0.0, and -- where they fit -- latents with 0, 1, CHUNK - 1, CHUNK, CHUNK + 1 and (full)
-    n entries; without `full` some rows hold no entry at all."""
-    rng = np.random.default_rng(seed)
-    counts = rng.integers(0, min(n, 40) + 1, size=s)
-    wanted = [0, 1, CHUNK - 1, CHUNK, CHUNK + 1] + ([n] if full else [])
-    if specials:
-        for j, k in enumerate(k for k in wanted if k <= n):
-            if j < s:
-                counts[j] = k
-    if full and s < 6:
-        counts[s - 1] = n
-    free_rows = np.arange(n) if full or n < 8 else np.setdiff1d(np.arange(n), np.arange(3, n, 17))  # rows 3, 20, ... stay empty
-    rows, cols = [], []
-    for j in range(s):
-        k = min(int(counts[j]), free_rows.size) if counts[j] < n else n
-        r = np.arange(n) if k == n else rng.choice(free_rows, size=k, replace=False)
-        rows.append(r)
-        cols.append(np.full(k, j))
-    rows, cols = np.concatenate(rows), np.concatenate(cols)
-    vals = rng.standard_normal(rows.size).astype(np.float32) * 1.5
-    if vals.size:
-        vals[rng.integers(vals.size)] = 0.0
-    order = np.lexsort((cols, rows))
-    rows, cols, vals = rows[order], cols[order], vals[order]
-    indptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int64)
-    return indptr, cols.astype(np.int32), vals
-
-
-def make_labels(n, c, seed):
-    rng = np.random.default_rng(seed + 1000)
-    ids = rng.integers(0, c, size=n)
-    if c > 2 and n > c:
-        ids[ids == c - 2] = 0  # a class that never occurs
-    return ids.astype(np.uint8 if c <= 256 else np.int32)
-
-
-# every C of the contract's dispatch (1, <= 8, <= 16, <= 32, one group, several groups, a ragged last word) on the three sizes
-CASES = [(1, 1, 1, False), (257, 48, 11, False), (257, 1, 32, True), (257, 48, 33, False), (5000, 1031, 64, True), (5000, 48, 65, False),
-         (5000, 1031, 151, True), (5000, 1031, 256, False), (1, 48, 11, True)]
 
 
 class Case:
@@ -141,16 +99,6 @@ def test_prepare_reports_bad_labels_and_columns_from_the_device(cases):
         engine.Probe1D(k.n, k.s, k.c, k.data.size, "cuda").prepare(k.csr[0], cols, k.csr[2], labels=torch.from_numpy(k.ids).cuda())
     with pytest.raises(ValueError, match="one of the two"):
         engine.Probe1D(k.n, k.s, k.c, k.data.size, "cuda").prepare(*k.csr)
-
-
-def _coefficients(s, c, seed):
-    """(b, w) with ordinary pairs, logits beyond +-40 and products w v beyond +-800."""
-    rng = np.random.default_rng(seed)
-    b, w = rng.normal(0, 2, size=(s, c)), rng.normal(0, 1, size=(s, c))
-    far = rng.random((s, c))
-    b = np.where(far < 0.05, 45.0, np.where(far < 0.10, -45.0, b))
-    w = np.where((far > 0.10) & (far < 0.15), 900.0, np.where((far > 0.15) & (far < 0.20), -900.0, w))
-    return b, w
 
 
 @pytest.mark.parametrize("i", range(len(CASES)), ids=[f"n{n}_s{s}_c{c}" for n, s, c, _ in CASES])
@@ -258,10 +206,10 @@ def test_update_takes_every_branch_as_the_restatement_does():
     assert (new["b"][-1] == 0).all() and (new["w"][-1] == 0).all() and (new["lam"][-1] == hp.lam_init).all()
 
 
-# ---- fixture G23 ------------------------------------------------------------------------------------------------------------------------
+# ---- fixtures G23 and G25 (the tags groups and wide) ------------------------------------------------------------------------------------------------------------------------
 
 def _g23(tag):
-    with np.load(GOLDEN / f"g23_probe1d_{tag}.npz") as z:
+    with np.load(GOLDEN / f"{'g25' if tag in ('groups', 'wide') else 'g23'}_probe1d_{tag}.npz") as z:
         return {k: z[k] for k in z.files}
 
 
@@ -277,7 +225,7 @@ def _probe(g, **kw):
                                                                   ("lam_grow", 0.0), ("delta_logit", 0.0))}, **kw)
 
 
-@pytest.mark.parametrize("tag", ["plain", "absent"])
+@pytest.mark.parametrize("tag", ["plain", "absent", "groups", "wide"])
 def test_evaluate_at_the_references_coefficients(tag):
     engine = _engine()
     g = _g23(tag)
@@ -314,7 +262,7 @@ def fits():
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["float32", "float64"])
-@pytest.mark.parametrize("tag", ["plain", "absent"])
+@pytest.mark.parametrize("tag", ["plain", "absent", "groups", "wide"])
 def test_fit_end_to_end_against_the_reference(fits, tag, dtype):
     """fit, then loss_matrix_with_aux, on the reference's recorded results (R64: dtype=float64, R32: its default float32):
     n_iter equal to R64's; every loss within loss_band = max |L_R32 - L_R64| of R64's; coefficient and intercept of every well-posed
@@ -351,7 +299,7 @@ def test_label_matrix_and_torch_csr_inputs_give_the_same_fit(fits):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("tag", ["plain", "absent"])
+@pytest.mark.parametrize("tag", ["plain", "absent", "groups", "wide"])
 def test_two_fits_and_a_polled_fit_give_identical_bits(tag):
     engine = _engine()
     g = _g23(tag)

@@ -1,7 +1,7 @@
 """CPU-only tests of the per-latent logistic probes (include/saev_amd.h: PROBE1D): the entries are declared,
 exported and bound with the header's types; the struct mirrors match what gcc makes of the header; every argument check refuses a
 call before anything touches a device; the Python surface refuses what the reference refuses; worker_fn returns 1 on every missing
-input; and the numpy restatement the GPU tests compare against (tests/probe1d_restatement.py) is held against fixture G23,
+input; and the numpy restatement the GPU tests compare against (tests/probe1d_restatement.py) is held against fixtures G23 and G25,
 recorded from the reference, under the rules the GPU end-to-end test applies to the kernels."""
 
 import ctypes as C
@@ -13,6 +13,7 @@ import pytest
 import scipy.sparse
 import torch
 
+import probe1d_cases as K
 import probe1d_restatement as R
 from conftest import GOLDEN, ROOT
 
@@ -20,7 +21,7 @@ ENTRIES = ("saev_probe1d_workspace_bytes", "saev_probe1d_layout_of", "saev_probe
            "saev_probe1d_update", "saev_probe1d_fit", "saev_probe1d_evaluate")
 CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
 INVALID, UNSUPPORTED = -1, -3
-FIXTURES = ("plain", "absent")
+FIXTURES = ("plain", "absent", "groups", "wide")
 
 
 def _lib():
@@ -262,7 +263,7 @@ def dataclasses_replace(cfg, **kw):
 
 
 def _g23(tag):
-    with np.load(GOLDEN / f"g23_probe1d_{tag}.npz") as z:
+    with np.load(GOLDEN / f"{'g25' if tag in ('groups', 'wide') else 'g23'}_probe1d_{tag}.npz") as z:
         return {k: z[k] for k in z.files}
 
 
@@ -284,6 +285,18 @@ def test_fixture_g23_holds_the_designs_the_tests_rely_on():
     assert a["r64_n_iter"][4:8].tolist() == [1] * 4 and a["r64_n_iter"].max() > 1  # that slab stops at once, the others run on
     for f in (g, a):
         assert f["min_gap"] >= 1e-9 and f["r64_coef"].dtype == np.float64 and f["r32_coef"].dtype == np.float32 and int(f["max_iter"]) == 30
+
+
+def test_fixture_g25_holds_the_designs_the_tests_rely_on():
+    g, w = _g23("groups"), _g23("wide")
+    assert (int(g["n_rows"]), int(g["n_classes"]), int(g["class_slab_size"])) == (600, 70, 32) and g["labels"].max() == 61
+    assert g["r64_n_iter"][64:].tolist() == [1] * 6 and g["r64_n_iter"][:64].min() > 1  # the last slab is absent and stops at once
+    assert (int(w["n_rows"]), int(w["n_classes"]), int(w["class_slab_size"])) == (600, 151, 8) and not np.isin(w["labels"], range(64, 72)).any()
+    assert w["r64_n_iter"][64:72].tolist() == [1] * 8 and np.delete(w["r64_n_iter"], range(64, 72)).min() > 1 and w["labels"].max() == 150
+    biggest = max((GOLDEN / f"g23_probe1d_{t}.npz").stat().st_size for t in ("plain", "absent"))
+    for f, name in ((g, "groups"), (w, "wide")):
+        assert f["min_gap"] >= 1e-9 and f["well_posed"].any() and f["r64_coef"].dtype == np.float64 and int(f["max_iter"]) == 30
+        assert (GOLDEN / f"g25_probe1d_{name}.npz").stat().st_size <= biggest
 
 
 @pytest.mark.parametrize("tag", FIXTURES)
@@ -319,3 +332,108 @@ def test_both_label_forms_restate_to_the_same_bits():
         np.testing.assert_array_equal(R.pack_bits(a), R.pack_bits(b))
         assert R.pack_bits(a).shape == (97, (c + 31) // 32)
         assert all((R.pack_bits(a)[i, ids[i] // 32] >> np.uint32(ids[i] % 32)) & 1 for i in range(97))
+
+
+# ---- the conditions the tests of test_gpu_probe1d_geometry.py rely on, checked on the very same arrays ---------------------------------------
+
+@pytest.mark.parametrize("name", list(K.PLACEMENT))
+def test_placement_designs_have_the_groups_per_part_they_are_named_for(name):
+    """From the library's own part count and p1_part_len restated here: a change of P1_PARTS or of the rule cannot quietly turn these
+    designs into ones with a single group of 64 per part."""
+    lib_mod, lib = _lib()
+    fn, groups, parts, ragged = K.PLACEMENT[name]
+    d = fn()
+    L = lib_mod.SaevProbe1DLayout()
+    assert lib.saev_probe1d_layout_of(d.n, d.s, d.c, d.nnz, C.byref(L)) == 0
+    per_part = -(-d.nnz // L.parts)
+    part_len = max(64, -(-per_part // 64) * 64)  # p1_part_len
+    assert L.parts == parts and part_len == 64 * groups and (L.parts, part_len) == K.parts_of(d.s, d.nnz)
+    assert -(-d.nnz // part_len) >= 2 and (not ragged or d.nnz % part_len != 0)
+    assert d.indptr[0] == 0 and d.indptr[-1] == d.nnz == d.indices.size and d.indptr.size == d.n + 1 and (d.data < 0).any()
+    per, row_len = np.bincount(d.indices, minlength=d.s), np.diff(d.indptr)
+    e = np.arange(d.nnz)
+    key = (e // part_len) * d.s + d.indices  # (part, latent)
+    in_first, in_later = key[e % part_len < 64], key[e % part_len >= 64]
+    if name != "long_rows":  # (there a part holds 128 different latents, each once)
+        assert np.intersect1d(in_first, in_later).size > 0  # a latent's cursor is advanced by one group and read by a later one
+    if name == "two_groups":
+        assert (d.n, d.s, d.c) == (2100, 300, 11) and 65537 <= d.nnz <= 70000 and set(row_len) == {31, 32}
+    if name == "four_groups":
+        stored = row_len > 0
+        assert (d.n, d.s, d.c) == (5000, 1031, 33) and 190000 <= d.nnz <= 210000
+        assert per[0] == stored.sum() and -(-per[0] // K.CHUNK) == 10 and per[1] == (stored & (np.arange(d.n) % 2 == 0)).sum() and per[2] == 0
+        assert not stored[0] and not stored[-1] and not stored[3::17].any() and stored.sum() == d.n - 2 - len(range(3, d.n, 17))
+        o = K.four_groups_other()
+        assert (o.n, o.s, o.c, o.nnz) == (d.n, d.s, d.c, d.nnz) and not np.array_equal(o.indices, d.indices) and not np.array_equal(o.ids, d.ids)
+    if name == "many_latents":
+        assert (d.n, d.s, d.c) == (3000, 131072, 1) and L.parts == (1 << 26) // d.s < -(-d.nnz // 64) and 95000 <= d.nnz <= 105000
+        assert (per == 0).mean() > 0.5 and per[-1] == 0 and d.s // 1024 == 128
+    if name == "one_latent_rows":
+        assert (d.n, d.s, d.c) == (70000, 5, 1) and d.nnz == d.n and (d.indices == 3).all() and (row_len == 1).all()
+    if name == "long_rows":
+        assert (d.n, d.s) == (40, 2048) and d.nnz == 81920 and (row_len == d.s).all() and (d.indices.reshape(d.n, d.s) == np.arange(d.s)).all()
+        assert d.s // 64 == 32 and part_len < d.s
+
+
+@pytest.mark.parametrize("c", K.LABEL_CLASSES)
+def test_label_designs_hold_the_classes_the_tests_name(c):
+    d = K.label_design(c)
+    assert (d.n, d.s) == (5000, 8) and d.ids.dtype == np.int64 and d.ids.min() == 0 and d.ids.max() == c - 1 and not (d.ids == c - 3).any()
+    assert np.bincount(d.indices, minlength=d.s).tolist() == list(K.LABEL_COUNTS) and d.nnz * c * 8 < 100 << 20  # (a term of the numpy sums)
+    assert all(d.ymat[:, k].sum() >= 30 for k in K.ALONE_CLASSES if k < c)
+    assert c <= 4096 and K.LABEL_CLASSES[-1] == 4096  # 4 097 is refused: test_python_entries_refuse_bad_arguments
+
+
+@pytest.mark.parametrize("pair", list(K.FIT_PAIRS), ids=[f"c{c}_slab{s}" for c, s in K.FIT_PAIRS])
+def test_fit_designs_stop_slab_by_slab_ten_times_clear_of_tol(pair):
+    """What test_gpu_probe1d_geometry.py takes for granted of a fit design, by the restatement: slabs stop at different iterations
+    (in C = 151 and 130 a whole 64-class group before another), one is still running at max_iter, and at every decision the slab's
+    largest scaled gradient is 10 x away from tol -- below it at the stopping iteration, above it at every one before and, for a
+    slab left running, through max_iter.  The factor is a condition on these inputs, not a tolerance on any kernel."""
+    c, slab = pair
+    d, hp = K.fit_design(c, slab), K.fit_hyper(c, slab)
+    b, w, n_iter, gmax, done = K.fit_trace(d, hp)
+    rb, rw, rn, _ = R.fit(*d.csr, d.s, d.ymat, d.c, hp)  # the trace is the restatement's fit
+    np.testing.assert_array_equal(b.view(np.uint64), rb.view(np.uint64))
+    np.testing.assert_array_equal(w.view(np.uint64), rw.view(np.uint64))
+    np.testing.assert_array_equal(n_iter, rn)
+    per = np.bincount(d.indices, minlength=d.s)
+    assert (d.n, d.s) == (600, 24) and per[0] == 0 and per[1] == d.n > K.CHUNK and per[2:].min() >= 30 and (d.data < 0).any()
+    slabs = K.slabs_of(c, slab)
+    stops = []
+    for i, (c0, c1) in enumerate(slabs):
+        assert (n_iter[c0:c1] == n_iter[c0]).all()
+        k = int(n_iter[c0])
+        stops.append(k if done[i] else None)
+        ran = gmax[:k, i]
+        assert np.isfinite(ran).all() and np.isnan(gmax[k:, i]).all()
+        if done[i]:
+            assert ran[-1] <= hp.tol / 10 and (ran[:-1] >= 10 * hp.tol).all(), (i, ran)
+        else:
+            assert k == hp.max_iter and (ran >= 10 * hp.tol).all(), (i, ran)
+    print(pair, "stopping iterations per slab (None: running at max_iter):", stops)
+    stopped = {k for k in stops if k is not None}
+    if len(slabs) == 1:
+        assert stops == ([None] if c == 8 else [hp.max_iter])
+    else:
+        assert len(stopped) >= 2 and None in stops and stops[1] == 1 and max(stopped) > 1
+    if pair in ((151, 8), (130, 64)):
+        group = [[k for k, (c0, c1) in zip(stops, slabs) if c0 < 64 * g + 64 and c1 > 64 * g] for g in range(-(-c // 64))]
+        ends = [None if None in ks else max(ks) for ks in group]
+        assert ends[1] == 1 and ends[0] is not None and ends[0] > 1 and ends[2] is None  # the second group's waves return early from iteration 2 on
+    if pair in K.POLLED:
+        assert hp.max_iter % 3 != 0 and hp.max_iter > 3
+
+
+def test_evaluate_inputs_keep_every_probability_off_the_thresholds():
+    """The counts of evaluate can only be compared exactly when no event's and no zero row's probability sits on a threshold:
+    at least 1e-9 away for every (case, threshold) of test_gpu_probe1d_geometry.py, as the fixtures' min_gap."""
+    gaps = {}
+    for i in range(len(K.CASES)):
+        d = K.case_design(i)
+        gaps[K.CASE_IDS[i]] = K.threshold_gap(d, *K.coefficients(d.s, d.c, K.EVAL_SEED + i))
+    d = K.four_groups()
+    gaps["four_groups"] = K.threshold_gap(d, *K.coefficients(d.s, d.c, K.EVAL_SEED - 1))
+    print(gaps)
+    assert all(g >= 1e-9 for g in gaps.values()), gaps
+    assert K.THRESHOLDS == (0.2, 0.5, 0.9)

@@ -1,4 +1,4 @@
-"""Generate the probe1d golden vectors (G23) by RUNNING the upstream reference on the CPU (build container only).
+"""Generate the probe1d golden vectors (G23, G25) by RUNNING the upstream reference on the CPU (build container only).
 
 Test infrastructure beside ``oracle/`` (it uses ``oracle/_refshim.py`` to import the reference's
 ``contrib/trait_discovery/src/tdiscovery/probe1d.py`` unchanged and changes nothing there).  The reference is read from its own
@@ -9,6 +9,11 @@ location at generation time only; the outputs are data under ``tests/golden/``:
                        values and an explicitly stored 0.0
   g23_probe1d_absent   600 x 40 x 12 with classes 4-7 never occurring, class_slab_size 4: that slab stops at iteration 1 while the
                        others run to 30
+  g25_probe1d_groups   600 x 12 x 70, class_slab_size 32 (slabs of 32, 32 and 6 classes: the last one inside the second 64-class group
+                       of the events kernel), classes 62-69 never occurring: the eight fill the last slab, which stops at iteration 1,
+                       and the end of the second
+  g25_probe1d_wide     600 x 8 x 151, class_slab_size 8 (19 slabs over three class groups), classes 64-71 never occurring: that slab
+                       stops at iteration 1.  (The latents of both G25 designs are few so that each file stays below the G23 ones.)
 
 Each holds the CSR, the class ids, the hyper-parameters; the reference's results with dtype=float64 (r64_*) and with its default
 float32 (r32_*): coef, intercept, n_iter, qx and the five matrices of loss_matrix_with_aux; and the bands the tests use:
@@ -21,7 +26,7 @@ float32 (r32_*): coef, intercept, n_iter, qx and the five matrices of loss_matri
 A seed is also rejected when R32 leaves more than 0.5 % of all pairs outside coef_band, or when the numpy restatement of the
 contract (tests/probe1d_restatement.py) does not reproduce R64's n_iter.
 
-    python tools/gen_golden_probe1d.py
+    python tools/gen_golden_probe1d.py [g23_probe1d_plain ...]     (no name: all four)
 """
 
 import pathlib
@@ -100,7 +105,7 @@ def distance(a, b):
     return np.abs(a.astype(np.float64) - b) / (1 + np.abs(b))
 
 
-def fixture(ref, tag, n_latents, n_classes, present, slab, special, seeds):
+def fixture(ref, name, n_latents, n_classes, present, slab, special, seeds):
     for seed in seeds:
         csr, ids = design(seed, n_latents, n_classes, present, special)
         r64 = run_reference(ref, csr, ids, n_classes, slab, torch.float64)
@@ -112,31 +117,43 @@ def fixture(ref, tag, n_latents, n_classes, present, slab, special, seeds):
         pos_ev = R._segment_sums(ymat[rows].astype(np.float64), starts)[0]
         well = (pos_ev >= 5) & (np.diff(starts)[:, None] - pos_ev >= 5)
         d32 = np.maximum(distance(r32["coef"], r64["coef"]), distance(r32["intercept"], r64["intercept"]))
+        if not well.any():
+            print(f"{name} seed {seed}: no well-posed pair")  # (nothing to take coef_band from: the next seed)
+            continue
         coef_band = 4.0 * float(d32[well].max())
         outside = float((d32 > coef_band).mean())
         loss_band = float(np.abs(r32["loss"].astype(np.float64) - r64["loss"].astype(np.float64)).max())
         hp = R.Hyper(class_slab_size=slab, **HYPER)
         own = R.fit(csr.indptr, csr.indices, csr.data, n_latents, ids, n_classes, hp)
-        print(f"{tag} seed {seed}: nnz {csr.nnz}, n_iter {r64['n_iter'].tolist()}, min gap {gap:.3g}, well-posed {int(well.sum())}/{well.size}, "
+        print(f"{name} seed {seed}: nnz {csr.nnz}, n_iter {r64['n_iter'].tolist()}, min gap {gap:.3g}, well-posed {int(well.sum())}/{well.size}, "
               f"coef_band {coef_band:.3g}, R32 outside {outside:.4f}, loss_band {loss_band:.3g}, restatement n_iter {own[2].tolist()}")
         if gap >= 1e-9 and outside <= 0.005 and (own[2] == r64["n_iter"]).all():
             break
     else:
-        raise RuntimeError(f"{tag}: no seed passes the generator's checks")
+        raise RuntimeError(f"{name}: no seed passes the generator's checks")
     out = dict(indptr=csr.indptr.astype(np.int64), indices=csr.indices.astype(np.int32), data=csr.data.astype(np.float32), labels=ids,
                n_rows=N, n_latents=n_latents, n_classes=n_classes, class_slab_size=slab, seed=seed, loss_band=loss_band, coef_band=coef_band,
                well_posed=well, min_gap=gap, **HYPER)
     out.update({f"r64_{k}": v for k, v in r64.items()})
     out.update({f"r32_{k}": v for k, v in r32.items()})
-    np.savez_compressed(GOLDEN / f"g23_probe1d_{tag}.npz", **out)
+    np.savez_compressed(GOLDEN / f"{name}.npz", **out)
 
 
-def main():
+# name -> n_latents, n_classes, the classes that occur, class_slab_size, the special latents of G23, the seeds to try
+FIXTURES = {
+    "g23_probe1d_plain": (48, 11, list(range(11)), 8, True, range(2300, 2340)),
+    "g23_probe1d_absent": (40, 12, [0, 1, 2, 3, 8, 9, 10, 11], 4, False, range(2400, 2440)),
+    "g25_probe1d_groups": (12, 70, list(range(62)), 32, False, range(2500, 2540)),
+    "g25_probe1d_wide": (8, 151, [k for k in range(151) if not 64 <= k < 72], 8, False, range(2600, 2640)),
+}
+
+
+def main(names):
     torch.set_num_threads(1)  # index_add_ on the CPU: one thread, one order
     ref = reference_module()
-    fixture(ref, "plain", 48, 11, list(range(11)), 8, True, range(2300, 2340))
-    fixture(ref, "absent", 40, 12, [0, 1, 2, 3, 8, 9, 10, 11], 4, False, range(2400, 2440))
+    for name in names or FIXTURES:
+        fixture(ref, name, *FIXTURES[name])
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])
