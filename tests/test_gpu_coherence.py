@@ -3,7 +3,11 @@ fp32 route) against an fp64 computation of max_{i<j} |<w_i, w_j>| / (||w_i|| ||w
 
 Tolerance: (D + 2) 2^-24 for an fp32 dot product of unit rows, plus 2 (D / 2 + 2) 2^-24 for the fp32 normalisation of the two
 rows (the norm's fp32 sum and the division).  The value must be within it of the fp64 max; the fp64 coherence of the pair
-returned within twice it (the pair's own error and the maximiser's)."""
+returned within twice it (the pair's own error and the maximiser's).
+
+On these inputs the fp16 images err by less than that tolerance, or the planted ties are equal in fp64: the pair returned never
+depends on the filter's bound here.  The inputs on which it does -- small D, planted pairs a few tol apart that the images
+misorder -- and the bracket of the candidate count live in test_gpu_dictionary_geometry.py."""
 
 import struct
 import types

@@ -7,7 +7,11 @@ fp64 score of the pair returned within twice it (the pair's own error and the ma
 is asserted only for rows whose fp64 gap between best and second best exceeds 4 tol(D): below that the fp32 order may
 legitimately differ.  A test that asserts equality for every row first asserts that gap for its inputs.
 
-The filter's tile is 128 rows of A x 128 rows of B with 64-wide k stages; the shapes are the smallest that reach each class."""
+The filter's tile is 128 rows of A x 128 rows of B with 64-wide k stages; the shapes are the smallest that reach each class.
+
+On these inputs the fp16 images err by less than tol(D), or the planted ties are equal in fp64: the index a row returns never
+depends on the filter's bound here.  The inputs on which it does -- small D, decoys a few tol apart that the images misorder --
+and the bracket of the candidate count live in test_gpu_dictionary_geometry.py."""
 
 import json
 import pathlib
