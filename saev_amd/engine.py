@@ -1343,8 +1343,8 @@ class SaeEngine:
         The momentum buffers are the W_dec / W_enc segments of ``adam_m``."""
         self._trains("muon_tail")
         cfg = (muon or MuonConfig()).c_struct()
-        self.adam_steps += 1
-        self._chk(self.lib.saev_muon_tail(self.ctx, lr, max_norm, grad_scale, self.adam_steps, C.byref(cfg), _stream()), "saev_muon_tail")
+        self._chk(self.lib.saev_muon_tail(self.ctx, lr, max_norm, grad_scale, self.adam_steps + 1, C.byref(cfg), _stream()), "saev_muon_tail")
+        self.adam_steps += 1  # (counted once the step is enqueued: a refused call -- d_model > d_sae -- is not an optimizer step)
 
     def train_step_muon(self, x: torch.Tensor, lr: float, max_norm: float = 1.0, muon: MuonConfig | None = None):
         """One optimizer step with Muon on the weight matrices: the phases, then ``muon_tail``."""
