@@ -820,6 +820,65 @@ int saev_probe1d_fit(int64_t N, int64_t S, int64_t C, int64_t nnz, const saev_pr
                      int32_t* n_iter_out, void* workspace, int64_t workspace_bytes, void* stream);
 int saev_probe1d_evaluate(int64_t N, int64_t S, int64_t C, int64_t nnz, const double* b, const double* w, double threshold, int32_t out_dtype,
                           void* loss, void* tp, void* fp, void* tn, void* fn, void* workspace, int64_t workspace_bytes, void* stream);
+/* LATENT AP (the concept audit of the reference's contrib/trait_discovery tdiscovery.classification: compute_ap_for_latent over every
+ * latent and class, what eval_worker_fn turns into audit_ap_s.npy and Yield@B), context-free: AP[j, c], the average precision of
+ * latent j's activation as a detector of class c over N rows, EXACT AND TIE-AWARE (McSherry and Najork 2008: the expectation over
+ * all orders of tied scores), for all S x C pairs in one call.
+ * x is CSR: row_ptr (N + 1 int64, absolute positions into indices / data, non-decreasing), indices (int32 in [0, S)), data (fp32),
+ * nnz = row_ptr[N] - row_ptr[0] given by the host.  1 <= N, S < 2^31, 0 <= nnz < 2^31, 1 <= C <= 4096 (else SAEV_UNSUPPORTED, and
+ * -1 from the workspace-size function).
+ * CLASSES, one class per row in one of two forms (none or both is SAEV_INVALID_ARG): class_i32 (N int32, -1 = the row belongs to no
+ * class; it is still ranked), or class_u8 (N bytes) with an optional remap (256 int32: byte -> column or -1; NULL = the identity).
+ * EVENT RULE: an event of latent j is a stored entry of column j with value != 0 -- +0.0 and -0.0 are NOT events (as in LATENT
+ * TOP-K, unlike PROBE1D); negative values and +-Inf are.  NaN, and more than one entry per (row, latent), are outside the contract.
+ * m_j = events of j.
+ * RANKING: latent j ranks all N rows by activation, descending; a row without an event has activation 0.  A TIE GROUP is a maximal
+ * set of rows of equal activation (fp32 ==).  The groups of a latent in order: its distinct positive values, descending; the ZERO
+ * GROUP of the Z_j = N - m_j rows without an event (if Z_j > 0); its distinct negative values, descending.  For group g: t = rows
+ * ranked before it, n = its size, r = its rows of class c, R = the sum of r over earlier groups.
+ *   term(g, c) = 0                                                                  if r = 0
+ *              = r (R + 1) / (t + 1)                                                if n = 1
+ *              = sum_{q = 0 .. n-1} ((r / n) (R + 1 + q a)) / (t + 1 + q)           if 2 <= n <= direct_max,  a = (r - 1) / (n - 1)
+ *              = (r / n) ((R + 1 - a (t + 1)) dH + a n)                             otherwise,  dH = H_{t+n} - H_t
+ * pos_c = rows of class c;  AP[j, c] = (sum over g of term(g, c)) / pos_c, 0 when pos_c = 0.
+ * dH (harmonic numbers) is never a difference of two table entries.  For t >= 32: dH = log1p(n / t) + corr with m = t + n and
+ *   corr = (((((-(m^-10 - t^-10) / 132 + (m^-8 - t^-8) / 240) - (m^-6 - t^-6) / 252) + (m^-4 - t^-4) / 120)
+ *            + n (t + m) (t^-2 m^-2) / 12) - n / (2 t m)),
+ * the powers built from 1 / t and 1 / m by squaring.  For t < 32: the terms 1 / p for p = min(t + n, 32) down to t + 1, added in
+ * that order, plus (when t + n > 32) the formula above at t = 32, n = t + n - 32.
+ * ARITHMETIC AND ORDER: everything is fp64, every operation rounded on its own (no contraction); counts are integers.  The sum of a
+ * pair starts at 0 and receives its non-zero terms one at a time in the group order above -- no blocking, no partial sums; the q
+ * loop of a small group runs from 0 upwards into a sum of its own that is then added as one term.  The order depends on the pair's
+ * own events only -- not on other latents or classes, C, the launch or timing: two calls give the same bits, a latent scored alone
+ * gives the bits it has among others, and so does a class.  Integer atomics only (digit counts, class counts, the error word).
+ * OUTPUTS (device): ap (S x C fp64), pos (C int64), best_ap (S fp64: the row maximum of ap) and best_class (S int32: the LOWEST
+ * column that attains it); best_* may be NULL.  err is int32[0] at off_err of the workspace: 0, or the largest SAEV_LATENT_AP_ERR_*
+ * met on the device (a class id outside [-1, C), a latent outside [0, S)); the caller reads it when it next synchronises, and the
+ * outputs are void if it is not 0.
+ * The call also leaves in the workspace (byte offsets, all multiples of 256: saev_latent_ap_layout_of) the stored entries sorted by
+ * (latent, value descending, row ascending), non-events last: key (nnz uint32: ~k(v), k the order-preserving image of the fp32
+ * value), latent (nnz uint32; S for a non-event), row (nnz int32), and starts (S + 1 int64: latent j's events are
+ * [starts[j], starts[j + 1]), starts[S] = the number of events).  The sort is a stable LSD radix sort of `passes` 8-bit passes over
+ * `parts` contiguous parts of part_len entries; key2 / latent2 / row2 and hist (the 256 x parts digit table and 256 totals) are its scratch.
+ * Arguments are checked before the device is touched; a refused call leaves its message with saev_last_error(NULL).  Nothing is
+ * allocated, nothing is read back and nothing synchronises.  workspace: saev_latent_ap_workspace_bytes(N, S, C, nnz) bytes of device
+ * memory, 256-byte aligned; its size depends on nnz and S only (24 bytes per stored entry, 8 per latent) -- never an N x S, N x C
+ * or nnz x C array. */
+#define SAEV_LATENT_AP_ERR_CLASS 1
+#define SAEV_LATENT_AP_ERR_LATENT 2
+typedef struct {               /* byte offsets into the workspace (all multiples of 256) */
+    int32_t struct_size;
+    int32_t direct_max;        /* tie groups of at most this many rows are summed term by term */
+    int64_t parts, part_len;   /* the sort's parts */
+    int64_t passes;            /* 4 over the value + as many as the bytes of S */
+    int64_t total_bytes;
+    int64_t off_err, off_starts, off_hist, off_key, off_latent, off_row, off_key2, off_latent2, off_row2;
+} saev_latent_ap_layout;
+int64_t saev_latent_ap_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t nnz);
+int saev_latent_ap_layout_of(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_latent_ap_layout* out);
+int saev_latent_ap(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+                   const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, double* ap, int64_t* pos, double* best_ap,
+                   int32_t* best_class, void* workspace, int64_t workspace_bytes, void* stream);
 /* PARAMETER OWNERSHIP.  With the f16r encoder the context keeps, from one call to the next, what its forward needs of W_enc
  * (fp16 operand images, a slice-major fp32 transpose, bias and norm shares: written by the Adam launch of saev_train_step, or by
  * the last forward that prepared them itself) and uses it for as long as only the library has written the parameter buffer.  A

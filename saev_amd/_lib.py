@@ -97,6 +97,14 @@ class SaevProbe1DLayout(C.Structure):
                                          "off_n_iter", "off_active")]
 
 
+class SaevLatentAPLayout(C.Structure):
+    """include/saev_amd.h: saev_latent_ap_layout (byte offsets into the workspace of saev_latent_ap)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("direct_max", C.c_int32)] + \
+               [(n, C.c_int64) for n in ("parts", "part_len", "passes", "total_bytes", "off_err", "off_starts", "off_hist", "off_key",
+                                         "off_latent", "off_row", "off_key2", "off_latent2", "off_row2")]
+
+
 ACT_TOPK, ACT_RELU, ACT_BATCHTOPK = 0, 1, 2
 ROW_OVERFLOW = -7  # saev_status SAEV_ROW_OVERFLOW
 BATCH_OVERWRITE = 1
@@ -201,6 +209,9 @@ _SIGNATURES = {
     "saev_probe1d_update": (C.c_int, [C.c_int64] * 4 + [C.POINTER(SaevProbe1DCfg), P, P, P, P, C.c_int64, P]),
     "saev_probe1d_fit": (C.c_int, [C.c_int64] * 4 + [C.POINTER(SaevProbe1DCfg), P, P, P, P, C.c_int64, P]),
     "saev_probe1d_evaluate": (C.c_int, [C.c_int64] * 4 + [P, P, C.c_double, C.c_int32, P, P, P, P, P, P, C.c_int64, P]),
+    "saev_latent_ap_workspace_bytes": (C.c_int64, [C.c_int64] * 4),
+    "saev_latent_ap_layout_of": (C.c_int, [C.c_int64] * 4 + [C.POINTER(SaevLatentAPLayout)]),
+    "saev_latent_ap": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, P, P, P, P, C.c_int64, P]),
     "saev_comm_unique_id": (C.c_int, [P]),
     "saev_comm_init": (C.c_int, [P, P, C.c_int32, C.c_int32]),
     "saev_comm_world": (C.c_int, [P]),

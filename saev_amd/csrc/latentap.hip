@@ -1,0 +1,453 @@
+// Exact tie-aware average precision of every latent against every class on sparse codes (include/saev_amd.h: LATENT AP;
+// DESIGN.md 3.19): AP[j, c] of latent j's activation as a detector of class c, the expectation over all orders of tied scores
+// (McSherry and Najork), with the latent's zero rows as ONE tie group in closed form.
+//
+//   sort     the stored entries by (latent, value descending, row ascending): a stable LSD radix sort, 8 bits a pass, four passes
+//            over the order-reversing 32-bit image of the value and one to four over the latent (as many bytes as S needs).  An
+//            entry that is no event (+-0.0, a latent outside [0, S)) gets the latent S and so ends up behind every event.  The
+//            entries are cut into up to LA_MAX_PARTS contiguous parts; per pass a wave per part counts its digits in LDS (integer
+//            atomics), a workgroup per digit scans its row of the (digit, part) table and leaves the digit's total, and a wave per part
+//            (its cursors: the smaller digits' totals plus its own row prefix) walks its entries in order, 64 at a time:
+//            the lanes of equal digit find each other with eight ballots, the rank inside the 64 is a population count and the
+//            base a cursor in LDS that only this wave touches -- stable whatever the timing.  The key is a total order (entries
+//            come in ascending row order), so the sorted arrays have one answer.  starts[j] is a lower bound in the sorted latents.
+//   terms    lane = class: a wave owns one latent and up to 64 classes and walks the latent's events in rank order, 64 loaded at a
+//            time and handed round by lane shuffles.  The value image and the row's class are the same in every lane; each lane
+//            keeps r (rows of its class in the running group), R (in earlier groups) and the pair's sum in registers.  When the
+//            value changes the group is closed: its term is added, R += r, t += n.  The zero group is put between the last
+//            positive and the first negative event; a latent with negative events is walked once before to count each pair's
+//            events (the zero group's r is pos_c minus that count).  A pair without events gets the zero group's term alone.
+//            Groups of at most LA_DIRECT_MAX rows are summed term by term, larger ones use the closed form with
+//            H_{t+n} - H_t from log1p and the differences of the asymptotic terms (la_dh).  No regrouping by class: no second
+//            sort, no array per (event, class), and a pair's sum is a plain left-to-right sum in group order.
+//   best     a wave per latent: the row maximum of ap and the lowest column that attains it.
+//
+// Integer atomics only (digit counts in LDS, class counts, the error word); nothing is read back, nothing synchronises.
+#include "common.h"
+#include "kernels.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace {
+
+constexpr int LA_H_SMALL = 32;        // below this t the first terms of H_{t+n} - H_t are added directly
+constexpr int LA_MAX_PARTS = 2048;
+constexpr int LA_SCAN_THREADS = 256;
+constexpr int LA_MAX_C = 4096;
+
+int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
+
+bool la_shape_ok(int64_t N, int64_t S, int64_t C, int64_t nnz) {
+    return N >= 1 && N <= 0x7fffffffLL && S >= 1 && S <= 0x7fffffffLL && C >= 1 && C <= LA_MAX_C && nnz >= 0 && nnz <= 0x7fffffffLL;
+}
+
+int la_latent_passes(int64_t S) { return S < (1 << 8) ? 1 : S < (1 << 16) ? 2 : S < (1 << 24) ? 3 : 4; }  // bytes that hold the value S
+
+void la_layout(int64_t S, int64_t C, int64_t nnz, saev_latent_ap_layout* L) {
+    std::memset(L, 0, sizeof *L);
+    L->struct_size = (int32_t)sizeof *L;
+    L->direct_max = LA_DIRECT_MAX;
+    L->parts = std::max<int64_t>(1, std::min<int64_t>(LA_MAX_PARTS, (nnz + 63) / 64));
+    L->part_len = std::max<int64_t>(64, ((nnz + L->parts - 1) / L->parts + 63) / 64 * 64);
+    L->passes = 4 + la_latent_passes(S);
+    int64_t at = 0;
+    const auto take = [&](int64_t bytes) { const int64_t o = at; at += round256(std::max<int64_t>(bytes, 1)); return o; };
+    L->off_err = take(64);
+    L->off_starts = take(8 * (S + 1));
+    L->off_hist = take(4 * 256 * (L->parts + 1));  // the (digit, part) table and the 256 digit totals behind it
+    L->off_key = take(4 * nnz);
+    L->off_latent = take(4 * nnz);
+    L->off_row = take(4 * nnz);
+    L->off_key2 = take(4 * nnz);
+    L->off_latent2 = take(4 * nnz);
+    L->off_row2 = take(4 * nnz);
+    L->total_bytes = at;
+    (void)C;
+}
+
+// ---------------------------------------------------------------- labels -----------------------------------------------------------------
+
+__device__ __forceinline__ int la_raw_class(const uint8_t* __restrict__ u8, const int32_t* __restrict__ remap, const int32_t* __restrict__ i32,
+                                            long row) {
+    if (u8 == nullptr) return i32[row];
+    const int b = (int)u8[row];
+    return remap ? remap[b] : b;
+}
+// the column of a row, -1 for a row without a class (or with an id the count pass has reported)
+__device__ __forceinline__ int la_class(const uint8_t* __restrict__ u8, const int32_t* __restrict__ remap, const int32_t* __restrict__ i32, long row,
+                                        int C) {
+    const int c = la_raw_class(u8, remap, i32, row);
+    return (c >= 0 && c < C) ? c : -1;
+}
+
+__global__ __launch_bounds__(256) void la_labels_kernel(const uint8_t* __restrict__ u8, const int32_t* __restrict__ remap,
+                                                        const int32_t* __restrict__ i32, int N, int C, unsigned long long* __restrict__ pos,
+                                                        int32_t* __restrict__ err) {
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= N) return;
+    const int c = la_raw_class(u8, remap, i32, r);
+    if (c < -1 || c >= C) { atomicMax(err, SAEV_LATENT_AP_ERR_CLASS); return; }
+    if (c >= 0) atomicAdd(pos + c, 1ull);
+}
+
+// ---------------------------------------------------------------- sort -------------------------------------------------------------------
+
+// ascending key = descending value: positive events below 0x7fffffff, negative ones above 0x80000000
+__device__ __forceinline__ uint32_t la_key(float v) { return ~f2ukey(v); }
+
+__global__ __launch_bounds__(256) void la_init_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ indices,
+                                                      const float* __restrict__ data, long nnz, int N, int S, uint32_t* __restrict__ key,
+                                                      uint32_t* __restrict__ latent, int32_t* __restrict__ row, int32_t* __restrict__ err) {
+    const int64_t p0 = row_ptr[0];
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (long)gridDim.x * 256) {
+        const int64_t p = p0 + e;
+        const int col = indices[p];
+        const float v = data[p];
+        const bool ok = col >= 0 && col < S;
+        if (!ok) atomicMax(err, SAEV_LATENT_AP_ERR_LATENT);
+        int lo = 0, hi = N;  // the row r with row_ptr[r] <= p < row_ptr[r + 1]
+        while (hi - lo > 1) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (row_ptr[mid] <= p) lo = mid; else hi = mid;
+        }
+        key[e] = la_key(v);
+        latent[e] = (ok && v != 0.f) ? (uint32_t)col : (uint32_t)S;
+        row[e] = lo;
+    }
+}
+
+// one wave per part: hist[digit][part] = entries of the part with that digit
+__global__ __launch_bounds__(64) void la_hist_kernel(const uint32_t* __restrict__ src, long nnz, long part_len, int shift, int parts,
+                                                     int32_t* __restrict__ hist) {
+    __shared__ int h[256];
+    const int lane = threadIdx.x;
+    const long part = blockIdx.x;
+    for (int d = lane; d < 256; d += 64) h[d] = 0;
+    __syncthreads();
+    const long first = part * part_len, last = min(first + part_len, nnz);
+    for (long e = first + lane; e < last; e += 64) atomicAdd(&h[(src[e] >> shift) & 255u], 1);
+    __syncthreads();
+    for (int d = lane; d < 256; d += 64) hist[(size_t)d * parts + part] = h[d];
+}
+
+// per digit (one workgroup each): hist[digit][.] -> the exclusive prefix over the parts, total[digit] = the row's sum.  A thread sums
+// a contiguous piece, the pieces are scanned, then placed
+__global__ __launch_bounds__(LA_SCAN_THREADS) void la_scan_kernel(int32_t* __restrict__ hist, int parts, int32_t* __restrict__ total) {
+    __shared__ int sw[LA_SCAN_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    int32_t* row = hist + (size_t)blockIdx.x * parts;
+    const int per = (parts + LA_SCAN_THREADS - 1) / LA_SCAN_THREADS;
+    const int lo = min(t * per, parts), hi = min(lo + per, parts);
+    int sum = 0;
+    for (int i = lo; i < hi; ++i) sum += row[i];
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += up;
+    }
+    if (lane == 63) sw[w] = inc;
+    __syncthreads();
+    int run = inc - sum;
+    for (int q = 0; q < w; ++q) run += sw[q];
+    for (int i = lo; i < hi; ++i) {
+        const int v = row[i];
+        row[i] = run;
+        run += v;
+    }
+    if (t == LA_SCAN_THREADS - 1) total[blockIdx.x] = run;
+}
+
+// one wave per part (see the head of the file); `by_latent` picks the array the digit is taken from
+__global__ __launch_bounds__(64) void la_scatter_kernel(const uint32_t* __restrict__ key_in, const uint32_t* __restrict__ lat_in,
+                                                        const int32_t* __restrict__ row_in, uint32_t* __restrict__ key_out,
+                                                        uint32_t* __restrict__ lat_out, int32_t* __restrict__ row_out, long nnz, long part_len,
+                                                        int shift, int by_latent, int parts, const int32_t* __restrict__ hist,
+                                                        const int32_t* __restrict__ total) {
+    __shared__ int cur[256];
+    const int lane = threadIdx.x;
+    const long part = blockIdx.x;
+    {  // cursor of digit d = the entries of smaller digits (an exclusive scan of total, four digits a lane) + those of d in earlier parts
+        int v[4], sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { v[k] = total[lane * 4 + k]; sum += v[k]; }
+        int inc = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += up;
+        }
+        int run = inc - sum;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { cur[lane * 4 + k] = run + hist[(size_t)(lane * 4 + k) * parts + part]; run += v[k]; }
+    }
+    __syncthreads();
+    const long first = part * part_len, last = min(first + part_len, nnz);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (long g = first; g < last; g += 64) {
+        const long e = g + lane;
+        const bool active = e < last;
+        uint32_t k = 0, l = 0;
+        int r = 0;
+        if (active) { k = key_in[e]; l = lat_in[e]; r = row_in[e]; }
+        const unsigned digit = ((by_latent ? l : k) >> shift) & 255u;
+        unsigned long long peers = __ballot(active);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = ((digit >> b) & 1u) != 0u;
+            const unsigned long long m = __ballot(active && bit);
+            peers &= bit ? m : ~m;
+        }
+        const int rank = __popcll(peers & below), same = __popcll(peers);
+        const int leader = __ffsll((long long)peers) - 1;
+        const int old = active ? cur[digit] : 0;
+        __syncthreads();
+        if (active && lane == leader) cur[digit] = old + same;
+        __syncthreads();
+        if (active) {
+            const long at = (long)old + rank;
+            if (at >= 0 && at < nnz) { key_out[at] = k; lat_out[at] = l; row_out[at] = r; }  // (always: the digits partition the entries)
+        }
+    }
+}
+
+// starts[l] = the first sorted entry whose latent is >= l, for l = 0 .. S (starts[S] = the number of events)
+__global__ __launch_bounds__(256) void la_starts_kernel(const uint32_t* __restrict__ latent, long nnz, int S, int64_t* __restrict__ starts) {
+    const long l = (long)blockIdx.x * 256 + threadIdx.x;
+    if (l > S) return;
+    long lo = 0, hi = nnz;  // the first position with latent[pos] >= l
+    while (lo < hi) {
+        const long mid = lo + ((hi - lo) >> 1);
+        if (latent[mid] < (uint32_t)l) lo = mid + 1; else hi = mid;
+    }
+    starts[l] = lo;
+}
+
+// ---------------------------------------------------------------- terms ------------------------------------------------------------------
+
+// H_{t+n} - H_t for t >= LA_H_SMALL, from H_m = ln m + gamma + 1/(2m) - 1/(12m^2) + 1/(120m^4) - 1/(252m^6) + 1/(240m^8) - 1/(132m^10):
+// the logarithms as log1p(n / t), the two leading corrections as exact differences, the rest (below 1e-8 of the result) subtracted
+__device__ __forceinline__ double la_dh_asym(double t, double n) {
+#pragma clang fp contract(off)
+    const double m = t + n;
+    const double it = 1.0 / t, im = 1.0 / m;
+    const double it2 = it * it, im2 = im * im, it4 = it2 * it2, im4 = im2 * im2;
+    double corr = -((im4 * im4) * im2 - (it4 * it4) * it2) / 132.0;
+    corr = corr + (im4 * im4 - it4 * it4) / 240.0;
+    corr = corr - (im4 * im2 - it4 * it2) / 252.0;
+    corr = corr + (im4 - it4) / 120.0;
+    corr = corr + (n * (t + m)) * (it2 * im2) / 12.0;
+    corr = corr - n / ((2.0 * t) * m);
+    return log1p(n / t) + corr;
+}
+
+// H_{t+n} - H_t, n >= 1: below LA_H_SMALL the terms 1 / p, p = min(t + n, LA_H_SMALL) down to t + 1, added in that order; the rest from
+// la_dh_asym(LA_H_SMALL, .), the two added last
+__device__ __forceinline__ double la_dh(long t, long n) {
+#pragma clang fp contract(off)
+    const long hi = t + n;
+    if (t >= LA_H_SMALL) return la_dh_asym((double)t, (double)n);
+    double direct = 0.0;
+    for (long p = min(hi, (long)LA_H_SMALL); p > t; --p) direct = direct + 1.0 / (double)p;
+    if (hi <= LA_H_SMALL) return direct;
+    return direct + la_dh_asym((double)LA_H_SMALL, (double)(hi - LA_H_SMALL));
+}
+
+// term(g, c) of include/saev_amd.h; dh = H_{t+n} - H_t (read when n > LA_DIRECT_MAX only)
+__device__ __forceinline__ double la_term(long t, long n, long R, long r, double dh) {
+#pragma clang fp contract(off)
+    if (r == 0) return 0.0;
+    if (n == 1) return (double)(r * (R + 1)) / (double)(t + 1);
+    const double rn = (double)r / (double)n;
+    const double a = (double)(r - 1) / (double)(n - 1);
+    const double R1 = (double)(R + 1);
+    if (n <= LA_DIRECT_MAX) {
+        double s = 0.0;
+        for (long q = 0; q < n; ++q) s = s + (rn * (R1 + (double)q * a)) / (double)(t + 1 + q);
+        return s;
+    }
+    return rn * ((R1 - a * (double)(t + 1)) * dh + a * (double)n);
+}
+
+struct LaTerms {
+    const int64_t* starts;
+    const uint32_t* key;
+    const int32_t* row;
+    const uint8_t* u8;
+    const int32_t* remap;
+    const int32_t* i32;
+    const unsigned long long* pos;
+    double* ap;
+    int N, S, C;
+};
+
+// a wave per (latent, 64 classes).  grid: (ceil(S / 4), ceil(C / 64))
+__global__ __launch_bounds__(256) void la_terms_kernel(LaTerms a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= a.S) return;
+    const int c = blockIdx.y * 64 + lane;
+    const bool active = c < a.C;
+    const int64_t s0 = a.starts[j], s1 = a.starts[j + 1];
+    const long Z = (long)a.N - (long)(s1 - s0);
+    const long posc = active ? (long)a.pos[c] : 0;
+
+    // with negative events the zero group sits inside the walk: count the pair's events first
+    const bool has_neg = s1 > s0 && a.key[s1 - 1] >= 0x80000000u;
+    long mine = 0;
+    if (has_neg) {
+        for (int64_t base = s0; base < s1; base += 64) {
+            const int64_t e = base + lane;
+            const int cl = e < s1 ? la_class(a.u8, a.remap, a.i32, a.row[e], a.C) : -1;
+            const int cnt = (int)min((int64_t)64, s1 - base);
+            for (int i = 0; i < cnt; ++i) {
+                const int ci = __shfl(cl, i, 64);  // (every lane takes part: lane i may belong to no class of this group)
+                mine += (active && ci == c) ? 1 : 0;
+            }
+        }
+    }
+
+    double acc = 0.0;
+    long t = 0, n = 0, R = 0, r = 0;
+    uint32_t curk = 0;
+    bool zero_done = false;
+    const auto close_group = [&]() {  // (n > 0)
+        const double dh = (n > LA_DIRECT_MAX && __any(r > 0)) ? la_dh(t, n) : 0.0;
+        if (r > 0) acc = acc + la_term(t, n, R, r, dh);
+        R += r;
+        t += n;
+        r = 0;
+        n = 0;
+    };
+    const auto zero_group = [&]() {
+        zero_done = true;
+        if (Z <= 0) return;
+        const long rz = min(max(posc - (has_neg ? mine : R), 0L), Z);
+        const double dh = (Z > LA_DIRECT_MAX && __any(rz > 0)) ? la_dh(t, Z) : 0.0;
+        if (rz > 0) acc = acc + la_term(t, Z, R, rz, dh);
+        R += rz;
+        t += Z;
+    };
+    for (int64_t base = s0; base < s1; base += 64) {
+        const int64_t e = base + lane;
+        uint32_t myk = 0;
+        int mycl = -1;
+        if (e < s1) { myk = a.key[e]; mycl = la_class(a.u8, a.remap, a.i32, a.row[e], a.C); }
+        const int cnt = (int)min((int64_t)64, s1 - base);
+        for (int i = 0; i < cnt; ++i) {
+            const uint32_t k = __shfl(myk, i, 64);
+            const int cl = __shfl(mycl, i, 64);
+            if (n > 0 && k != curk) close_group();
+            if (!zero_done && k >= 0x80000000u) zero_group();  // (a negative key differs from every positive one: the group is closed)
+            curk = k;
+            n += 1;
+            if (active && cl == c) r += 1;
+        }
+    }
+    if (n > 0) close_group();
+    if (!zero_done) zero_group();
+    if (active) a.ap[(size_t)j * a.C + c] = posc > 0 ? acc / (double)posc : 0.0;
+}
+
+// a wave per latent: the largest ap of the row and the lowest column that has it
+__global__ __launch_bounds__(256) void la_best_kernel(const double* __restrict__ ap, int S, int C, double* __restrict__ best_ap,
+                                                      int32_t* __restrict__ best_class) {
+    const int lane = threadIdx.x & 63;
+    const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= S) return;
+    double best = -1.0;
+    int bi = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+        const double v = ap[(size_t)j * C + c];
+        if (v > best) { best = v; bi = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) {
+        if (best_ap) best_ap[j] = best;
+        if (best_class) best_class[j] = bi;
+    }
+}
+
+}  // namespace
+
+int64_t saev_latent_ap_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t nnz) {
+    if (!la_shape_ok(N, S, C, nnz)) return -1;
+    saev_latent_ap_layout L;
+    la_layout(S, C, nnz, &L);
+    return L.total_bytes;
+}
+
+int saev_latent_ap_layout_of(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_latent_ap_layout* out) {
+    if (!out) return free_refuse(SAEV_INVALID_ARG, "saev_latent_ap_layout_of: no saev_latent_ap_layout");
+    if (!la_shape_ok(N, S, C, nnz)) return free_refuse(SAEV_UNSUPPORTED, "saev_latent_ap_layout_of: 1 <= N, S < 2^31, 1 <= C <= 4096, 0 <= nnz < 2^31");
+    la_layout(S, C, nnz, out);
+    return SAEV_OK;
+}
+
+int saev_latent_ap(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+                   const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, double* ap, int64_t* pos, double* best_ap,
+                   int32_t* best_class, void* workspace, int64_t workspace_bytes, void* stream) {
+    const auto refuse = [](int code, const char* msg) { return free_refuse(code, msg); };
+    if (N < 0 || S < 0 || C < 0 || nnz < 0) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: negative size");
+    if (N > 0x7fffffffLL || S > 0x7fffffffLL || nnz > 0x7fffffffLL) return refuse(SAEV_UNSUPPORTED, "saev_latent_ap: N, S and nnz must stay below 2^31");
+    if (N < 1 || S < 1) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: N and S must be at least 1");
+    if (C < 1 || C > LA_MAX_C) return refuse(SAEV_UNSUPPORTED, "saev_latent_ap: the number of classes must lie in [1, 4096]");
+    if (!row_ptr) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: row_ptr is NULL");
+    if (nnz > 0 && (!indices || !data)) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: indices and data come with nnz > 0");
+    if ((class_u8 != nullptr) == (class_i32 != nullptr))
+        return refuse(SAEV_INVALID_ARG, "saev_latent_ap: give the classes as class_u8 (with an optional remap) or as class_i32, one of the two");
+    if (remap && !class_u8) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: remap goes with class_u8");
+    if (!ap || !pos) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: ap and pos must not be NULL");
+    saev_latent_ap_layout L;
+    la_layout(S, C, nnz, &L);
+    if (!workspace || workspace_bytes < L.total_bytes)
+        return refuse(SAEV_INVALID_ARG, "saev_latent_ap: workspace smaller than saev_latent_ap_workspace_bytes(N, S, C, nnz)");
+    if (((uintptr_t)workspace & 255) != 0) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: workspace must be 256-byte aligned");
+
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    int32_t* err = reinterpret_cast<int32_t*>(ws + L.off_err);
+    int64_t* starts = reinterpret_cast<int64_t*>(ws + L.off_starts);
+    int32_t* hist = reinterpret_cast<int32_t*>(ws + L.off_hist);
+    int32_t* total = hist + 256 * L.parts;
+    // the sort ends in (key, latent, row); it starts there when the number of passes is even
+    uint32_t* key[2] = {reinterpret_cast<uint32_t*>(ws + L.off_key), reinterpret_cast<uint32_t*>(ws + L.off_key2)};
+    uint32_t* lat[2] = {reinterpret_cast<uint32_t*>(ws + L.off_latent), reinterpret_cast<uint32_t*>(ws + L.off_latent2)};
+    int32_t* row[2] = {reinterpret_cast<int32_t*>(ws + L.off_row), reinterpret_cast<int32_t*>(ws + L.off_row2)};
+    unsigned long long* upos = reinterpret_cast<unsigned long long*>(pos);
+
+    bool ok = hipMemsetAsync(err, 0, 64, s) == hipSuccess;
+    ok = ok && hipMemsetAsync(pos, 0, (size_t)(8 * C), s) == hipSuccess;
+    if (!ok) return refuse(SAEV_HIP_ERROR, "saev_latent_ap: hipMemsetAsync failed");
+    hipLaunchKernelGGL(la_labels_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, class_u8, remap, class_i32, (int)N, (int)C, upos, err);
+    int at = (int)(L.passes & 1);
+    if (nnz > 0) {
+        const int parts = (int)((nnz + L.part_len - 1) / L.part_len);
+        const int grid = (int)std::min<int64_t>((nnz + 255) / 256, 8192);
+        hipLaunchKernelGGL(la_init_kernel, dim3(grid), dim3(256), 0, s, row_ptr, indices, data, (long)nnz, (int)N, (int)S, key[at], lat[at], row[at],
+                           err);
+        for (int p = 0; p < (int)L.passes; ++p) {
+            const int by_latent = p >= 4 ? 1 : 0, shift = 8 * (by_latent ? p - 4 : p);
+            hipLaunchKernelGGL(la_hist_kernel, dim3(parts), dim3(64), 0, s, by_latent ? lat[at] : key[at], (long)nnz, (long)L.part_len, shift, parts,
+                               hist);
+            hipLaunchKernelGGL(la_scan_kernel, dim3(256), dim3(LA_SCAN_THREADS), 0, s, hist, parts, total);
+            hipLaunchKernelGGL(la_scatter_kernel, dim3(parts), dim3(64), 0, s, key[at], lat[at], row[at], key[at ^ 1], lat[at ^ 1], row[at ^ 1],
+                               (long)nnz, (long)L.part_len, shift, by_latent, parts, hist, total);
+            at ^= 1;
+        }
+    }
+    hipLaunchKernelGGL(la_starts_kernel, dim3((unsigned)((S + 1 + 255) / 256)), dim3(256), 0, s, lat[0], (long)nnz, (int)S, starts);
+    LaTerms a{starts, key[0], row[0], class_u8, remap, class_i32, upos, ap, (int)N, (int)S, (int)C};
+    hipLaunchKernelGGL(la_terms_kernel, dim3((unsigned)((S + 3) / 4), (unsigned)((C + 63) / 64)), dim3(256), 0, s, a);
+    if (best_ap || best_class)
+        hipLaunchKernelGGL(la_best_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, ap, (int)S, (int)C, best_ap, best_class);
+    if (hipGetLastError() != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_latent_ap: kernel launch failed");
+    return SAEV_OK;
+}

@@ -838,6 +838,97 @@ class Probe1D:
         return tuple(outs)
 
 
+class LatentAPResult:
+    """What ``latent_ap`` leaves on the device: ``ap`` (S, C) float64, ``n_pos`` (C) int64, ``best_ap`` (S) float64 and ``best_class``
+    (S) int32, the lowest column that attains the row maximum.  The call itself does not synchronise; the first read of any of the
+    four reads the device's error word (one synchronisation) and raises ValueError if it is not 0.  ``sorted_events()`` gives the
+    workspace's sorted entries (include/saev_amd.h: LATENT AP)."""
+
+    _ERRORS = {1: "a class id lies outside [-1, n_classes)", 2: "a column index lies outside [0, n_latents)"}
+
+    def __init__(self, ap, n_pos, best_ap, best_class, ws, layout, shape):
+        self._out = dict(ap=ap, n_pos=n_pos, best_ap=best_ap, best_class=best_class)
+        self._ws, self.layout, self.shape = ws, layout, shape
+        self._checked = False
+
+    def _read(self, name):
+        if not self._checked:
+            code = int(self._ws[self.layout.off_err:self.layout.off_err + 4].view(torch.int32).item())
+            if code != 0:
+                raise ValueError(f"latent_ap: {self._ERRORS.get(code, code)} (found on the device)")
+            self._checked = True
+        return self._out[name]
+
+    ap = property(lambda self: self._read("ap"))
+    n_pos = property(lambda self: self._read("n_pos"))
+    best_ap = property(lambda self: self._read("best_ap"))
+    best_class = property(lambda self: self._read("best_class"))
+
+    def sorted_events(self):
+        """(starts (S + 1) int64, key (E) int32 bit patterns of the uint32 keys, latent (E) int32, row (E) int32) of the E events in
+        (latent, value descending, row ascending) order."""
+        n, s, c, nnz = self.shape
+        lay = self.layout
+        view = lambda off, dtype, k: self._ws[off:off + k * torch.empty((), dtype=dtype).element_size()].view(dtype)  # noqa: E731
+        starts = view(lay.off_starts, torch.int64, s + 1)
+        e = int(starts[s].item())
+        return starts, view(lay.off_key, torch.int32, nnz)[:e], view(lay.off_latent, torch.int32, nnz)[:e], view(lay.off_row, torch.int32, nnz)[:e]
+
+
+def latent_ap(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_rows: int, n_latents: int, n_classes: int, *,
+              labels: torch.Tensor, remap: torch.Tensor | None = None, nnz: int | None = None) -> LatentAPResult:
+    """Exact tie-aware average precision of every latent against every class (include/saev_amd.h: LATENT AP).
+    x as CSR on the device (indptr (N + 1) int64, indices (nnz) int32, data (nnz) float32); ``labels`` (N) int32 / int64 columns with
+    -1 for a row without a class, or uint8 bytes with an optional ``remap`` (256) int32 byte -> column or -1.  ``indptr`` holds
+    absolute positions into ``indices`` / ``data``: when it does not start at 0 (a block cut out of a longer CSR) give
+    ``nnz = indptr[-1] - indptr[0]``, which is otherwise taken to be ``indices.numel()`` -- the call reads no device value back to
+    find it out, and ``indices`` and ``data`` must hold ``indptr[-1]`` entries.  One call, one workspace, no synchronisation; there
+    is no CPU path."""
+    for name, v, hi in (("n_rows", n_rows, 2**31), ("n_latents", n_latents, 2**31), ("n_classes", n_classes, 4097)):
+        if not 1 <= v < hi:
+            raise ValueError(f"latent_ap: unsupported {name} {v} (1 <= {name} < {hi})")
+    device = indptr.device
+    if device.type != "cuda":
+        raise RuntimeError("latent_ap runs on a HIP device only (there is no CPU path)")
+    stored = indices.numel()
+    nnz = stored if nnz is None else int(nnz)
+    if not 0 <= nnz < 2**31 or nnz > stored:
+        raise ValueError(f"latent_ap: unsupported nnz {nnz} (0 <= nnz < 2^31, and at most the {stored} entries of indices)")
+
+    def on(t, dtype, shape, what):
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device:
+            raise ValueError(f"{what} must be {dtype} of shape {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.contiguous()
+
+    indptr = on(indptr, torch.int64, (n_rows + 1,), "indptr")
+    indices = on(indices, torch.int32, (stored,), "indices")
+    data = on(data, torch.float32, (stored,), "data")
+    u8 = i32 = None
+    if labels.dtype == torch.uint8:
+        u8 = on(labels, torch.uint8, (n_rows,), "labels")
+        if remap is not None:
+            remap = on(remap, torch.int32, (256,), "remap")
+    elif labels.dtype in (torch.int32, torch.int64):
+        if remap is not None:
+            raise ValueError("latent_ap: remap goes with uint8 labels")
+        i32 = on(labels.to(torch.int32), torch.int32, (n_rows,), "labels")
+    else:
+        raise ValueError(f"labels must be uint8, int32 or int64, got {labels.dtype}")
+    lib = _lib.load()
+    layout = _lib.SaevLatentAPLayout()
+    _lib.check(lib, None, lib.saev_latent_ap_layout_of(n_rows, n_latents, n_classes, nnz, C.byref(layout)), "saev_latent_ap_layout_of")
+    ws = torch.empty(layout.total_bytes, device=device, dtype=torch.uint8)
+    ap = torch.empty(n_latents, n_classes, device=device, dtype=torch.float64)
+    n_pos = torch.empty(n_classes, device=device, dtype=torch.int64)
+    best_ap = torch.empty(n_latents, device=device, dtype=torch.float64)
+    best_class = torch.empty(n_latents, device=device, dtype=torch.int32)
+    with torch.cuda.device(device):
+        rc = lib.saev_latent_ap(_ptr(indptr), _ptr(indices), _ptr(data), nnz, n_rows, n_latents, n_classes, _ptr(u8), _ptr(remap), _ptr(i32),
+                                _ptr(ap), _ptr(n_pos), _ptr(best_ap), _ptr(best_class), _ptr(ws), ws.numel(), _stream())
+    _lib.check(lib, None, rc, "saev_latent_ap")
+    return LatentAPResult(ap, n_pos, best_ap, best_class, ws, layout, (n_rows, n_latents, n_classes, nnz))
+
+
 @dataclasses.dataclass
 class StepStats:
     mse: float
