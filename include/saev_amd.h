@@ -879,6 +879,92 @@ int saev_latent_ap_layout_of(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_
 int saev_latent_ap(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
                    const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, double* ap, int64_t* pos, double* best_ap,
                    int32_t* best_class, void* workspace, int64_t workspace_bytes, void* stream);
+/* SPARSE LINEAR (the training half of the concept audit, the reference's contrib/trait_discovery tdiscovery.classification:
+ * aggregate_to_images and the LogisticRegression(penalty="l1") of train_worker_fn), context-free; DESIGN.md 3.20.
+ *
+ * POOLING.  saev_pool_images turns a token CSR of n_images * tokens_per_image rows (indptr: that many + 1 int64 absolute positions
+ * with indptr[last] <= nnz, indices int32 in [0, n_latents), data fp32) into out (n_images x n_latents fp32, row-major): per image
+ * and latent the maximum or the mean over the image's tokens_per_image dense values.
+ *   SAEV_POOL_MAX   the largest stored value, and 0 as well when the latent is stored in fewer than tokens_per_image of the image's
+ *                   rows (so a latent stored in every row with negative values only has a negative maximum).
+ *   SAEV_POOL_MEAN  the fp32 sum of the stored values in ascending row order (what a row-by-row fp32 reduction of the dense block
+ *                   gives: the implicit zeros change nothing), then ONE fp32 division by (float)tokens_per_image.
+ * Rows must be CANONICAL: no column twice in a row (the value of such a column is unspecified; nothing is read or written out of
+ * bounds).  The sign of a zero is not specified.  err (one int32 on the device, zeroed by the call): 0, or the largest
+ * SAEV_POOL_ERR_* met -- the outputs are void then; the caller reads it when it next synchronises.  A workgroup owns one image and
+ * saev_pool_images_range() consecutive latents (accumulators and patch counts in LDS); out is written once, no memset.  1 <=
+ * n_images * tokens_per_image < 2^31, 1 <= n_latents < 2^31 and at most 65535 ranges (else SAEV_UNSUPPORTED).  Nothing is allocated,
+ * read back or synchronised.
+ *
+ * L1 LOGISTIC.  Minimises  F(W, b) = C * sum_i loss_i(W, b) + ||W||_1  (the intercept b is not penalised) over X (n x S fp32,
+ * row-major, finite) and y (n int32 class indices in [0, K)): scikit-learn's LogisticRegression(penalty="l1", C=C) problem.
+ *   K == 2   loss_i = log(1 + exp(-t_i z_i)), t_i = +1 for class 1 and -1 for class 0, z = X w + b: ONE coefficient row.
+ *   K >= 3   loss_i = logsumexp_k(z_ik) - z_{i y_i}, Z = X W^T + b: K rows; the intercepts are reported with mean zero.
+ * coef_rows = K == 2 ? 1 : K.  2 <= K <= 64, 1 <= n < 2^31, 1 <= S <= 2^30 (else SAEV_UNSUPPORTED, -1 from the size function; K < 2
+ * is SAEV_INVALID_ARG); C > 0 and finite, kkt_tol >= 0.
+ * STOPPING RULE.  With g = C dLoss/dW and g_b = C dLoss/db at a point (W, b): the residual of a coefficient is |g + sign(w)| where
+ * w != 0 and max(|g| - 1, 0) where w == 0, that of an intercept |g_b|; the KKT residual is the largest of them, and the fit is
+ * done when it is <= kkt_tol.
+ * METHOD.  FISTA in fp64 with backtracking on L (start 1, doubling, never lowered) and function-value restart.  The logits of the
+ * last two iterates are kept, so the logits of the extrapolated point y are a combination of the two: an iteration is one gradient
+ * pass over X (at y) and one forward pass (at the candidate).  The KKT residual is evaluated AT y, whose gradient the iteration has:
+ * when it is within kkt_tol, y is the answer.  A step that fails  f(w+) <= f(y) + <g, w+ - y> + L/2 |w+ - y|^2 + 1e-12 |f(y)|
+ * doubles L and the next iteration retries it with the kept gradient; an accepted step whose objective is above the last
+ * iterate's while beta != 0 is dropped and the momentum restarts (t = 1) from that iterate.  Control lives in the state block
+ * (SAEV_L1_STATE_* doubles at off_state): the kernels of a finished fit, or of a phase an iteration does not need, leave on it in
+ * their first instructions, and the host may read it as seldom as it likes -- saev_l1_logistic_iterate(n_iters) enqueues n_iters
+ * iterations and never synchronises.  Sums are in an order fixed by (n, S, K): rows of a gradient chunk ascending, chunks ascending,
+ * lanes by a butterfly; no float atomics: two fits give the same bits, however the iterations are split over calls.
+ * ENTRIES.  _init zeroes the iterate (W = 0, b = 0) and checks X and y (err: int32[0] at off_err, the largest SAEV_L1_ERR_* met);
+ * _iterate continues; _result writes coef (coef_rows x S fp64), intercept (coef_rows fp64) and scalars (8 fp64: iterations run, the
+ * KKT residual of the returned point, its objective F, done 0/1, L, rejected steps, restarts, 0).  Of a fit that is done the
+ * returned point is y; of one that is not, the last iterate -- _result then evaluates its gradient (one more pass), and drops the
+ * momentum, so that the residual and the objective are those of what it returns.  All entries of one fit take the same X, y, n, S,
+ * K, C, kkt_tol and workspace (saev_l1_logistic_workspace_bytes(n, S, K) bytes of device memory, 256-byte aligned: three weight
+ * and three logit arrays, the gradient, n_chunks partial gradients, r, two loss vectors and the per-block sums).  Arguments are
+ * checked before the device is touched; a refused call leaves its message with saev_last_error(NULL). */
+#define SAEV_POOL_MAX 0
+#define SAEV_POOL_MEAN 1
+#define SAEV_POOL_ERR_COLUMN 1
+#define SAEV_POOL_ERR_VALUE 2
+#define SAEV_POOL_ERR_INDPTR 3
+#define SAEV_L1_ERR_VALUE 1
+#define SAEV_L1_ERR_CLASS 2
+#define SAEV_L1_STATE_WORDS 16
+#define SAEV_L1_STATE_ITER 0       /* iterations run (accepted, rejected and restarted ones alike) */
+#define SAEV_L1_STATE_L 1
+#define SAEV_L1_STATE_T 2
+#define SAEV_L1_STATE_BETA 3       /* y = w + beta (w - w_prev) */
+#define SAEV_L1_STATE_F 4          /* F of the last iterate */
+#define SAEV_L1_STATE_FY 5         /* C * loss at y */
+#define SAEV_L1_STATE_KKT 6        /* the KKT residual last evaluated (at y) */
+#define SAEV_L1_STATE_OBJ 7        /* F of the returned point, once done or after _result */
+#define SAEV_L1_STATE_DONE 8
+#define SAEV_L1_STATE_NEED_GRAD 9  /* 0 after a rejected step: the next iteration keeps the gradient */
+#define SAEV_L1_STATE_CUR 10       /* which of the three weight / logit arrays holds w, w_prev and the candidate */
+#define SAEV_L1_STATE_PREV 11
+#define SAEV_L1_STATE_NEXT 12
+#define SAEV_L1_STATE_REJECTS 13
+#define SAEV_L1_STATE_RESTARTS 14
+typedef struct {               /* byte offsets into the workspace (all multiples of 256) */
+    int32_t struct_size;
+    int32_t coef_rows;         /* K == 2 ? 1 : K */
+    int64_t chunk_rows, n_chunks;  /* the gradient's row chunks: a multiple of 64 rows each, at most 32 */
+    int64_t col_blocks;        /* workgroups of 256 columns over the S + 1 columns (the intercept is column S) */
+    int64_t total_bytes;
+    int64_t off_err, off_state, off_w, off_z, off_g, off_part, off_r, off_loss, off_bp;
+} saev_l1_logistic_layout;
+int64_t saev_pool_images_range(void);
+int saev_pool_images(const int64_t* indptr, const int32_t* indices, const float* data, int64_t nnz, int64_t n_images,
+                     int64_t tokens_per_image, int64_t n_latents, int32_t agg, float* out, int32_t* err, void* stream);
+int64_t saev_l1_logistic_workspace_bytes(int64_t n, int64_t S, int64_t K);
+int saev_l1_logistic_layout_of(int64_t n, int64_t S, int64_t K, saev_l1_logistic_layout* out);
+int saev_l1_logistic_init(const float* X, const int32_t* y, int64_t n, int64_t S, int64_t K, double C, double kkt_tol, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int saev_l1_logistic_iterate(const float* X, const int32_t* y, int64_t n, int64_t S, int64_t K, double C, double kkt_tol, int32_t n_iters,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int saev_l1_logistic_result(const float* X, const int32_t* y, int64_t n, int64_t S, int64_t K, double C, double kkt_tol, double* coef,
+                            double* intercept, double* scalars, void* workspace, int64_t workspace_bytes, void* stream);
 /* PARAMETER OWNERSHIP.  With the f16r encoder the context keeps, from one call to the next, what its forward needs of W_enc
  * (fp16 operand images, a slice-major fp32 transpose, bias and norm shares: written by the Adam launch of saev_train_step, or by
  * the last forward that prepared them itself) and uses it for as long as only the library has written the parameter buffer.  A

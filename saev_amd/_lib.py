@@ -105,6 +105,14 @@ class SaevLatentAPLayout(C.Structure):
                                          "off_latent", "off_row", "off_key2", "off_latent2", "off_row2")]
 
 
+class SaevL1LogisticLayout(C.Structure):
+    """include/saev_amd.h: saev_l1_logistic_layout (byte offsets into the workspace of the saev_l1_logistic entries)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("coef_rows", C.c_int32)] + \
+               [(n, C.c_int64) for n in ("chunk_rows", "n_chunks", "col_blocks", "total_bytes", "off_err", "off_state", "off_w", "off_z",
+                                         "off_g", "off_part", "off_r", "off_loss", "off_bp")]
+
+
 ACT_TOPK, ACT_RELU, ACT_BATCHTOPK = 0, 1, 2
 ROW_OVERFLOW = -7  # saev_status SAEV_ROW_OVERFLOW
 BATCH_OVERWRITE = 1
@@ -212,6 +220,13 @@ _SIGNATURES = {
     "saev_latent_ap_workspace_bytes": (C.c_int64, [C.c_int64] * 4),
     "saev_latent_ap_layout_of": (C.c_int, [C.c_int64] * 4 + [C.POINTER(SaevLatentAPLayout)]),
     "saev_latent_ap": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, P, P, P, P, C.c_int64, P]),
+    "saev_pool_images_range": (C.c_int64, []),
+    "saev_pool_images": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, P, P, P]),
+    "saev_l1_logistic_workspace_bytes": (C.c_int64, [C.c_int64] * 3),
+    "saev_l1_logistic_layout_of": (C.c_int, [C.c_int64] * 3 + [C.POINTER(SaevL1LogisticLayout)]),
+    "saev_l1_logistic_init": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, P, C.c_int64, P]),
+    "saev_l1_logistic_iterate": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, P, C.c_int64, P]),
+    "saev_l1_logistic_result": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, P, P, P, P, C.c_int64, P]),
     "saev_comm_unique_id": (C.c_int, [P]),
     "saev_comm_init": (C.c_int, [P, P, C.c_int32, C.c_int32]),
     "saev_comm_world": (C.c_int, [P]),

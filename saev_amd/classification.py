@@ -5,15 +5,23 @@ kernels behind ``engine.latent_ap`` (include/saev_amd.h: LATENT AP; DESIGN.md 3.
 The average precision of a latent's activation as a detector of each segmentation class is the exact tie-aware value of McSherry and
 Najork (2008) -- the expectation over all orders of tied scores -- for every latent and every class, in one call on the device: the
 stored entries are sorted once and each latent's zero rows enter as one tie group in closed form.  All sums are fp64 in a fixed
-order (two runs give the same bits).  There is no CPU path: without a HIP device everything that computes raises."""
+order (two runs give the same bits).  There is no CPU path: without a HIP device everything that computes raises.
+
+The training half (``train_worker_fn``: ``PatchAgg``, ``LabelGrouping``, ``SparseLinear``, ``DecisionTree``, ``TrainConfig``,
+``apply_grouping``, ``aggregate_to_images``, ``load_image_labels``) pools the token codes to one row per image with
+``engine.pool_images`` and fits the L1-penalised logistic regression with ``engine.l1_logistic``: the reference's
+problem solved to a certified optimum on the device, and written as the checkpoint ``eval_worker_fn`` reads."""
 
 from __future__ import annotations
 
+import csv
 import dataclasses
+import enum
 import json
 import logging
 import pathlib
 import pickle
+import typing as tp
 
 import numpy as np
 import scipy.sparse
@@ -289,4 +297,282 @@ def eval_worker_fn(cfg: EvalConfig) -> int:
             "classifiers": all_results,
         }, fd)
     logger.info("Saved %d classifier results to %s", len(all_results), results_fpath)
+    return 0
+
+
+# ---------------------------------------------------------------- the training half ------------------------------------------------------
+
+class PatchAgg(enum.Enum):
+    """How to aggregate patch-level features to image-level."""
+
+    MEAN = "mean"
+    MAX = "max"
+
+
+@dataclasses.dataclass(frozen=True)
+class LabelGrouping:
+    """A classification task as a grouping of labels, the reference's fields: with ``groups`` empty the original labels of
+    ``source_col`` are the classes; otherwise each group name is a class, and an image whose label is in no group is left out."""
+
+    name: str
+    """Task name for output files."""
+    source_col: str
+    """Label column to read. Use 'class' for ImgFolder class names."""
+    groups: dict[str, list[str]] = dataclasses.field(default_factory=dict)
+    """Mapping from group name to list of original labels. Empty = no grouping."""
+
+
+@dataclasses.dataclass(frozen=True)
+class DecisionTree:
+    """The reference's decision-tree choice.  Accepted as a configuration and NOT trained here: a CPU tree has nothing for a kernel to
+    win (the policy of PCA in ``baselines.py``); ``train_worker_fn`` raises NotImplementedError naming it."""
+
+    key: tp.Literal["decision-tree"] = "decision-tree"
+    max_depth: int = -1
+    """Maximum depth of the tree. Negative numbers mean unlimited."""
+
+
+@dataclasses.dataclass(frozen=True)
+class SparseLinear:
+    """Sparse linear classifier: logistic regression with an L1 penalty, ``engine.l1_logistic``.  ``C`` is scikit-learn's inverse
+    regularisation strength.  ``max_iter`` is the reference's field, the epoch cap of its saga solver; it does not translate to this
+    solver and is accepted and recorded in the checkpoint header like the Slurm fields.  What bounds this solver is ``kkt_tol`` (the
+    KKT residual at which it stops) and ``solver_iters`` (its iteration cap)."""
+
+    key: tp.Literal["sparse-linear"] = "sparse-linear"
+    C: float = 0.01
+    """Inverse regularization strength. Lower C = more sparsity."""
+    max_iter: int = 90
+    """The reference's saga epoch cap: recorded, unused."""
+    kkt_tol: float = 1e-4
+    solver_iters: int = 5000
+
+
+@dataclasses.dataclass(frozen=True)
+class TrainConfig:
+    """Configuration of the training stage, the reference's fields and defaults (the Slurm fields are accepted and unused)."""
+
+    run: pathlib.Path = pathlib.Path("./runs/abcdefg")
+    """Run directory."""
+    train_shards: pathlib.Path = pathlib.Path("./shards/01234567")
+    """Training shards directory."""
+    test_shards: pathlib.Path = pathlib.Path("./shards/abcdef01")
+    """Test shards directory."""
+    task: LabelGrouping = dataclasses.field(default_factory=lambda: LabelGrouping(name="habitat", source_col="habitat"))
+    """Classification task definition."""
+    patch_agg: PatchAgg = PatchAgg.MAX
+    """How to aggregate patch features to image features."""
+    cls: DecisionTree | SparseLinear = SparseLinear()
+    """Classifier architecture."""
+    debug: bool = False
+    mem_gb: int = 80
+    slurm_acct: str = ""
+    slurm_partition: str = ""
+    n_hours: float = 4.0
+    log_to: pathlib.Path = pathlib.Path("./logs")
+
+
+IMAGE_LABELS_FNAME = "image_labels.csv"
+
+
+def load_image_labels(shards_dpath: pathlib.Path) -> tuple[list[str], dict[str, list[str]]]:
+    """(label_columns, {column: one string label per image}) of a shards directory.  The reference rebuilds the image dataset from
+    the shard metadata; here the labels are read from ``image_labels.csv`` in the shards directory: a header ``stem,<col>,...`` (the
+    columns of the reference's ``labels.csv``) and one row per example in example order (INTEGRATION.md has the lines that write it
+    from the reference's function).  The row count is checked against ``Metadata.n_examples``."""
+    shards_dpath = pathlib.Path(shards_dpath)
+    fpath = shards_dpath / IMAGE_LABELS_FNAME
+    if not fpath.exists():
+        raise FileNotFoundError(f"Image labels missing: '{fpath}' (a header 'stem,<col>,...' and one row per example in example order).")
+    with open(fpath, newline="") as fd:
+        rows = list(csv.reader(fd))
+    if not rows or len(rows[0]) < 2 or rows[0][0] != "stem":
+        raise ValueError(f"'{fpath}' must start with the header 'stem,<col>,...'.")
+    label_cols = rows[0][1:]
+    body = rows[1:]
+    n_examples = saev_data.Metadata.load(shards_dpath).n_examples
+    if len(body) != n_examples:
+        raise ValueError(f"'{fpath}' has {len(body)} rows, the shards hold {n_examples} examples.")
+    if not body:
+        raise ValueError("Dataset has no samples")
+    for i, row in enumerate(body):
+        if len(row) != len(rows[0]):
+            raise ValueError(f"'{fpath}' row {i + 1} has {len(row)} fields, the header {len(rows[0])}.")
+    return label_cols, {col: [row[j + 1] for row in body] for j, col in enumerate(label_cols)}
+
+
+def apply_grouping(labels: list[str], task: LabelGrouping) -> tuple[np.ndarray, list[str], np.ndarray]:
+    """(targets int32 (-1 if excluded), class_names in order, mask of the images to include) of a list of string labels, the
+    reference's arithmetic: without groups the sorted unique labels are the classes; with groups the sorted group names are, and a
+    label in no group is masked out."""
+    n = len(labels)
+    if not task.groups:
+        unique_labels = sorted(set(labels))
+        label_to_idx = {lbl: i for i, lbl in enumerate(unique_labels)}
+        return np.array([label_to_idx[lbl] for lbl in labels], dtype=np.int32), unique_labels, np.ones(n, dtype=bool)
+    label_to_group: dict[str, str] = {}
+    for group_name, group_labels in task.groups.items():
+        for lbl in group_labels:
+            assert lbl not in label_to_group, f"Label '{lbl}' in multiple groups"
+            label_to_group[lbl] = group_name
+    group_names = sorted(task.groups.keys())
+    group_to_idx = {g: i for i, g in enumerate(group_names)}
+    targets = np.full(n, -1, dtype=np.int32)
+    mask = np.zeros(n, dtype=bool)
+    for i, lbl in enumerate(labels):
+        if lbl in label_to_group:
+            targets[i] = group_to_idx[label_to_group[lbl]]
+            mask[i] = True
+    return targets, group_names, mask
+
+
+def aggregate_to_images(patch_acts, n_images: int, n_patches_per_image: int, patch_agg: PatchAgg, device=None) -> np.ndarray:
+    """Dense (n_images, d_sae) float32 of a scipy CSR matrix (n_patches, d_sae), the reference's values as numbers: per image the
+    column maximum or mean of its ``n_patches_per_image`` dense rows, computed by ``engine.pool_images`` on the device without the
+    dense rows."""
+    n_patches, d_sae = patch_acts.shape
+    assert n_patches == n_images * n_patches_per_image
+    if not isinstance(patch_agg, PatchAgg):
+        raise ValueError(f"Unknown aggregation: {patch_agg}")
+    dev = _device(device)
+    return engine.pool_images(*_csr_on(patch_acts, dev), n_images, n_patches_per_image, d_sae, patch_agg.value).pooled.cpu().numpy()
+
+
+class SparseLinearClassifier:
+    """A trained sparse linear classifier: a plain class (it pickles with the standard library; it is not a scikit-learn object)
+    with scikit-learn's attributes -- ``coef_`` (1, d) for two classes and (K, d) otherwise, ``intercept_``, ``classes_`` -- and the
+    solver's certificate ``n_iter_``, ``kkt_residual_``, ``objective_``, ``converged_``."""
+
+    def __init__(self, coef_, intercept_, classes_, *, C: float = 0.01, n_iter_: int = 0, kkt_residual_: float = float("nan"),
+                 objective_: float = float("nan"), converged_: bool = True):
+        self.coef_ = np.asarray(coef_, dtype=np.float64)
+        self.intercept_ = np.asarray(intercept_, dtype=np.float64)
+        self.classes_ = np.asarray(classes_)
+        self.C, self.n_iter_, self.kkt_residual_, self.objective_, self.converged_ = C, n_iter_, kkt_residual_, objective_, converged_
+
+    @classmethod
+    def fit(cls, X: np.ndarray, y: np.ndarray, *, C: float = 0.01, kkt_tol: float = 1e-4, solver_iters: int = 5000, device=None) -> "SparseLinearClassifier":
+        """Fit on dense float32 rows X (n, d) and integer targets y (n) with ``engine.l1_logistic``."""
+        dev = _device(device)
+        res = engine.l1_logistic(torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).to(dev),
+                                 torch.from_numpy(np.ascontiguousarray(y).astype(np.int64)).to(dev), C, kkt_tol=kkt_tol, max_iter=solver_iters)
+        return cls(res.coef_.cpu().numpy(), res.intercept_.cpu().numpy(), res.classes_.cpu().numpy().astype(np.asarray(y).dtype), C=C,
+                   n_iter_=res.n_iter_, kkt_residual_=res.kkt_residual_, objective_=res.objective_, converged_=res.converged_)
+
+    def decision_function(self, X: np.ndarray) -> np.ndarray:
+        """X @ coef_.T + intercept_ in float64: (n,) for two classes, (n, K) otherwise, as scikit-learn's."""
+        scores = np.asarray(X, dtype=np.float64) @ self.coef_.T + self.intercept_
+        return scores[:, 0] if self.coef_.shape[0] == 1 else scores
+
+    def predict(self, X: np.ndarray) -> np.ndarray:
+        scores = self.decision_function(X)
+        return self.classes_[(scores > 0).astype(np.int64)] if scores.ndim == 1 else self.classes_[scores.argmax(axis=1)]
+
+
+def _jsonable(obj):
+    if isinstance(obj, dict):
+        return {k: _jsonable(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [_jsonable(v) for v in obj]
+    if isinstance(obj, pathlib.PurePath):
+        return str(obj)
+    if isinstance(obj, enum.Enum):
+        return obj.value
+    return obj
+
+
+def train_worker_fn(cfg: TrainConfig) -> int:
+    """Train a classifier on pooled SAE codes, as the reference's function of this name: the same checks and messages, both splits
+    pooled on the device, the images masked by ``apply_grouping``, the fit, ``test_pred`` and ``test_acc``, and the checkpoint
+    ``<run>/inference/<test shards>/cls_{task}_{agg}_C{C}.pkl`` -- one JSON header line (``cfg``, ``test_acc``, ``n_classes``,
+    ``class_names``), then the pickle of ``{"classifier", "test_pred", "test_y"}`` -- which ``eval_worker_fn`` reads."""
+    log_format = "[%(asctime)s] [%(levelname)s] [%(name)s] %(message)s"
+    logging.basicConfig(level=logging.DEBUG if cfg.debug else logging.INFO, format=log_format, force=True)
+    logger = logging.getLogger("cls::train")
+    logger.info("Started train_worker_fn().")
+
+    if isinstance(cfg.cls, DecisionTree):
+        raise NotImplementedError("cls=DecisionTree is not built here: a CPU decision tree has nothing for a kernel to win (DESIGN.md section 7); "
+                                  "train it with the reference and audit its checkpoint with eval_worker_fn.")
+    if not isinstance(cfg.cls, SparseLinear):
+        raise ValueError(f"Unknown classifier type: {type(cfg.cls)}")
+
+    run = disk.Run(cfg.run)
+    train_shards_dpath, test_shards_dpath = pathlib.Path(cfg.train_shards), pathlib.Path(cfg.test_shards)
+    assert train_shards_dpath.exists(), f"Train shards directory {train_shards_dpath} does not exist."
+    assert test_shards_dpath.exists(), f"Test shards directory {test_shards_dpath} does not exist."
+    train_inference_dpath = run.inference / train_shards_dpath.name
+    assert train_inference_dpath.exists(), f"Train inference directory {train_inference_dpath} doesn't exist. Run inference.py."
+    test_inference_dpath = run.inference / test_shards_dpath.name
+    assert test_inference_dpath.exists(), f"Test inference directory {test_inference_dpath} doesn't exist. Run inference.py."
+    train_token_acts_fpath = train_inference_dpath / "token_acts.npz"
+    assert train_token_acts_fpath.exists(), f"Train SAE acts missing: '{train_token_acts_fpath}'. Run inference.py."
+    test_token_acts_fpath = test_inference_dpath / "token_acts.npz"
+    assert test_token_acts_fpath.exists(), f"Test SAE acts missing: '{test_token_acts_fpath}'. Run inference.py."
+
+    train_md = saev_data.Metadata.load(train_shards_dpath)
+    test_md = saev_data.Metadata.load(test_shards_dpath)
+    logger.info("Loaded metadata: train=%d images, test=%d images.", train_md.n_examples, test_md.n_examples)
+
+    logger.info("Loading image-level labels from train shards...")
+    train_label_cols, train_labels = load_image_labels(train_shards_dpath)
+    logger.info("Train label columns: %s", train_label_cols)
+    logger.info("Loading image-level labels from test shards...")
+    test_label_cols, test_labels = load_image_labels(test_shards_dpath)
+    logger.info("Test label columns: %s", test_label_cols)
+
+    source_col = cfg.task.source_col
+    assert source_col in train_labels, f"Source column '{source_col}' not in train labels: {train_label_cols}"
+    assert source_col in test_labels, f"Source column '{source_col}' not in test labels: {test_label_cols}"
+
+    train_targets, class_names, train_mask = apply_grouping(train_labels[source_col], cfg.task)
+    test_targets, _, test_mask = apply_grouping(test_labels[source_col], cfg.task)
+    n_classes = len(class_names)
+    logger.info("Task '%s': %d classes %s", cfg.task.name, n_classes, class_names)
+    logger.info("Train: %d/%d images after filtering", train_mask.sum(), len(train_mask))
+    logger.info("Test: %d/%d images after filtering", test_mask.sum(), len(test_mask))
+
+    logger.info("Loading train SAE activations from %s...", train_token_acts_fpath)
+    train_acts_csr = scipy.sparse.load_npz(train_token_acts_fpath).tocsr()
+    logger.info("Train acts: shape=%s, nnz=%d", train_acts_csr.shape, train_acts_csr.nnz)
+    logger.info("Loading test SAE activations from %s...", test_token_acts_fpath)
+    test_acts_csr = scipy.sparse.load_npz(test_token_acts_fpath).tocsr()
+    logger.info("Test acts: shape=%s, nnz=%d", test_acts_csr.shape, test_acts_csr.nnz)
+
+    train_n_patches_per_image = train_md.content_tokens_per_example
+    train_n_patches_expected = train_md.n_examples * train_n_patches_per_image
+    assert train_acts_csr.shape[0] == train_n_patches_expected, f"Train acts have {train_acts_csr.shape[0]} rows, expected {train_n_patches_expected}"
+    test_n_patches_per_image = test_md.content_tokens_per_example
+    test_n_patches_expected = test_md.n_examples * test_n_patches_per_image
+    assert test_acts_csr.shape[0] == test_n_patches_expected, f"Test acts have {test_acts_csr.shape[0]} rows, expected {test_n_patches_expected}"
+
+    logger.info("Aggregating train patches to images using %s...", cfg.patch_agg.value)
+    train_X_all = aggregate_to_images(train_acts_csr, train_md.n_examples, train_n_patches_per_image, cfg.patch_agg)
+    logger.info("Train features (all): shape=%s", train_X_all.shape)
+    logger.info("Aggregating test patches to images using %s...", cfg.patch_agg.value)
+    test_X_all = aggregate_to_images(test_acts_csr, test_md.n_examples, test_n_patches_per_image, cfg.patch_agg)
+    logger.info("Test features (all): shape=%s", test_X_all.shape)
+
+    train_X, train_y = train_X_all[train_mask], train_targets[train_mask]
+    test_X, test_y = test_X_all[test_mask], test_targets[test_mask]
+    logger.info("Train features (filtered): shape=%s", train_X.shape)
+    logger.info("Test features (filtered): shape=%s", test_X.shape)
+
+    logger.info("Training SparseLinear (LogisticRegression L1) with C=%g...", cfg.cls.C)
+    classifier = SparseLinearClassifier.fit(train_X, train_y, C=cfg.cls.C, kkt_tol=cfg.cls.kkt_tol, solver_iters=cfg.cls.solver_iters)
+    logger.info("Training complete: %d iterations, KKT residual %.3g, objective %.6g, converged %s.", classifier.n_iter_, classifier.kkt_residual_,
+                classifier.objective_, classifier.converged_)
+
+    test_pred = classifier.predict(test_X)
+    test_acc = (test_pred == test_y).mean()
+    logger.info("Test accuracy: %.4f", test_acc)
+    nonzero_i = np.where(np.any(classifier.coef_ != 0, axis=0))[0]
+    logger.info("L1 selected %d features: %s", len(nonzero_i), nonzero_i.tolist())
+
+    out_fpath = test_inference_dpath / f"cls_{cfg.task.name}_{cfg.patch_agg.value}_C{cfg.cls.C}.pkl"
+    header = {"cfg": _jsonable(dataclasses.asdict(cfg)), "test_acc": float(test_acc), "n_classes": int(n_classes), "class_names": class_names}
+    with open(out_fpath, "wb") as fd:
+        fd.write(json.dumps(header).encode() + b"\n")
+        pickle.dump({"classifier": classifier, "test_pred": test_pred, "test_y": test_y}, fd)
+    logger.info("Saved checkpoint to %s", out_fpath)
     return 0

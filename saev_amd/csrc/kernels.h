@@ -866,3 +866,7 @@ constexpr int P1_PARTS = 1024;  // at most this many contiguous parts of the CSR
 // ---- Latent AP (latentap.hip: kernels and their C entries; include/saev_amd.h: LATENT AP) -----------------------------------------
 // tie groups of at most this many rows are summed term by term, larger ones through the closed form (saev_latent_ap_layout.direct_max)
 constexpr int LA_DIRECT_MAX = 8;
+
+// ---- Sparse linear (sparselinear.hip: kernels and their C entries; include/saev_amd.h: SPARSE LINEAR) ------------------------------
+// latents of one pooling workgroup: an fp32 accumulator and an int32 patch count each, 64 KB of LDS (saev_pool_images_range)
+constexpr int SL_POOL_RANGE = 8192;

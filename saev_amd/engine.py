@@ -929,6 +929,151 @@ def latent_ap(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n
     return LatentAPResult(ap, n_pos, best_ap, best_class, ws, layout, (n_rows, n_latents, n_classes, nnz))
 
 
+class PoolResult:
+    """What ``pool_images`` leaves on the device: ``pooled`` (n_images, n_latents) float32.  The call itself does not synchronise; the
+    first read of ``pooled`` reads the device's error word (one synchronisation) and raises ValueError if it is not 0.  ``ranges`` is
+    the number of latent ranges (workgroups per image) the launch ran, ``range_len`` the latents of one."""
+
+    _ERRORS = {1: "a column index lies outside [0, n_latents)", 2: "a stored value is not finite", 3: "indptr is not a non-decreasing sequence of positions into indices"}
+
+    def __init__(self, out, err, ranges, range_len):
+        self._out, self._err, self.ranges, self.range_len = out, err, ranges, range_len
+        self._checked = False
+
+    @property
+    def pooled(self) -> torch.Tensor:
+        if not self._checked:
+            code = int(self._err.item())
+            if code != 0:
+                raise ValueError(f"pool_images: {self._ERRORS.get(code, code)} (found on the device)")
+            self._checked = True
+        return self._out
+
+
+def pool_images(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_images: int, tokens_per_image: int, n_latents: int,
+                agg: str = "max") -> PoolResult:
+    """Pool a token CSR on the device (indptr (n_images * tokens_per_image + 1) int64, indices int32, data float32, as ``latent_ap``
+    takes it) to one dense float32 row per image: ``PoolResult.pooled`` (n_images, n_latents) holds, per image and latent, the
+    reference's ``aggregate_to_images`` value as numbers (include/saev_amd.h: SPARSE LINEAR).  ``"max"``: the largest
+    of the image's ``tokens_per_image`` dense values -- a latent stored in fewer patches competes with an implicit 0, one stored in all
+    of them with negative values only has a negative maximum.  ``"mean"``: the float32 sum of the stored values in patch order, then
+    one float32 division by ``float32(tokens_per_image)``.  Rows must be canonical (no column twice in a row).  A column index outside
+    [0, n_latents) or a non-finite value raises ValueError on the first read of ``pooled``.  There is no CPU path."""
+    aggs = {"max": 0, "mean": 1}
+    if agg not in aggs:
+        raise ValueError(f"pool_images: agg must be 'max' or 'mean', got {agg!r}")
+    for name, v in (("n_images", n_images), ("tokens_per_image", tokens_per_image), ("n_latents", n_latents)):
+        if not 1 <= v < 2**31:
+            raise ValueError(f"pool_images: unsupported {name} {v} (1 <= {name} < 2^31)")
+    if n_images * tokens_per_image >= 2**31:
+        raise ValueError(f"pool_images: unsupported n_images * tokens_per_image {n_images * tokens_per_image} (below 2^31)")
+    device = indptr.device
+    if device.type != "cuda":
+        raise RuntimeError("pool_images runs on a HIP device only (there is no CPU path)")
+    nnz = indices.numel()
+
+    def on(t, dtype, shape, what):
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device:
+            raise ValueError(f"{what} must be {dtype} of shape {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.contiguous()
+
+    indptr = on(indptr, torch.int64, (n_images * tokens_per_image + 1,), "indptr")
+    indices = on(indices, torch.int32, (nnz,), "indices")
+    data = on(data, torch.float32, (nnz,), "data")
+    lib = _lib.load()
+    out = torch.empty(n_images, n_latents, device=device, dtype=torch.float32)
+    err = torch.empty(1, device=device, dtype=torch.int32)
+    with torch.cuda.device(device):
+        rc = lib.saev_pool_images(_ptr(indptr), _ptr(indices), _ptr(data), nnz, n_images, tokens_per_image, n_latents, aggs[agg], _ptr(out),
+                                  _ptr(err), _stream())
+    _lib.check(lib, None, rc, "saev_pool_images")
+    range_len = int(lib.saev_pool_images_range())
+    return PoolResult(out, err, -(-n_latents // range_len), range_len)
+
+
+@dataclasses.dataclass
+class L1LogisticResult:
+    """A fit of ``l1_logistic``: ``coef_`` (1, S) for two classes and (K, S) otherwise and ``intercept_`` (float64, on the device; the
+    intercepts of K >= 3 have mean zero), ``classes_`` (the sorted unique values of y), the iterations run, the KKT residual and the
+    objective F = C * sum loss + ||W||_1 of the returned point, whether the residual reached ``kkt_tol``, and the step bound L the
+    backtracking ended at."""
+
+    coef_: torch.Tensor
+    intercept_: torch.Tensor
+    classes_: torch.Tensor
+    n_iter_: int
+    kkt_residual_: float
+    objective_: float
+    converged_: bool
+    lipschitz_: float
+    n_rejected_: int = 0
+    n_restarts_: int = 0
+    layout: object = None
+
+
+def l1_logistic(X: torch.Tensor, y: torch.Tensor, C: float, *, kkt_tol: float = 1e-4, max_iter: int = 5000, check_every: int = 25) -> L1LogisticResult:
+    """L1-penalised logistic regression on the device, scikit-learn's ``LogisticRegression(penalty="l1", C=C)`` problem solved to a
+    certified optimum (include/saev_amd.h: SPARSE LINEAR): minimise ``C * sum_i loss_i + ||W||_1`` with an unpenalised
+    intercept.  ``X`` (n, S) float32 on the device, ``y`` (n) int32 / int64 class ids; ``classes_ = unique(y)``.  Two classes give a
+    binary logistic loss with one coefficient row (positive class ``classes_[1]``), three or more a softmax with one row per class.
+    FISTA in fp64 with backtracking and restart; it stops when the KKT residual (the largest of ``|g + sign(w)|`` where ``w != 0``,
+    ``max(|g| - 1, 0)`` where ``w == 0`` and ``|g_b|``, g the gradient of the C-scaled loss) is ``<= kkt_tol``.  The host reads the
+    device's state block once per ``check_every`` iterations; the result does not depend on it.  Running out of ``max_iter`` returns
+    the last iterate with ``converged_ = False`` and a warning.  One class, more than 64, ``C <= 0`` and a non-finite X raise
+    ValueError.  There is no CPU path."""
+    import warnings
+
+    if X.dim() != 2 or y.dim() != 1 or X.shape[0] != y.shape[0] or X.shape[0] < 1 or X.shape[1] < 1:
+        raise ValueError(f"l1_logistic: X must be (n, S) and y (n) with n, S >= 1, got {tuple(X.shape)} and {tuple(y.shape)}")
+    if X.dtype != torch.float32 or y.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"l1_logistic: X must be float32 and y int32 or int64, got {X.dtype} and {y.dtype}")
+    if not (C > 0 and math.isfinite(C)):
+        raise ValueError(f"l1_logistic: C must be positive and finite, got {C}")
+    if not kkt_tol >= 0 or max_iter < 0 or check_every < 1:
+        raise ValueError(f"l1_logistic: kkt_tol >= 0, max_iter >= 0 and check_every >= 1, got {kkt_tol}, {max_iter}, {check_every}")
+    device = X.device
+    if device.type != "cuda" or y.device != device:
+        raise RuntimeError("l1_logistic runs on a HIP device only (there is no CPU path)")
+    n, s = X.shape
+    classes, inverse = torch.unique(y, return_inverse=True)
+    k = int(classes.numel())
+    if k < 2:
+        raise ValueError(f"This solver needs samples of at least 2 classes in the data, but the data contains only one class: {classes.tolist()[0]!r}")
+    if k > 64:
+        raise ValueError(f"l1_logistic: unsupported number of classes {k} (at most 64)")
+    X = X.contiguous()
+    yi = inverse.to(torch.int32).contiguous()
+    lib = _lib.load()
+    layout = _lib.SaevL1LogisticLayout()
+    _lib.check(lib, None, lib.saev_l1_logistic_layout_of(n, s, k, _lib.C.byref(layout)), "saev_l1_logistic_layout_of")
+    ws = torch.empty(layout.total_bytes, device=device, dtype=torch.uint8)
+    common = (_ptr(X), _ptr(yi), n, s, k, float(C), float(kkt_tol))
+    state = ws[layout.off_state:layout.off_state + 128].view(torch.float64)
+    with torch.cuda.device(device):
+        _lib.check(lib, None, lib.saev_l1_logistic_init(*common, _ptr(ws), ws.numel(), _stream()), "saev_l1_logistic_init")
+        code = int(ws[layout.off_err:layout.off_err + 4].view(torch.int32).item())
+        if code != 0:
+            raise ValueError("l1_logistic: " + {1: "X holds a value that is not finite", 2: "a class index lies outside [0, K)"}.get(code, str(code)) + " (found on the device)")
+        left = max_iter
+        while left > 0:
+            step = min(check_every, left)
+            _lib.check(lib, None, lib.saev_l1_logistic_iterate(*common, step, _ptr(ws), ws.numel(), _stream()), "saev_l1_logistic_iterate")
+            left -= step
+            if state[8].item() != 0.0:  # SAEV_L1_STATE_DONE
+                break
+        coef = torch.empty(layout.coef_rows, s, device=device, dtype=torch.float64)
+        intercept = torch.empty(layout.coef_rows, device=device, dtype=torch.float64)
+        scalars = torch.empty(8, device=device, dtype=torch.float64)
+        _lib.check(lib, None, lib.saev_l1_logistic_result(*common, _ptr(coef), _ptr(intercept), _ptr(scalars), _ptr(ws), ws.numel(), _stream()),
+                   "saev_l1_logistic_result")
+        sc = scalars.cpu().tolist()
+    res = L1LogisticResult(coef, intercept, classes, int(sc[0]), float(sc[1]), float(sc[2]), bool(sc[3]), float(sc[4]), int(sc[5]), int(sc[6]), layout)
+    if not res.converged_:
+        warnings.warn(f"l1_logistic: the KKT residual is {res.kkt_residual_:.3g} after {res.n_iter_} iterations (kkt_tol {kkt_tol:g}): not converged",
+                      RuntimeWarning, stacklevel=2)
+    return res
+
+
 @dataclasses.dataclass
 class StepStats:
     mse: float
