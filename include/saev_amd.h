@@ -879,6 +879,48 @@ int saev_latent_ap_layout_of(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_
 int saev_latent_ap(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
                    const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, double* ap, int64_t* pos, double* best_ap,
                    int32_t* best_class, void* workspace, int64_t workspace_bytes, void* stream);
+/* PROBE AP (the reference's contrib/trait_discovery tdiscovery.metrics: the fitted probes of PROBE1D scored on another split),
+ * context-free; DESIGN.md 3.21.  For every pair (j, c) with w = w[j, c] and b = b[j, c]: the exact tie-aware AP of the score
+ * w * a + b of latent j as a detector of class c over N rows, the counts behind precision and recall at the threshold s > 0, and
+ * the top rows of every latent.
+ * CARRIED OVER FROM LATENT AP UNCHANGED: x, the shapes and their limits, the two label forms, the event rule (a stored +-0.0 is no
+ * event), term(g, c), dH, direct_max, pos_c, the arithmetic and the order of addition, the workspace
+ * (saev_latent_ap_workspace_bytes(N, S, C, nnz), the same layout, the same sorted arrays left behind), the argument checks before
+ * the device is touched, saev_last_error(NULL); nothing is allocated, nothing is read back, nothing synchronises; integer atomics
+ * only.
+ * SCORE: s(a) = fl(fl(w * a) + b) in the arithmetic of score_dtype (0 = fp32, 1 = fp64; w and b are S x C arrays of that type), each
+ * operation rounded on its own, no contraction; in fp64 a is converted exactly -- what numpy computes for
+ * acts.astype(float32) * w + b.  A row without an event has a = 0, so s = b.  With finite a, w and b no NaN arises; w * a may
+ * overflow to +-Inf, an ordinary ordered value.
+ * VOID PAIR: if w or b is not finite, ap = NaN and tp = pred_pos = 0 (also when pos_c = 0); the error word is not set and no other
+ * pair is touched.
+ * RANKING: all N rows by s, descending.  A TIE GROUP is a maximal set of rows of equal s (== in the score's type, so +0 == -0).
+ * TIES ARE DEFINED ON THE ROUNDED SCORE, not on the activation: the score is what a user of the probe ranks by, and two rows whose
+ * scores round to the same number cannot be told apart by it.  s is monotone in a (non-decreasing for w > 0, non-increasing for
+ * w < 0), so the groups are runs of the value-sorted events: walked by descending value for w > 0, by ascending value for w < 0;
+ * w == +-0 gives one group of N rows.  The Z_j rows without an event enter as ONE BLOCK at a = 0 with score b -- behind the positive
+ * events and before the negative ones for w > 0, the mirror image for w < 0 (so FIRST when every event is positive) -- and the
+ * block MERGES with the neighbouring events whose score equals b (|w a| < ulp(b) / 2 makes such neighbours).
+ * t, n, r, R of a group and AP[j, c] = (sum over g of term(g, c)) / pos_c (0 when pos_c = 0) are LATENT AP's, in the group order
+ * of this ranking.
+ * COUNTS: pred_pos = the rows with s > 0 (the zero block counts when b > 0), tp = those of them that belong to class c; exact
+ * integers.
+ * DETERMINISM: a pair's bits depend on its own events, w and b only -- not on other pairs, C, the launch or timing; two calls give
+ * the same bits.  With w = 1, b = 0 the ranking is LATENT AP's and so are the bits of ap.
+ * TOP ROWS (top_k > 0): top_row[j, i] for i < min(top_k, m_j) = the row of latent j's i-th event in (value descending, row
+ * ascending) order, and 0 for the remaining i (the padding of csr_topk(axis=0)); any top_k up to N.
+ * OUTPUTS (device): ap (S x C fp64), pos (C int64), tp and pred_pos (S x C int64), top_row (S x top_k int64, or top_k = 0 and NULL).
+ * top_k < 0 or top_k > N, a score_dtype other than 0 or 1, and a NULL w, b, ap, pos, tp or pred_pos are SAEV_INVALID_ARG.  err is
+ * int32[0] at off_err of the workspace: 0, or the largest of SAEV_LATENT_AP_ERR_CLASS, SAEV_LATENT_AP_ERR_LATENT and
+ * SAEV_PROBE_AP_ERR_VALUE (a stored value that is not finite: unlike LATENT AP, +-Inf is refused, for Inf * w + b need not be
+ * ordered) met on the device; the outputs are void if it is not 0. */
+#define SAEV_PROBE_AP_ERR_VALUE 3
+int saev_probe_ap(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+                  const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32,
+                  const void* w, const void* b, int32_t score_dtype,          /* S x C each; 0 = fp32, 1 = fp64 */
+                  double* ap, int64_t* pos, int64_t* tp, int64_t* pred_pos,   /* S x C, C, S x C, S x C */
+                  int32_t top_k, int64_t* top_row,                            /* S x top_k, or top_k = 0 and NULL */
+                  void* workspace, int64_t workspace_bytes, void* stream);
 /* SPARSE LINEAR (the training half of the concept audit, the reference's contrib/trait_discovery tdiscovery.classification:
  * aggregate_to_images and the LogisticRegression(penalty="l1") of train_worker_fn), context-free; DESIGN.md 3.20.
  *

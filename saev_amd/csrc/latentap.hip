@@ -22,6 +22,14 @@
 //            sort, no array per (event, class), and a pair's sum is a plain left-to-right sum in group order.
 //   best     a wave per latent: the row maximum of ap and the lowest column that attains it.
 //
+// PROBE AP (include/saev_amd.h: PROBE AP) shares the sort (la_sort) and ranks by the per-pair score fl(fl(w a) + b):
+//   probe    lane = class as above, but every lane has its own w and b and so its own tie groups: a group is closed per lane, with
+//            no cross-lane operation under that branch (the shuffles that hand the 64 loaded events round stay at the top level of
+//            the loop).  The events are walked by descending value for the lanes with w >= 0 and by ascending value for those with
+//            w < 0 -- a direction no lane of the wave needs is skipped -- and the zero rows enter at a = 0 as one block that merges
+//            with the neighbours whose rounded score equals b.
+//   top rows a gather from row and starts.
+//
 // Integer atomics only (digit counts in LDS, class counts, the error word); nothing is read back, nothing synchronises.
 #include "common.h"
 #include "kernels.h"
@@ -375,6 +383,190 @@ __global__ __launch_bounds__(256) void la_best_kernel(const double* __restrict__
     }
 }
 
+// the sorted events of a workspace: what la_sort leaves at off_starts, off_key and off_row
+struct LaSorted {
+    const int64_t* starts;
+    const uint32_t* key;
+    const int32_t* row;
+};
+
+// init, the radix passes and starts, enqueued on s: both entries sort with this
+LaSorted la_sort(const saev_latent_ap_layout& L, uint8_t* ws, const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz,
+                 int64_t N, int64_t S, hipStream_t s) {
+    int32_t* err = reinterpret_cast<int32_t*>(ws + L.off_err);
+    int64_t* starts = reinterpret_cast<int64_t*>(ws + L.off_starts);
+    int32_t* hist = reinterpret_cast<int32_t*>(ws + L.off_hist);
+    int32_t* total = hist + 256 * L.parts;
+    // the sort ends in (key, latent, row); it starts there when the number of passes is even
+    uint32_t* key[2] = {reinterpret_cast<uint32_t*>(ws + L.off_key), reinterpret_cast<uint32_t*>(ws + L.off_key2)};
+    uint32_t* lat[2] = {reinterpret_cast<uint32_t*>(ws + L.off_latent), reinterpret_cast<uint32_t*>(ws + L.off_latent2)};
+    int32_t* row[2] = {reinterpret_cast<int32_t*>(ws + L.off_row), reinterpret_cast<int32_t*>(ws + L.off_row2)};
+    int at = (int)(L.passes & 1);
+    if (nnz > 0) {
+        const int parts = (int)((nnz + L.part_len - 1) / L.part_len);
+        const int grid = (int)std::min<int64_t>((nnz + 255) / 256, 8192);
+        hipLaunchKernelGGL(la_init_kernel, dim3(grid), dim3(256), 0, s, row_ptr, indices, data, (long)nnz, (int)N, (int)S, key[at], lat[at], row[at],
+                           err);
+        for (int p = 0; p < (int)L.passes; ++p) {
+            const int by_latent = p >= 4 ? 1 : 0, shift = 8 * (by_latent ? p - 4 : p);
+            hipLaunchKernelGGL(la_hist_kernel, dim3(parts), dim3(64), 0, s, by_latent ? lat[at] : key[at], (long)nnz, (long)L.part_len, shift, parts,
+                               hist);
+            hipLaunchKernelGGL(la_scan_kernel, dim3(256), dim3(LA_SCAN_THREADS), 0, s, hist, parts, total);
+            hipLaunchKernelGGL(la_scatter_kernel, dim3(parts), dim3(64), 0, s, key[at], lat[at], row[at], key[at ^ 1], lat[at ^ 1], row[at ^ 1],
+                               (long)nnz, (long)L.part_len, shift, by_latent, parts, hist, total);
+            at ^= 1;
+        }
+    }
+    hipLaunchKernelGGL(la_starts_kernel, dim3((unsigned)((S + 1 + 255) / 256)), dim3(256), 0, s, lat[0], (long)nnz, (int)S, starts);
+    return LaSorted{starts, key[0], row[0]};
+}
+
+// ---------------------------------------------------------------- probe ------------------------------------------------------------------
+
+// s(a) = fl(fl(w a) + b) in the score's arithmetic, each operation rounded on its own (a fused multiply-add changes which scores tie)
+__device__ __forceinline__ float pa_score(float w, float a, float b) { return __fadd_rn(__fmul_rn(w, a), b); }
+__device__ __forceinline__ double pa_score(double w, float a, double b) { return __dadd_rn(__dmul_rn(w, (double)a), b); }
+
+__global__ __launch_bounds__(256) void pa_values_kernel(const int64_t* __restrict__ row_ptr, const float* __restrict__ data, long nnz,
+                                                        int32_t* __restrict__ err) {
+    const int64_t p0 = row_ptr[0];
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (long)gridDim.x * 256)
+        if (!isfinite(data[p0 + e])) atomicMax(err, SAEV_PROBE_AP_ERR_VALUE);
+}
+
+struct PaTerms {
+    LaTerms la;
+    const void* w;
+    const void* b;
+    long long* tp;
+    long long* pred_pos;
+};
+
+// a wave per (latent, 64 classes), lane = class = pair.  grid: (ceil(S / 4), ceil(C / 64))
+template <typename T>
+__global__ __launch_bounds__(256) void pa_terms_kernel(PaTerms p) {
+#pragma clang fp contract(off)
+    const LaTerms& a = p.la;
+    const int lane = threadIdx.x & 63;
+    const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= a.S) return;
+    const int c = blockIdx.y * 64 + lane;
+    const bool active = c < a.C;
+    const int64_t s0 = a.starts[j], s1 = a.starts[j + 1];
+    const long Z = (long)a.N - (long)(s1 - s0);
+    const long posc = active ? (long)a.pos[c] : 0;
+    T w = (T)0, b = (T)0;
+    if (active) {
+        w = static_cast<const T*>(p.w)[(size_t)j * a.C + c];
+        b = static_cast<const T*>(p.b)[(size_t)j * a.C + c];
+    }
+    const bool live = active && isfinite(w) && isfinite(b);  // (a void pair walks nothing)
+    const bool fwd = live && w >= (T)0, bwd = live && w < (T)0;
+    const bool any_fwd = __any(fwd), any_bwd = __any(bwd);
+
+    // the zero block's r is pos_c minus the pair's events; it is needed before the walk unless the block comes last in it: in the
+    // descending walk of a latent with negative events, and in every ascending walk.  The lanes that walk ascending count while the
+    // others walk descending; a pass of its own is made only where that is too late or does not happen
+    const bool has_neg = s1 > s0 && a.key[s1 - 1] >= 0x80000000u;
+    const bool count_first = has_neg || (any_bwd && !any_fwd);
+    const bool counted = bwd || count_first;
+    long mine = 0;
+    if (count_first) {
+        for (int64_t base = s0; base < s1; base += 64) {
+            const int64_t e = base + lane;
+            const int cl = e < s1 ? la_class(a.u8, a.remap, a.i32, a.row[e], a.C) : -1;
+            const int cnt = (int)min((int64_t)64, s1 - base);
+            for (int i = 0; i < cnt; ++i) {
+                const int ci = __shfl(cl, i, 64);
+                mine += (active && ci == c) ? 1 : 0;
+            }
+        }
+    }
+
+    // everything below the shuffles is per lane: a lane closes its groups where ITS score changes
+    double acc = 0.0;
+    long t = 0, n = 0, R = 0, r = 0, hit = 0, pred = 0;
+    T curs = (T)0;
+    bool zero_done = false;
+    const auto close_group = [&]() {  // (n > 0)
+        if (r > 0) acc = acc + la_term(t, n, R, r, n > LA_DIRECT_MAX ? la_dh(t, n) : 0.0);
+        R += r;
+        t += n;
+        r = 0;
+        n = 0;
+    };
+    const auto feed = [&](T s, long rows, long of_class) {
+        if (n > 0 && s != curs) close_group();
+        curs = s;
+        n += rows;
+        r += of_class;
+        if (s > (T)0) { pred += rows; hit += of_class; }
+    };
+    const auto zero_block = [&]() {  // the Z rows without an event, at a = 0; it joins the open group when the scores are equal
+        zero_done = true;
+        if (Z <= 0) return;
+        feed(pa_score(w, 0.f, b), Z, min(max(posc - (counted ? mine : R + r), 0L), Z));
+    };
+
+    if (any_fwd) {  // by descending value: the positive events, the zero block, the negative events
+        for (int64_t base = s0; base < s1; base += 64) {
+            const int64_t e = base + lane;
+            float myv = 0.f;
+            int mycl = -1;
+            if (e < s1) { myv = ukey2f(~a.key[e]); mycl = la_class(a.u8, a.remap, a.i32, a.row[e], a.C); }
+            const int cnt = (int)min((int64_t)64, s1 - base);
+            for (int i = 0; i < cnt; ++i) {
+                const float v = __shfl(myv, i, 64);
+                const int cl = __shfl(mycl, i, 64);
+                if (fwd) {
+                    if (!zero_done && !(v > 0.f)) zero_block();
+                    feed(pa_score(w, v, b), 1, cl == c ? 1 : 0);
+                } else if (bwd && !count_first) {
+                    mine += cl == c ? 1 : 0;
+                }
+            }
+        }
+        if (fwd && !zero_done) zero_block();
+    }
+    if (any_bwd) {  // by ascending value: the same events from the far end, in chunks [top - 64, top) that end at s0
+        for (int64_t top = s1; top > s0; top -= 64) {
+            const int64_t base = max(s0, top - 64);
+            const int cnt = (int)(top - base);
+            float myv = 0.f;
+            int mycl = -1;
+            if (lane < cnt) { myv = ukey2f(~a.key[base + lane]); mycl = la_class(a.u8, a.remap, a.i32, a.row[base + lane], a.C); }
+            for (int i = cnt - 1; i >= 0; --i) {
+                const float v = __shfl(myv, i, 64);
+                const int cl = __shfl(mycl, i, 64);
+                if (bwd) {
+                    if (!zero_done && !(v < 0.f)) zero_block();
+                    feed(pa_score(w, v, b), 1, cl == c ? 1 : 0);
+                }
+            }
+        }
+        if (bwd && !zero_done) zero_block();
+    }
+    if (n > 0) close_group();
+    if (active) {
+        const size_t at = (size_t)j * a.C + c;
+        a.ap[at] = !live ? __longlong_as_double(0x7ff8000000000000LL) : posc > 0 ? acc / (double)posc : 0.0;
+        p.tp[at] = hit;
+        p.pred_pos[at] = pred;
+    }
+}
+
+// top_row[j][i] = the row of latent j's i-th event, 0 behind its last
+__global__ __launch_bounds__(256) void pa_top_rows_kernel(const int64_t* __restrict__ starts, const int32_t* __restrict__ row, long S, int top_k,
+                                                          long long* __restrict__ top_row) {
+    const long total = S * (long)top_k;
+    for (long at = (long)blockIdx.x * 256 + threadIdx.x; at < total; at += (long)gridDim.x * 256) {
+        const long j = at / top_k;
+        const int i = (int)(at - j * top_k);
+        const int64_t e = starts[j] + i;
+        top_row[at] = e < starts[j + 1] ? (long long)row[e] : 0ll;
+    }
+}
+
 }  // namespace
 
 int64_t saev_latent_ap_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t nnz) {
@@ -414,40 +606,66 @@ int saev_latent_ap(const int64_t* row_ptr, const int32_t* indices, const float* 
     hipStream_t s = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
     int32_t* err = reinterpret_cast<int32_t*>(ws + L.off_err);
-    int64_t* starts = reinterpret_cast<int64_t*>(ws + L.off_starts);
-    int32_t* hist = reinterpret_cast<int32_t*>(ws + L.off_hist);
-    int32_t* total = hist + 256 * L.parts;
-    // the sort ends in (key, latent, row); it starts there when the number of passes is even
-    uint32_t* key[2] = {reinterpret_cast<uint32_t*>(ws + L.off_key), reinterpret_cast<uint32_t*>(ws + L.off_key2)};
-    uint32_t* lat[2] = {reinterpret_cast<uint32_t*>(ws + L.off_latent), reinterpret_cast<uint32_t*>(ws + L.off_latent2)};
-    int32_t* row[2] = {reinterpret_cast<int32_t*>(ws + L.off_row), reinterpret_cast<int32_t*>(ws + L.off_row2)};
     unsigned long long* upos = reinterpret_cast<unsigned long long*>(pos);
 
     bool ok = hipMemsetAsync(err, 0, 64, s) == hipSuccess;
     ok = ok && hipMemsetAsync(pos, 0, (size_t)(8 * C), s) == hipSuccess;
     if (!ok) return refuse(SAEV_HIP_ERROR, "saev_latent_ap: hipMemsetAsync failed");
     hipLaunchKernelGGL(la_labels_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, class_u8, remap, class_i32, (int)N, (int)C, upos, err);
-    int at = (int)(L.passes & 1);
-    if (nnz > 0) {
-        const int parts = (int)((nnz + L.part_len - 1) / L.part_len);
-        const int grid = (int)std::min<int64_t>((nnz + 255) / 256, 8192);
-        hipLaunchKernelGGL(la_init_kernel, dim3(grid), dim3(256), 0, s, row_ptr, indices, data, (long)nnz, (int)N, (int)S, key[at], lat[at], row[at],
-                           err);
-        for (int p = 0; p < (int)L.passes; ++p) {
-            const int by_latent = p >= 4 ? 1 : 0, shift = 8 * (by_latent ? p - 4 : p);
-            hipLaunchKernelGGL(la_hist_kernel, dim3(parts), dim3(64), 0, s, by_latent ? lat[at] : key[at], (long)nnz, (long)L.part_len, shift, parts,
-                               hist);
-            hipLaunchKernelGGL(la_scan_kernel, dim3(256), dim3(LA_SCAN_THREADS), 0, s, hist, parts, total);
-            hipLaunchKernelGGL(la_scatter_kernel, dim3(parts), dim3(64), 0, s, key[at], lat[at], row[at], key[at ^ 1], lat[at ^ 1], row[at ^ 1],
-                               (long)nnz, (long)L.part_len, shift, by_latent, parts, hist, total);
-            at ^= 1;
-        }
-    }
-    hipLaunchKernelGGL(la_starts_kernel, dim3((unsigned)((S + 1 + 255) / 256)), dim3(256), 0, s, lat[0], (long)nnz, (int)S, starts);
-    LaTerms a{starts, key[0], row[0], class_u8, remap, class_i32, upos, ap, (int)N, (int)S, (int)C};
+    const LaSorted e = la_sort(L, ws, row_ptr, indices, data, nnz, N, S, s);
+    LaTerms a{e.starts, e.key, e.row, class_u8, remap, class_i32, upos, ap, (int)N, (int)S, (int)C};
     hipLaunchKernelGGL(la_terms_kernel, dim3((unsigned)((S + 3) / 4), (unsigned)((C + 63) / 64)), dim3(256), 0, s, a);
     if (best_ap || best_class)
         hipLaunchKernelGGL(la_best_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, ap, (int)S, (int)C, best_ap, best_class);
     if (hipGetLastError() != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_latent_ap: kernel launch failed");
+    return SAEV_OK;
+}
+
+int saev_probe_ap(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+                  const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, const void* w, const void* b, int32_t score_dtype,
+                  double* ap, int64_t* pos, int64_t* tp, int64_t* pred_pos, int32_t top_k, int64_t* top_row, void* workspace,
+                  int64_t workspace_bytes, void* stream) {
+    const auto refuse = [](int code, const char* msg) { return free_refuse(code, msg); };
+    if (N < 0 || S < 0 || C < 0 || nnz < 0) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: negative size");
+    if (N > 0x7fffffffLL || S > 0x7fffffffLL || nnz > 0x7fffffffLL) return refuse(SAEV_UNSUPPORTED, "saev_probe_ap: N, S and nnz must stay below 2^31");
+    if (N < 1 || S < 1) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: N and S must be at least 1");
+    if (C < 1 || C > LA_MAX_C) return refuse(SAEV_UNSUPPORTED, "saev_probe_ap: the number of classes must lie in [1, 4096]");
+    if (!row_ptr) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: row_ptr is NULL");
+    if (nnz > 0 && (!indices || !data)) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: indices and data come with nnz > 0");
+    if ((class_u8 != nullptr) == (class_i32 != nullptr))
+        return refuse(SAEV_INVALID_ARG, "saev_probe_ap: give the classes as class_u8 (with an optional remap) or as class_i32, one of the two");
+    if (remap && !class_u8) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: remap goes with class_u8");
+    if (!w || !b) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: w and b must not be NULL");
+    if (score_dtype != 0 && score_dtype != 1) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: score_dtype is 0 (fp32) or 1 (fp64)");
+    if (!ap || !pos || !tp || !pred_pos) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: ap, pos, tp and pred_pos must not be NULL");
+    if (top_k < 0 || (int64_t)top_k > N) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: top_k must lie in [0, N]");
+    if (top_k > 0 && !top_row) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: top_row comes with top_k > 0");
+    saev_latent_ap_layout L;
+    la_layout(S, C, nnz, &L);
+    if (!workspace || workspace_bytes < L.total_bytes)
+        return refuse(SAEV_INVALID_ARG, "saev_probe_ap: workspace smaller than saev_latent_ap_workspace_bytes(N, S, C, nnz)");
+    if (((uintptr_t)workspace & 255) != 0) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: workspace must be 256-byte aligned");
+
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    int32_t* err = reinterpret_cast<int32_t*>(ws + L.off_err);
+    unsigned long long* upos = reinterpret_cast<unsigned long long*>(pos);
+
+    bool ok = hipMemsetAsync(err, 0, 64, s) == hipSuccess;
+    ok = ok && hipMemsetAsync(pos, 0, (size_t)(8 * C), s) == hipSuccess;
+    if (!ok) return refuse(SAEV_HIP_ERROR, "saev_probe_ap: hipMemsetAsync failed");
+    hipLaunchKernelGGL(la_labels_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, class_u8, remap, class_i32, (int)N, (int)C, upos, err);
+    if (nnz > 0)
+        hipLaunchKernelGGL(pa_values_kernel, dim3((unsigned)std::min<int64_t>((nnz + 255) / 256, 8192)), dim3(256), 0, s, row_ptr, data, (long)nnz, err);
+    const LaSorted e = la_sort(L, ws, row_ptr, indices, data, nnz, N, S, s);
+    PaTerms a{{e.starts, e.key, e.row, class_u8, remap, class_i32, upos, ap, (int)N, (int)S, (int)C}, w, b, reinterpret_cast<long long*>(tp),
+              reinterpret_cast<long long*>(pred_pos)};
+    const dim3 grid((unsigned)((S + 3) / 4), (unsigned)((C + 63) / 64));
+    if (score_dtype == 0) hipLaunchKernelGGL(pa_terms_kernel<float>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(pa_terms_kernel<double>, grid, dim3(256), 0, s, a);
+    if (top_k > 0)
+        hipLaunchKernelGGL(pa_top_rows_kernel, dim3((unsigned)std::min<int64_t>((S * (int64_t)top_k + 255) / 256, 8192)), dim3(256), 0, s, e.starts,
+                           e.row, (long)S, (int)top_k, reinterpret_cast<long long*>(top_row));
+    if (hipGetLastError() != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_probe_ap: kernel launch failed");
     return SAEV_OK;
 }

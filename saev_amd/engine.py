@@ -929,6 +929,100 @@ def latent_ap(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n
     return LatentAPResult(ap, n_pos, best_ap, best_class, ws, layout, (n_rows, n_latents, n_classes, nnz))
 
 
+class ProbeAPResult:
+    """What ``probe_ap`` leaves on the device: ``ap`` (S, C) float64 (NaN for a pair whose w or b is not finite), ``n_pos`` (C) int64,
+    ``tp`` and ``n_pred_pos`` (S, C) int64 (rows with score > 0, and those of them in the class) and ``top_rows`` (S, top_k) int64 or
+    None.  The call itself does not synchronise; the first read of a result -- or ``check()`` -- reads the device's error word (one
+    synchronisation) and raises ValueError if it is not 0.  ``layout`` is the workspace's, as of ``latent_ap``
+    (include/saev_amd.h: PROBE AP)."""
+
+    _ERRORS = {**LatentAPResult._ERRORS, 3: "a stored value is not finite"}
+
+    def __init__(self, ap, n_pos, tp, n_pred_pos, top_rows, ws, layout, shape):
+        self._out = dict(ap=ap, n_pos=n_pos, tp=tp, n_pred_pos=n_pred_pos, top_rows=top_rows)
+        self._ws, self.layout, self.shape = ws, layout, shape
+        self._checked = False
+
+    def check(self) -> None:
+        if not self._checked:
+            code = int(self._ws[self.layout.off_err:self.layout.off_err + 4].view(torch.int32).item())
+            if code != 0:
+                raise ValueError(f"probe_ap: {self._ERRORS.get(code, code)} (found on the device)")
+            self._checked = True
+
+    def _read(self, name):
+        self.check()
+        return self._out[name]
+
+    ap = property(lambda self: self._read("ap"))
+    n_pos = property(lambda self: self._read("n_pos"))
+    tp = property(lambda self: self._read("tp"))
+    n_pred_pos = property(lambda self: self._read("n_pred_pos"))
+    top_rows = property(lambda self: self._read("top_rows"))
+
+    sorted_events = LatentAPResult.sorted_events
+
+
+def probe_ap(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_rows: int, n_latents: int, n_classes: int, *,
+             labels: torch.Tensor, remap: torch.Tensor | None = None, weights: torch.Tensor, biases: torch.Tensor, top_k: int = 0,
+             nnz: int | None = None) -> ProbeAPResult:
+    """Exact tie-aware average precision of the score ``w * a + b`` of every (latent, class) pair, the counts behind precision and
+    recall at score > 0, and the ``top_k`` highest rows of every latent (include/saev_amd.h: PROBE AP).  x, ``labels``,
+    ``remap`` and ``nnz`` as for ``latent_ap``; ``weights`` and ``biases`` (S, C), both float32 or both float64: their dtype is the
+    arithmetic the score is rounded in.  One call, one workspace, no synchronisation; there is no CPU path."""
+    for name, v, hi in (("n_rows", n_rows, 2**31), ("n_latents", n_latents, 2**31), ("n_classes", n_classes, 4097)):
+        if not 1 <= v < hi:
+            raise ValueError(f"probe_ap: unsupported {name} {v} (1 <= {name} < {hi})")
+    if not 0 <= top_k <= n_rows:
+        raise ValueError(f"probe_ap: top_k {top_k} must lie in [0, n_rows = {n_rows}]")
+    device = indptr.device
+    if device.type != "cuda":
+        raise RuntimeError("probe_ap runs on a HIP device only (there is no CPU path)")
+    stored = indices.numel()
+    nnz = stored if nnz is None else int(nnz)
+    if not 0 <= nnz < 2**31 or nnz > stored:
+        raise ValueError(f"probe_ap: unsupported nnz {nnz} (0 <= nnz < 2^31, and at most the {stored} entries of indices)")
+
+    def on(t, dtype, shape, what):
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device:
+            raise ValueError(f"{what} must be {dtype} of shape {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.contiguous()
+
+    indptr = on(indptr, torch.int64, (n_rows + 1,), "indptr")
+    indices = on(indices, torch.int32, (stored,), "indices")
+    data = on(data, torch.float32, (stored,), "data")
+    if weights.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"weights must be float32 or float64, got {weights.dtype}")
+    weights = on(weights, weights.dtype, (n_latents, n_classes), "weights")
+    biases = on(biases, weights.dtype, (n_latents, n_classes), "biases")
+    u8 = i32 = None
+    if labels.dtype == torch.uint8:
+        u8 = on(labels, torch.uint8, (n_rows,), "labels")
+        if remap is not None:
+            remap = on(remap, torch.int32, (256,), "remap")
+    elif labels.dtype in (torch.int32, torch.int64):
+        if remap is not None:
+            raise ValueError("probe_ap: remap goes with uint8 labels")
+        i32 = on(labels.to(torch.int32), torch.int32, (n_rows,), "labels")
+    else:
+        raise ValueError(f"labels must be uint8, int32 or int64, got {labels.dtype}")
+    lib = _lib.load()
+    layout = _lib.SaevLatentAPLayout()
+    _lib.check(lib, None, lib.saev_latent_ap_layout_of(n_rows, n_latents, n_classes, nnz, C.byref(layout)), "saev_latent_ap_layout_of")
+    ws = torch.empty(layout.total_bytes, device=device, dtype=torch.uint8)
+    ap = torch.empty(n_latents, n_classes, device=device, dtype=torch.float64)
+    n_pos = torch.empty(n_classes, device=device, dtype=torch.int64)
+    tp = torch.empty(n_latents, n_classes, device=device, dtype=torch.int64)
+    n_pred_pos = torch.empty(n_latents, n_classes, device=device, dtype=torch.int64)
+    top_rows = torch.empty(n_latents, top_k, device=device, dtype=torch.int64) if top_k > 0 else None
+    with torch.cuda.device(device):
+        rc = lib.saev_probe_ap(_ptr(indptr), _ptr(indices), _ptr(data), nnz, n_rows, n_latents, n_classes, _ptr(u8), _ptr(remap), _ptr(i32),
+                               _ptr(weights), _ptr(biases), 0 if weights.dtype == torch.float32 else 1, _ptr(ap), _ptr(n_pos), _ptr(tp),
+                               _ptr(n_pred_pos), top_k, _ptr(top_rows), _ptr(ws), ws.numel(), _stream())
+    _lib.check(lib, None, rc, "saev_probe_ap")
+    return ProbeAPResult(ap, n_pos, tp, n_pred_pos, top_rows, ws, layout, (n_rows, n_latents, n_classes, nnz))
+
+
 class PoolResult:
     """What ``pool_images`` leaves on the device: ``pooled`` (n_images, n_latents) float32.  The call itself does not synchronise; the
     first read of ``pooled`` reads the device's error word (one synchronisation) and raises ValueError if it is not 0.  ``ranges`` is
