@@ -40,6 +40,16 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// inclusive prefix sum over the wave: lane i gets the sum of lanes 0 .. i (`lane` is the caller's lane id)
+template <typename T>
+__device__ __forceinline__ T wave_scan_incl(T v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T up = __shfl_up(v, o, 64);
+        if (lane >= o) v += up;
+    }
+    return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

@@ -855,7 +855,7 @@ hipError_t launch_kmeans_collapsed(const float* C, int k, int D, float tol, cons
 // ---- Batch statistics (batchstats.hip: kernels and their C entries) ---------------------------------------------------------
 // message of the last refused context-free call on this thread ("null context" before any): what saev_last_error(NULL) returns
 const char* free_error();
-// leaves `msg` there and returns `code`: how a context-free entry of another file refuses a call (latenttopk.hip)
+// leaves `msg` there and returns `code`: what entry_refuse (entry_util.h) ends in, for the context-free entries of the other files
 int free_refuse(int code, const char* msg);
 
 // ---- Per-latent logistic probes (probe1d.hip: kernels and their C entries; include/saev_amd.h: PROBE1D) ------------------------

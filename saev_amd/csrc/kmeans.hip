@@ -344,12 +344,7 @@ __global__ __launch_bounds__(256, 2) void km_filter_kernel(KmDev a) {
                         }
                     }
             }
-            int incl = cnt;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int v = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += v;
-            }
+            const int incl = wave_scan_incl(cnt, lane);
             const int tot = __shfl(incl, 63, 64);
             if (tot > 0) {  // (wave-uniform)
                 u64 base = 0;
@@ -531,12 +526,7 @@ __global__ __launch_bounds__(256) void km_sort_kernel(const int32_t* __restrict_
                 for (int e = 0; e < 16; ++e)
                     if (i0 + e < n && index[i0 + e] == j) hit |= 1u << e;
                 const int cnt = __popc(hit);
-                int incl = cnt;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int v = __shfl_up(incl, o, 64);
-                    if (lane >= o) incl += v;
-                }
+                const int incl = wave_scan_incl(cnt, lane);
                 if (lane == 63) wsum[w] = incl;
                 __syncthreads();
                 int off = base + incl - cnt, tot = 0;

@@ -31,8 +31,7 @@
 //   top rows a gather from row and starts.
 //
 // Integer atomics only (digit counts in LDS, class counts, the error word); nothing is read back, nothing synchronises.
-#include "common.h"
-#include "kernels.h"
+#include "entry_util.h"
 
 #include <algorithm>
 #include <cstring>
@@ -42,13 +41,6 @@ namespace {
 constexpr int LA_H_SMALL = 32;        // below this t the first terms of H_{t+n} - H_t are added directly
 constexpr int LA_MAX_PARTS = 2048;
 constexpr int LA_SCAN_THREADS = 256;
-constexpr int LA_MAX_C = 4096;
-
-int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
-
-bool la_shape_ok(int64_t N, int64_t S, int64_t C, int64_t nnz) {
-    return N >= 1 && N <= 0x7fffffffLL && S >= 1 && S <= 0x7fffffffLL && C >= 1 && C <= LA_MAX_C && nnz >= 0 && nnz <= 0x7fffffffLL;
-}
 
 int la_latent_passes(int64_t S) { return S < (1 << 8) ? 1 : S < (1 << 16) ? 2 : S < (1 << 24) ? 3 : 4; }  // bytes that hold the value S
 
@@ -59,18 +51,17 @@ void la_layout(int64_t S, int64_t C, int64_t nnz, saev_latent_ap_layout* L) {
     L->parts = std::max<int64_t>(1, std::min<int64_t>(LA_MAX_PARTS, (nnz + 63) / 64));
     L->part_len = std::max<int64_t>(64, ((nnz + L->parts - 1) / L->parts + 63) / 64 * 64);
     L->passes = 4 + la_latent_passes(S);
-    int64_t at = 0;
-    const auto take = [&](int64_t bytes) { const int64_t o = at; at += round256(std::max<int64_t>(bytes, 1)); return o; };
-    L->off_err = take(64);
-    L->off_starts = take(8 * (S + 1));
-    L->off_hist = take(4 * 256 * (L->parts + 1));  // the (digit, part) table and the 256 digit totals behind it
-    L->off_key = take(4 * nnz);
-    L->off_latent = take(4 * nnz);
-    L->off_row = take(4 * nnz);
-    L->off_key2 = take(4 * nnz);
-    L->off_latent2 = take(4 * nnz);
-    L->off_row2 = take(4 * nnz);
-    L->total_bytes = at;
+    WsCarve ws;
+    L->off_err = ws.take(64);
+    L->off_starts = ws.take(8 * (S + 1));
+    L->off_hist = ws.take(4 * 256 * (L->parts + 1));  // the (digit, part) table and the 256 digit totals behind it
+    L->off_key = ws.take(4 * nnz);
+    L->off_latent = ws.take(4 * nnz);
+    L->off_row = ws.take(4 * nnz);
+    L->off_key2 = ws.take(4 * nnz);
+    L->off_latent2 = ws.take(4 * nnz);
+    L->off_row2 = ws.take(4 * nnz);
+    L->total_bytes = ws.at;
     (void)C;
 }
 
@@ -114,14 +105,10 @@ __global__ __launch_bounds__(256) void la_init_kernel(const int64_t* __restrict_
         const float v = data[p];
         const bool ok = col >= 0 && col < S;
         if (!ok) atomicMax(err, SAEV_LATENT_AP_ERR_LATENT);
-        int lo = 0, hi = N;  // the row r with row_ptr[r] <= p < row_ptr[r + 1]
-        while (hi - lo > 1) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (row_ptr[mid] <= p) lo = mid; else hi = mid;
-        }
+        const int r = csr_row_of(row_ptr, N, p);
         key[e] = la_key(v);
         latent[e] = (ok && v != 0.f) ? (uint32_t)col : (uint32_t)S;
-        row[e] = lo;
+        row[e] = r;
     }
 }
 
@@ -149,12 +136,7 @@ __global__ __launch_bounds__(LA_SCAN_THREADS) void la_scan_kernel(int32_t* __res
     const int lo = min(t * per, parts), hi = min(lo + per, parts);
     int sum = 0;
     for (int i = lo; i < hi; ++i) sum += row[i];
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
+    const int inc = wave_scan_incl(sum, lane);
     if (lane == 63) sw[w] = inc;
     __syncthreads();
     int run = inc - sum;
@@ -180,13 +162,7 @@ __global__ __launch_bounds__(64) void la_scatter_kernel(const uint32_t* __restri
         int v[4], sum = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) { v[k] = total[lane * 4 + k]; sum += v[k]; }
-        int inc = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int up = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += up;
-        }
-        int run = inc - sum;
+        int run = wave_scan_incl(sum, lane) - sum;
 #pragma unroll
         for (int k = 0; k < 4; ++k) { cur[lane * 4 + k] = run + hist[(size_t)(lane * 4 + k) * parts + part]; run += v[k]; }
     }
@@ -567,18 +543,56 @@ __global__ __launch_bounds__(256) void pa_top_rows_kernel(const int64_t* __restr
     }
 }
 
+// ---------------------------------------------------------------- host -------------------------------------------------------------------
+
+// what la_open leaves for the rest of an entry
+struct LaOpen {
+    saev_latent_ap_layout L;
+    uint8_t* ws;
+    int32_t* err;
+    unsigned long long* pos;
+    hipStream_t s;
+};
+
+// the front half of both entries: the refusals they share, the layout, err and pos cleared and the class counts enqueued (la_sort
+// is the back half).  `own` is the refusal of the entry's own arguments (NULL: none); it is raised where each entry has always made
+// those checks, behind the label forms and before the workspace
+int la_open(const char* who, const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+            const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, int64_t* pos, const char* own, void* workspace,
+            int64_t workspace_bytes, void* stream, LaOpen* o) {
+    if (const int rc = entry_check_shape(who, N, S, C, nnz)) return rc;
+    if (!row_ptr) return entry_refuse(SAEV_INVALID_ARG, who, "row_ptr is NULL");
+    if (nnz > 0 && (!indices || !data)) return entry_refuse(SAEV_INVALID_ARG, who, "indices and data come with nnz > 0");
+    if ((class_u8 != nullptr) == (class_i32 != nullptr))
+        return entry_refuse(SAEV_INVALID_ARG, who, "give the classes as class_u8 (with an optional remap) or as class_i32, one of the two");
+    if (remap && !class_u8) return entry_refuse(SAEV_INVALID_ARG, who, "remap goes with class_u8");
+    if (own) return entry_refuse(SAEV_INVALID_ARG, who, own);
+    la_layout(S, C, nnz, &o->L);
+    if (const int rc = entry_check_workspace(who, workspace, workspace_bytes, o->L.total_bytes, "workspace smaller than saev_latent_ap_workspace_bytes(N, S, C, nnz)"))
+        return rc;
+    o->s = (hipStream_t)stream;
+    o->ws = static_cast<uint8_t*>(workspace);
+    o->err = reinterpret_cast<int32_t*>(o->ws + o->L.off_err);
+    o->pos = reinterpret_cast<unsigned long long*>(pos);
+    bool ok = hipMemsetAsync(o->err, 0, 64, o->s) == hipSuccess;
+    ok = ok && hipMemsetAsync(pos, 0, (size_t)(8 * C), o->s) == hipSuccess;
+    if (!ok) return entry_refuse(SAEV_HIP_ERROR, who, "hipMemsetAsync failed");
+    hipLaunchKernelGGL(la_labels_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, o->s, class_u8, remap, class_i32, (int)N, (int)C, o->pos, o->err);
+    return SAEV_OK;
+}
+
 }  // namespace
 
 int64_t saev_latent_ap_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t nnz) {
-    if (!la_shape_ok(N, S, C, nnz)) return -1;
+    if (!entry_shape_ok(N, S, C, nnz)) return -1;
     saev_latent_ap_layout L;
     la_layout(S, C, nnz, &L);
     return L.total_bytes;
 }
 
 int saev_latent_ap_layout_of(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_latent_ap_layout* out) {
-    if (!out) return free_refuse(SAEV_INVALID_ARG, "saev_latent_ap_layout_of: no saev_latent_ap_layout");
-    if (!la_shape_ok(N, S, C, nnz)) return free_refuse(SAEV_UNSUPPORTED, "saev_latent_ap_layout_of: 1 <= N, S < 2^31, 1 <= C <= 4096, 0 <= nnz < 2^31");
+    if (!out) return entry_refuse(SAEV_INVALID_ARG, "saev_latent_ap_layout_of", "no saev_latent_ap_layout");
+    if (!entry_shape_ok(N, S, C, nnz)) return entry_refuse(SAEV_UNSUPPORTED, "saev_latent_ap_layout_of", "1 <= N, S < 2^31, 1 <= C <= 4096, 0 <= nnz < 2^31");
     la_layout(S, C, nnz, out);
     return SAEV_OK;
 }
@@ -586,38 +600,18 @@ int saev_latent_ap_layout_of(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_
 int saev_latent_ap(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
                    const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, double* ap, int64_t* pos, double* best_ap,
                    int32_t* best_class, void* workspace, int64_t workspace_bytes, void* stream) {
-    const auto refuse = [](int code, const char* msg) { return free_refuse(code, msg); };
-    if (N < 0 || S < 0 || C < 0 || nnz < 0) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: negative size");
-    if (N > 0x7fffffffLL || S > 0x7fffffffLL || nnz > 0x7fffffffLL) return refuse(SAEV_UNSUPPORTED, "saev_latent_ap: N, S and nnz must stay below 2^31");
-    if (N < 1 || S < 1) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: N and S must be at least 1");
-    if (C < 1 || C > LA_MAX_C) return refuse(SAEV_UNSUPPORTED, "saev_latent_ap: the number of classes must lie in [1, 4096]");
-    if (!row_ptr) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: row_ptr is NULL");
-    if (nnz > 0 && (!indices || !data)) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: indices and data come with nnz > 0");
-    if ((class_u8 != nullptr) == (class_i32 != nullptr))
-        return refuse(SAEV_INVALID_ARG, "saev_latent_ap: give the classes as class_u8 (with an optional remap) or as class_i32, one of the two");
-    if (remap && !class_u8) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: remap goes with class_u8");
-    if (!ap || !pos) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: ap and pos must not be NULL");
-    saev_latent_ap_layout L;
-    la_layout(S, C, nnz, &L);
-    if (!workspace || workspace_bytes < L.total_bytes)
-        return refuse(SAEV_INVALID_ARG, "saev_latent_ap: workspace smaller than saev_latent_ap_workspace_bytes(N, S, C, nnz)");
-    if (((uintptr_t)workspace & 255) != 0) return refuse(SAEV_INVALID_ARG, "saev_latent_ap: workspace must be 256-byte aligned");
-
-    hipStream_t s = (hipStream_t)stream;
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-    int32_t* err = reinterpret_cast<int32_t*>(ws + L.off_err);
-    unsigned long long* upos = reinterpret_cast<unsigned long long*>(pos);
-
-    bool ok = hipMemsetAsync(err, 0, 64, s) == hipSuccess;
-    ok = ok && hipMemsetAsync(pos, 0, (size_t)(8 * C), s) == hipSuccess;
-    if (!ok) return refuse(SAEV_HIP_ERROR, "saev_latent_ap: hipMemsetAsync failed");
-    hipLaunchKernelGGL(la_labels_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, class_u8, remap, class_i32, (int)N, (int)C, upos, err);
-    const LaSorted e = la_sort(L, ws, row_ptr, indices, data, nnz, N, S, s);
-    LaTerms a{e.starts, e.key, e.row, class_u8, remap, class_i32, upos, ap, (int)N, (int)S, (int)C};
+    const char* who = "saev_latent_ap";
+    const char* own = (!ap || !pos) ? "ap and pos must not be NULL" : nullptr;
+    LaOpen o;
+    if (const int rc = la_open(who, row_ptr, indices, data, nnz, N, S, C, class_u8, remap, class_i32, pos, own, workspace, workspace_bytes, stream, &o))
+        return rc;
+    hipStream_t s = o.s;
+    const LaSorted e = la_sort(o.L, o.ws, row_ptr, indices, data, nnz, N, S, s);
+    LaTerms a{e.starts, e.key, e.row, class_u8, remap, class_i32, o.pos, ap, (int)N, (int)S, (int)C};
     hipLaunchKernelGGL(la_terms_kernel, dim3((unsigned)((S + 3) / 4), (unsigned)((C + 63) / 64)), dim3(256), 0, s, a);
     if (best_ap || best_class)
         hipLaunchKernelGGL(la_best_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, ap, (int)S, (int)C, best_ap, best_class);
-    if (hipGetLastError() != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_latent_ap: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");
     return SAEV_OK;
 }
 
@@ -625,40 +619,21 @@ int saev_probe_ap(const int64_t* row_ptr, const int32_t* indices, const float* d
                   const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, const void* w, const void* b, int32_t score_dtype,
                   double* ap, int64_t* pos, int64_t* tp, int64_t* pred_pos, int32_t top_k, int64_t* top_row, void* workspace,
                   int64_t workspace_bytes, void* stream) {
-    const auto refuse = [](int code, const char* msg) { return free_refuse(code, msg); };
-    if (N < 0 || S < 0 || C < 0 || nnz < 0) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: negative size");
-    if (N > 0x7fffffffLL || S > 0x7fffffffLL || nnz > 0x7fffffffLL) return refuse(SAEV_UNSUPPORTED, "saev_probe_ap: N, S and nnz must stay below 2^31");
-    if (N < 1 || S < 1) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: N and S must be at least 1");
-    if (C < 1 || C > LA_MAX_C) return refuse(SAEV_UNSUPPORTED, "saev_probe_ap: the number of classes must lie in [1, 4096]");
-    if (!row_ptr) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: row_ptr is NULL");
-    if (nnz > 0 && (!indices || !data)) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: indices and data come with nnz > 0");
-    if ((class_u8 != nullptr) == (class_i32 != nullptr))
-        return refuse(SAEV_INVALID_ARG, "saev_probe_ap: give the classes as class_u8 (with an optional remap) or as class_i32, one of the two");
-    if (remap && !class_u8) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: remap goes with class_u8");
-    if (!w || !b) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: w and b must not be NULL");
-    if (score_dtype != 0 && score_dtype != 1) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: score_dtype is 0 (fp32) or 1 (fp64)");
-    if (!ap || !pos || !tp || !pred_pos) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: ap, pos, tp and pred_pos must not be NULL");
-    if (top_k < 0 || (int64_t)top_k > N) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: top_k must lie in [0, N]");
-    if (top_k > 0 && !top_row) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: top_row comes with top_k > 0");
-    saev_latent_ap_layout L;
-    la_layout(S, C, nnz, &L);
-    if (!workspace || workspace_bytes < L.total_bytes)
-        return refuse(SAEV_INVALID_ARG, "saev_probe_ap: workspace smaller than saev_latent_ap_workspace_bytes(N, S, C, nnz)");
-    if (((uintptr_t)workspace & 255) != 0) return refuse(SAEV_INVALID_ARG, "saev_probe_ap: workspace must be 256-byte aligned");
-
-    hipStream_t s = (hipStream_t)stream;
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-    int32_t* err = reinterpret_cast<int32_t*>(ws + L.off_err);
-    unsigned long long* upos = reinterpret_cast<unsigned long long*>(pos);
-
-    bool ok = hipMemsetAsync(err, 0, 64, s) == hipSuccess;
-    ok = ok && hipMemsetAsync(pos, 0, (size_t)(8 * C), s) == hipSuccess;
-    if (!ok) return refuse(SAEV_HIP_ERROR, "saev_probe_ap: hipMemsetAsync failed");
-    hipLaunchKernelGGL(la_labels_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, class_u8, remap, class_i32, (int)N, (int)C, upos, err);
+    const char* who = "saev_probe_ap";
+    const char* own = (!w || !b) ? "w and b must not be NULL"
+        : (score_dtype != 0 && score_dtype != 1) ? "score_dtype is 0 (fp32) or 1 (fp64)"
+        : (!ap || !pos || !tp || !pred_pos) ? "ap, pos, tp and pred_pos must not be NULL"
+        : (top_k < 0 || (int64_t)top_k > N) ? "top_k must lie in [0, N]"
+        : (top_k > 0 && !top_row) ? "top_row comes with top_k > 0"
+        : nullptr;
+    LaOpen o;
+    if (const int rc = la_open(who, row_ptr, indices, data, nnz, N, S, C, class_u8, remap, class_i32, pos, own, workspace, workspace_bytes, stream, &o))
+        return rc;
+    hipStream_t s = o.s;
     if (nnz > 0)
-        hipLaunchKernelGGL(pa_values_kernel, dim3((unsigned)std::min<int64_t>((nnz + 255) / 256, 8192)), dim3(256), 0, s, row_ptr, data, (long)nnz, err);
-    const LaSorted e = la_sort(L, ws, row_ptr, indices, data, nnz, N, S, s);
-    PaTerms a{{e.starts, e.key, e.row, class_u8, remap, class_i32, upos, ap, (int)N, (int)S, (int)C}, w, b, reinterpret_cast<long long*>(tp),
+        hipLaunchKernelGGL(pa_values_kernel, dim3((unsigned)std::min<int64_t>((nnz + 255) / 256, 8192)), dim3(256), 0, s, row_ptr, data, (long)nnz, o.err);
+    const LaSorted e = la_sort(o.L, o.ws, row_ptr, indices, data, nnz, N, S, s);
+    PaTerms a{{e.starts, e.key, e.row, class_u8, remap, class_i32, o.pos, ap, (int)N, (int)S, (int)C}, w, b, reinterpret_cast<long long*>(tp),
               reinterpret_cast<long long*>(pred_pos)};
     const dim3 grid((unsigned)((S + 3) / 4), (unsigned)((C + 63) / 64));
     if (score_dtype == 0) hipLaunchKernelGGL(pa_terms_kernel<float>, grid, dim3(256), 0, s, a);
@@ -666,6 +641,6 @@ int saev_probe_ap(const int64_t* row_ptr, const int32_t* indices, const float* d
     if (top_k > 0)
         hipLaunchKernelGGL(pa_top_rows_kernel, dim3((unsigned)std::min<int64_t>((S * (int64_t)top_k + 255) / 256, 8192)), dim3(256), 0, s, e.starts,
                            e.row, (long)S, (int)top_k, reinterpret_cast<long long*>(top_row));
-    if (hipGetLastError() != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_probe_ap: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");
     return SAEV_OK;
 }

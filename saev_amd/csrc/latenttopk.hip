@@ -19,8 +19,7 @@
 //            sequence) and sorted again by the network's last six stages.  The first min(k, entries) lanes are the new list.
 //
 // No floating-point atomic, no n x S temporary, nothing read back, no synchronisation.
-#include "common.h"
-#include "kernels.h"
+#include "entry_util.h"
 
 #include <algorithm>
 #include <cstring>
@@ -59,12 +58,7 @@ __device__ __forceinline__ bool lt_candidate(const LtCodes& c, long e, const flo
     } else {
         const int64_t p = c.row_ptr[0] + e;
         if (p >= c.row_ptr[c.n]) return false;
-        int lo = 0, hi = c.n;  // the row r with row_ptr[r] <= p < row_ptr[r + 1] (empty rows are stepped over)
-        while (hi - lo > 1) {
-            const int mid = lo + ((hi - lo) >> 1);
-            if (c.row_ptr[mid] <= p) lo = mid; else hi = mid;
-        }
-        r = lo;
+        r = csr_row_of(c.row_ptr, c.n, p);
         if (c.keep != nullptr && c.keep[r] == 0) return false;
         i = c.indices[p];
         x = c.data[p];
@@ -92,30 +86,7 @@ __global__ __launch_bounds__(256) void lt_count_kernel(LtCodes c, const float* _
 // time grows with S whatever the number of candidates (the fixed cost of an update)
 __global__ __launch_bounds__(LT_SCAN_THREADS) void lt_scan_kernel(const int32_t* __restrict__ cnt, int S, int32_t* __restrict__ off,
                                                                   int32_t* __restrict__ cur) {
-    __shared__ int sw[LT_SCAN_THREADS / 64];
-    __shared__ int carry_s;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (int base = 0; base < S; base += LT_SCAN_THREADS) {
-        const int l = base + t;
-        const int mine = l < S ? cnt[l] : 0;
-        int inc = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int up = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += up;
-        }
-        if (lane == 63) sw[w] = inc;
-        __syncthreads();
-        int before = carry_s;
-        for (int q = 0; q < w; ++q) before += sw[q];
-        const int start = before + inc - mine;
-        if (l < S) { off[l] = start; cur[l] = start; }
-        __syncthreads();
-        if (t == LT_SCAN_THREADS - 1) carry_s = before + inc;
-        __syncthreads();
-    }
+    block_scan_rounds<LT_SCAN_THREADS, int, int>(S, [&](int l) { return cnt[l]; }, [&](int l, int start) { off[l] = start; cur[l] = start; });
 }
 
 __global__ __launch_bounds__(256) void lt_place_kernel(LtCodes c, const float* __restrict__ top_val, const int32_t* __restrict__ top_cnt,
@@ -192,8 +163,6 @@ __global__ __launch_bounds__(256) void lt_merge_kernel(const int32_t* __restrict
     if (lane == 0) top_cnt[l] = now;
 }
 
-int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 int64_t saev_latent_topk_workspace_bytes(int64_t n_entries, int64_t S) {
@@ -205,27 +174,26 @@ int saev_latent_topk_update(const int32_t* idx, const float* val, const int32_t*
                             const int32_t* indices, const float* data, int64_t nnz, const uint8_t* keep, int64_t n, int64_t S,
                             int64_t row_base, const saev_latent_topk_state* state, void* workspace, int64_t workspace_bytes,
                             void* stream) {
-    const auto refuse = [](int code, const char* msg) { return free_refuse(code, msg); };
-    if (n < 0 || S < 0 || cap < 0 || nnz < 0) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: negative size");
-    if (n > 0x7fffffffLL || S > 0x7fffffffLL || cap > 0x7fffffffLL) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: size above 2^31 - 1");
-    if (!state || state->struct_size < (int32_t)(2 * sizeof(int32_t))) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: no saev_latent_topk_state (or its struct_size is unset)");
+    const char* who = "saev_latent_topk_update";
+    if (n < 0 || S < 0 || cap < 0 || nnz < 0) return entry_refuse(SAEV_INVALID_ARG, who, "negative size");
+    if (n > 0x7fffffffLL || S > 0x7fffffffLL || cap > 0x7fffffffLL) return entry_refuse(SAEV_INVALID_ARG, who, "size above 2^31 - 1");
+    if (!state || state->struct_size < (int32_t)(2 * sizeof(int32_t))) return entry_refuse(SAEV_INVALID_ARG, who, "no saev_latent_topk_state (or its struct_size is unset)");
     saev_latent_topk_state st;
     std::memset(&st, 0, sizeof st);
     std::memcpy(&st, state, std::min<size_t>(sizeof st, (size_t)state->struct_size));
-    if (st.k < 1 || st.k > LT_MAX_K) return refuse(SAEV_UNSUPPORTED, "saev_latent_topk_update: k must lie in [1, 64]");
-    if (!st.top_val || !st.top_row || !st.top_cnt) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: a state pointer is NULL");
+    if (st.k < 1 || st.k > LT_MAX_K) return entry_refuse(SAEV_UNSUPPORTED, who, "k must lie in [1, 64]");
+    if (!st.top_val || !st.top_row || !st.top_cnt) return entry_refuse(SAEV_INVALID_ARG, who, "a state pointer is NULL");
     if (n == 0) return SAEV_OK;
     const bool padded = idx || val, csr = row_ptr || indices || data;
-    if (padded == csr) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: give the codes as padded rows (idx, val) or as CSR (row_ptr, indices, data), one of the two");
-    if (padded && (!idx || !val)) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: idx and val come together");
-    if (csr && (!row_ptr || !indices || !data)) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: row_ptr, indices and data come together");
-    if (csr && row_nnz) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: row_nnz belongs to the padded form");
-    if (row_base < 0 || row_base > 0x7fffffffffffffffLL - n) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: row_base + n leaves int64");
+    if (padded == csr) return entry_refuse(SAEV_INVALID_ARG, who, "give the codes as padded rows (idx, val) or as CSR (row_ptr, indices, data), one of the two");
+    if (padded && (!idx || !val)) return entry_refuse(SAEV_INVALID_ARG, who, "idx and val come together");
+    if (csr && (!row_ptr || !indices || !data)) return entry_refuse(SAEV_INVALID_ARG, who, "row_ptr, indices and data come together");
+    if (csr && row_nnz) return entry_refuse(SAEV_INVALID_ARG, who, "row_nnz belongs to the padded form");
+    if (row_base < 0 || row_base > 0x7fffffffffffffffLL - n) return entry_refuse(SAEV_INVALID_ARG, who, "row_base + n leaves int64");
     const int64_t total = padded ? n * cap : nnz;
-    if (total > 0x7fffffffLL) return refuse(SAEV_UNSUPPORTED, "saev_latent_topk_update: more than 2^31 - 1 entries in one batch");
+    if (total > 0x7fffffffLL) return entry_refuse(SAEV_UNSUPPORTED, who, "more than 2^31 - 1 entries in one batch");
     const int64_t need = saev_latent_topk_workspace_bytes(total, S);
-    if (!workspace || workspace_bytes < need) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: workspace smaller than saev_latent_topk_workspace_bytes(entries, S)");
-    if (((uintptr_t)workspace & 255) != 0) return refuse(SAEV_INVALID_ARG, "saev_latent_topk_update: workspace must be 256-byte aligned");
+    if (const int rc = entry_check_workspace(who, workspace, workspace_bytes, need, "workspace smaller than saev_latent_topk_workspace_bytes(entries, S)")) return rc;
     if (total == 0 || S == 0) return SAEV_OK;
 
     hipStream_t s = (hipStream_t)stream;
@@ -236,13 +204,13 @@ int saev_latent_topk_update(const int32_t* idx, const float* val, const int32_t*
     float* cand_val = reinterpret_cast<float*>(ws + 3 * round256(4 * S));
     int32_t* cand_row = reinterpret_cast<int32_t*>(ws + 3 * round256(4 * S) + round256(4 * total));
     LtCodes c{idx, val, row_nnz, (int)cap, row_ptr, indices, data, keep, (long)total, (int)n, (int)S, st.k};
-    if (hipMemsetAsync(cnt, 0, (size_t)S * 4, s) != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_latent_topk_update: hipMemsetAsync failed");
+    if (hipMemsetAsync(cnt, 0, (size_t)S * 4, s) != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "hipMemsetAsync failed");
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
     hipLaunchKernelGGL(lt_count_kernel, dim3(grid), dim3(256), 0, s, c, st.top_val, st.top_cnt, cnt);
     hipLaunchKernelGGL(lt_scan_kernel, dim3(1), dim3(LT_SCAN_THREADS), 0, s, cnt, (int)S, off, cur);
     hipLaunchKernelGGL(lt_place_kernel, dim3(grid), dim3(256), 0, s, c, st.top_val, st.top_cnt, cur, cand_val, cand_row);
     hipLaunchKernelGGL(lt_merge_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, cnt, off, cand_val, cand_row, (long)total, (int)S,
                        st.k, (long long)row_base, st.top_val, reinterpret_cast<long long*>(st.top_row), st.top_cnt);
-    if (hipGetLastError() != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_latent_topk_update: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");
     return SAEV_OK;
 }

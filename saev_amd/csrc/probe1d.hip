@@ -23,8 +23,7 @@
 //   evaluate the events pass with other accumulators (loss and three exact counts), then the closed form per pair.
 //
 // No floating-point atomic, no (nnz, C) temporary; nothing is read back except the optional poll of the done counter in fit.
-#include "common.h"
-#include "kernels.h"
+#include "entry_util.h"
 
 #include <algorithm>
 #include <cmath>
@@ -35,9 +34,6 @@ namespace {
 constexpr int P1_SUB = 64;                      // events per sub-chunk
 constexpr int P1_NSUBCHUNK = P1_CHUNK / P1_SUB;  // 8
 constexpr int P1_SCAN_THREADS = 1024;
-constexpr int P1_MAX_C = 4096;
-
-int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
 
 int p1_parts(int64_t S, int64_t nnz) {
     int64_t p = std::min<int64_t>(P1_PARTS, (nnz + 63) / 64);
@@ -46,10 +42,6 @@ int p1_parts(int64_t S, int64_t nnz) {
 }
 int64_t p1_part_len(int64_t nnz, int parts) { return std::max<int64_t>(64, ((nnz + parts - 1) / parts + 63) / 64 * 64); }
 
-bool p1_shape_ok(int64_t N, int64_t S, int64_t C, int64_t nnz) {
-    return N >= 1 && N <= 0x7fffffffLL && S >= 1 && S <= 0x7fffffffLL && C >= 1 && C <= P1_MAX_C && nnz >= 0 && nnz <= 0x7fffffffLL;
-}
-
 void p1_layout(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_probe1d_layout* L) {
     std::memset(L, 0, sizeof *L);
     L->struct_size = (int32_t)sizeof *L;
@@ -57,32 +49,31 @@ void p1_layout(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_probe1d_layout
     L->words = (C + 31) / 32;
     L->max_chunks = nnz / P1_CHUNK + S;
     L->parts = p1_parts(S, nnz);
-    int64_t at = 0;
-    const auto take = [&](int64_t bytes) { const int64_t o = at; at += round256(std::max<int64_t>(bytes, 1)); return o; };
+    WsCarve ws;
     const int64_t pairs = S * C;
-    L->off_err = take(64);
-    L->off_starts = take(8 * (S + 1));
-    L->off_chunk_starts = take(4 * (S + 1));
-    L->off_row = take(4 * nnz);
-    L->off_val = take(4 * nnz);
-    L->off_qx = take(8 * S);
-    L->off_ybits = take(4 * N * L->words);
-    L->off_pos = take(8 * C);
-    L->off_cnt = take(4 * (int64_t)L->parts * S);
-    L->off_tot = take(4 * S);
-    L->off_b = take(8 * pairs);
-    L->off_w = take(8 * pairs);
-    L->off_lam = take(8 * pairs);
-    L->off_prev_pred = take(8 * pairs);
-    L->off_prev_loss = take(8 * pairs);
-    L->off_clipped = take(4 * pairs);
-    L->off_sums = take(8 * 7 * pairs);
-    L->off_part = take(8 * 7 * C * L->max_chunks);
-    L->off_gmax = take(8 * C);
-    L->off_done = take(4 * C);
-    L->off_n_iter = take(4 * C);
-    L->off_active = take(64);
-    L->total_bytes = at;
+    L->off_err = ws.take(64);
+    L->off_starts = ws.take(8 * (S + 1));
+    L->off_chunk_starts = ws.take(4 * (S + 1));
+    L->off_row = ws.take(4 * nnz);
+    L->off_val = ws.take(4 * nnz);
+    L->off_qx = ws.take(8 * S);
+    L->off_ybits = ws.take(4 * N * L->words);
+    L->off_pos = ws.take(8 * C);
+    L->off_cnt = ws.take(4 * (int64_t)L->parts * S);
+    L->off_tot = ws.take(4 * S);
+    L->off_b = ws.take(8 * pairs);
+    L->off_w = ws.take(8 * pairs);
+    L->off_lam = ws.take(8 * pairs);
+    L->off_prev_pred = ws.take(8 * pairs);
+    L->off_prev_loss = ws.take(8 * pairs);
+    L->off_clipped = ws.take(4 * pairs);
+    L->off_sums = ws.take(8 * 7 * pairs);
+    L->off_part = ws.take(8 * 7 * C * L->max_chunks);
+    L->off_gmax = ws.take(8 * C);
+    L->off_done = ws.take(4 * C);
+    L->off_n_iter = ws.take(4 * C);
+    L->off_active = ws.take(64);
+    L->total_bytes = ws.at;
 }
 
 // ---------------------------------------------------------------- prepare ----------------------------------------------------------------
@@ -114,32 +105,15 @@ __global__ __launch_bounds__(256) void p1_parts_kernel(int32_t* __restrict__ cnt
 // halves of one 64-bit word (each stays below 2^31)
 __global__ __launch_bounds__(P1_SCAN_THREADS) void p1_scan_kernel(const int32_t* __restrict__ tot, int S, int64_t* __restrict__ starts,
                                                                   int32_t* __restrict__ chunk_starts) {
-    __shared__ unsigned long long sw[P1_SCAN_THREADS / 64];
-    __shared__ unsigned long long carry_s;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (long base = 0; base < S; base += P1_SCAN_THREADS) {
-        const long l = base + t;
-        const unsigned n = l < S ? (unsigned)tot[l] : 0u;
-        const unsigned long long mine = ((unsigned long long)((n + P1_CHUNK - 1) / P1_CHUNK) << 32) | n;
-        unsigned long long inc = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long up = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += up;
-        }
-        if (lane == 63) sw[w] = inc;
-        __syncthreads();
-        unsigned long long before = carry_s;
-        for (int q = 0; q < w; ++q) before += sw[q];
-        const unsigned long long start = before + inc - mine;
-        if (l < S) { starts[l] = (int64_t)(start & 0xffffffffull); chunk_starts[l] = (int32_t)(start >> 32); }
-        __syncthreads();
-        if (t == P1_SCAN_THREADS - 1) carry_s = before + inc;
-        __syncthreads();
-    }
-    if (t == 0) { starts[S] = (int64_t)(carry_s & 0xffffffffull); chunk_starts[S] = (int32_t)(carry_s >> 32); }
+    typedef unsigned long long u64;
+    const u64 end = block_scan_rounds<P1_SCAN_THREADS, u64, long>(
+        S,
+        [&](long l) {
+            const unsigned n = (unsigned)tot[l];
+            return ((u64)((n + P1_CHUNK - 1) / P1_CHUNK) << 32) | n;
+        },
+        [&](long l, u64 start) { starts[l] = (int64_t)(start & 0xffffffffull); chunk_starts[l] = (int32_t)(start >> 32); });
+    if (threadIdx.x == 0) { starts[S] = (int64_t)(end & 0xffffffffull); chunk_starts[S] = (int32_t)(end >> 32); }
 }
 
 // one wave per part (see the head of the file)
@@ -159,12 +133,7 @@ __global__ __launch_bounds__(64) void p1_place_kernel(const int64_t* __restrict_
             const int64_t p = row_ptr[0] + e;
             col = indices[p];
             if (col < 0 || col >= S) col = -1;  // (reported by the count pass)
-            int lo = 0, hi = N;  // the row r with row_ptr[r] <= p < row_ptr[r + 1]
-            while (hi - lo > 1) {
-                const int mid = lo + ((hi - lo) >> 1);
-                if (row_ptr[mid] <= p) lo = mid; else hi = mid;
-            }
-            row = lo;
+            row = csr_row_of(row_ptr, N, p);
             v = data[p];
         }
         int rank = 0, same = 0, leader = 64;
@@ -582,39 +551,25 @@ struct P1Ws {
 };
 
 int p1_open(const char* who, int64_t N, int64_t S, int64_t C, int64_t nnz, void* ws, int64_t ws_bytes, P1Ws* out) {
-    static thread_local char msg[160];
-    const auto refuse = [&](int code, const char* what) {
-        snprintf(msg, sizeof msg, "%s: %s", who, what);
-        return free_refuse(code, msg);
-    };
-    if (N < 0 || S < 0 || C < 0 || nnz < 0) return refuse(SAEV_INVALID_ARG, "negative size");
-    if (N > 0x7fffffffLL || S > 0x7fffffffLL || nnz > 0x7fffffffLL) return refuse(SAEV_UNSUPPORTED, "N, S and nnz must stay below 2^31");
-    if (N < 1 || S < 1) return refuse(SAEV_INVALID_ARG, "N and S must be at least 1");
-    if (C < 1 || C > P1_MAX_C) return refuse(SAEV_UNSUPPORTED, "the number of classes must lie in [1, 4096]");
+    if (const int rc = entry_check_shape(who, N, S, C, nnz)) return rc;
     p1_layout(N, S, C, nnz, &out->L);
-    if (!ws || ws_bytes < out->L.total_bytes) return refuse(SAEV_INVALID_ARG, "workspace smaller than saev_probe1d_workspace_bytes(N, S, C, nnz)");
-    if (((uintptr_t)ws & 255) != 0) return refuse(SAEV_INVALID_ARG, "workspace must be 256-byte aligned");
+    if (const int rc = entry_check_workspace(who, ws, ws_bytes, out->L.total_bytes, "workspace smaller than saev_probe1d_workspace_bytes(N, S, C, nnz)")) return rc;
     out->p = static_cast<uint8_t*>(ws);
     return SAEV_OK;
 }
 
 int p1_cfg(const char* who, const saev_probe1d_cfg* cfg, saev_probe1d_cfg* c) {
-    static thread_local char msg[160];
-    const auto refuse = [&](int code, const char* what) {
-        snprintf(msg, sizeof msg, "%s: %s", who, what);
-        return free_refuse(code, msg);
-    };
-    if (!cfg || cfg->struct_size < (int32_t)(2 * sizeof(int32_t))) return refuse(SAEV_INVALID_ARG, "no saev_probe1d_cfg (or its struct_size is unset)");
+    if (!cfg || cfg->struct_size < (int32_t)(2 * sizeof(int32_t))) return entry_refuse(SAEV_INVALID_ARG, who, "no saev_probe1d_cfg (or its struct_size is unset)");
     std::memset(c, 0, sizeof *c);
     std::memcpy(c, cfg, std::min<size_t>(sizeof *c, (size_t)cfg->struct_size));
-    if (c->max_iter < 0) return refuse(SAEV_INVALID_ARG, "max_iter must be >= 0");
-    if (c->class_slab_size < 1) return refuse(SAEV_INVALID_ARG, "class_slab_size must be >= 1");
-    if (c->poll_every < 0) return refuse(SAEV_INVALID_ARG, "poll_every must be >= 0");
-    if (c->out_dtype != SAEV_PROBE1D_F32 && c->out_dtype != SAEV_PROBE1D_F64) return refuse(SAEV_INVALID_ARG, "out_dtype must be SAEV_PROBE1D_F32 or SAEV_PROBE1D_F64");
-    if (!(c->lam_shrink > 0.0 && c->lam_shrink < 1.0)) return refuse(SAEV_INVALID_ARG, "lam_shrink must lie in (0, 1)");
-    if (!(c->lam_grow > 1.0)) return refuse(SAEV_INVALID_ARG, "lam_grow must be > 1");
-    if (!(c->delta_logit > 0.0)) return refuse(SAEV_INVALID_ARG, "delta_logit must be > 0");
-    if (!(c->ridge >= 0.0) || !(c->tol >= 0.0) || !(c->lam_init > 0.0)) return refuse(SAEV_INVALID_ARG, "ridge and tol must be >= 0 and lam_init > 0");
+    if (c->max_iter < 0) return entry_refuse(SAEV_INVALID_ARG, who, "max_iter must be >= 0");
+    if (c->class_slab_size < 1) return entry_refuse(SAEV_INVALID_ARG, who, "class_slab_size must be >= 1");
+    if (c->poll_every < 0) return entry_refuse(SAEV_INVALID_ARG, who, "poll_every must be >= 0");
+    if (c->out_dtype != SAEV_PROBE1D_F32 && c->out_dtype != SAEV_PROBE1D_F64) return entry_refuse(SAEV_INVALID_ARG, who, "out_dtype must be SAEV_PROBE1D_F32 or SAEV_PROBE1D_F64");
+    if (!(c->lam_shrink > 0.0 && c->lam_shrink < 1.0)) return entry_refuse(SAEV_INVALID_ARG, who, "lam_shrink must lie in (0, 1)");
+    if (!(c->lam_grow > 1.0)) return entry_refuse(SAEV_INVALID_ARG, who, "lam_grow must be > 1");
+    if (!(c->delta_logit > 0.0)) return entry_refuse(SAEV_INVALID_ARG, who, "delta_logit must be > 0");
+    if (!(c->ridge >= 0.0) || !(c->tol >= 0.0) || !(c->lam_init > 0.0)) return entry_refuse(SAEV_INVALID_ARG, who, "ridge and tol must be >= 0 and lam_init > 0");
     return SAEV_OK;
 }
 
@@ -658,15 +613,15 @@ void p1_launch_init(const P1Ws& W, int64_t N, int64_t S, int64_t C, const saev_p
 }  // namespace
 
 int64_t saev_probe1d_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t nnz) {
-    if (!p1_shape_ok(N, S, C, nnz)) return -1;
+    if (!entry_shape_ok(N, S, C, nnz)) return -1;
     saev_probe1d_layout L;
     p1_layout(N, S, C, nnz, &L);
     return L.total_bytes;
 }
 
 int saev_probe1d_layout_of(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_probe1d_layout* out) {
-    if (!out) return free_refuse(SAEV_INVALID_ARG, "saev_probe1d_layout_of: no saev_probe1d_layout");
-    if (!p1_shape_ok(N, S, C, nnz)) return free_refuse(SAEV_UNSUPPORTED, "saev_probe1d_layout_of: 1 <= N, S < 2^31, 1 <= C <= 4096, 0 <= nnz < 2^31");
+    if (!out) return entry_refuse(SAEV_INVALID_ARG, "saev_probe1d_layout_of", "no saev_probe1d_layout");
+    if (!entry_shape_ok(N, S, C, nnz)) return entry_refuse(SAEV_UNSUPPORTED, "saev_probe1d_layout_of", "1 <= N, S < 2^31, 1 <= C <= 4096, 0 <= nnz < 2^31");
     p1_layout(N, S, C, nnz, out);
     return SAEV_OK;
 }
@@ -674,14 +629,13 @@ int saev_probe1d_layout_of(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_pr
 int saev_probe1d_prepare(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
                          const uint8_t* class_u8, const int32_t* class_i32, const uint8_t* y_matrix, void* workspace, int64_t workspace_bytes,
                          void* stream) {
-    const auto refuse = [](int code, const char* msg) { return free_refuse(code, msg); };
     P1Ws W;
     if (const int rc = p1_open("saev_probe1d_prepare", N, S, C, nnz, workspace, workspace_bytes, &W)) return rc;
-    if (!row_ptr) return refuse(SAEV_INVALID_ARG, "saev_probe1d_prepare: row_ptr is NULL");
-    if (nnz > 0 && (!indices || !data)) return refuse(SAEV_INVALID_ARG, "saev_probe1d_prepare: indices and data come with nnz > 0");
+    if (!row_ptr) return entry_refuse(SAEV_INVALID_ARG, "saev_probe1d_prepare", "row_ptr is NULL");
+    if (nnz > 0 && (!indices || !data)) return entry_refuse(SAEV_INVALID_ARG, "saev_probe1d_prepare", "indices and data come with nnz > 0");
     const int forms = (class_u8 != nullptr) + (class_i32 != nullptr) + (y_matrix != nullptr);
-    if (forms != 1) return refuse(SAEV_INVALID_ARG, "saev_probe1d_prepare: give the labels as class ids (uint8 or int32) or as an N x C 0/1 matrix, one of the three");
-    if (class_u8 && C > 256) return refuse(SAEV_INVALID_ARG, "saev_probe1d_prepare: uint8 class ids cannot name more than 256 classes");
+    if (forms != 1) return entry_refuse(SAEV_INVALID_ARG, "saev_probe1d_prepare", "give the labels as class ids (uint8 or int32) or as an N x C 0/1 matrix, one of the three");
+    if (class_u8 && C > 256) return entry_refuse(SAEV_INVALID_ARG, "saev_probe1d_prepare", "uint8 class ids cannot name more than 256 classes");
 
     hipStream_t s = (hipStream_t)stream;
     const saev_probe1d_layout& L = W.L;
@@ -692,7 +646,7 @@ int saev_probe1d_prepare(const int64_t* row_ptr, const int32_t* indices, const f
     bool ok = hipMemsetAsync(err, 0, 64, s) == hipSuccess;
     ok = ok && hipMemsetAsync(cnt, 0, (size_t)(4 * L.parts * S), s) == hipSuccess;
     ok = ok && hipMemsetAsync(W.at<uint8_t>(L.off_pos), 0, (size_t)(8 * C), s) == hipSuccess;
-    if (!ok) return refuse(SAEV_HIP_ERROR, "saev_probe1d_prepare: hipMemsetAsync failed");
+    if (!ok) return entry_refuse(SAEV_HIP_ERROR, "saev_probe1d_prepare", "hipMemsetAsync failed");
     if (nnz > 0) {
         const int grid = (int)std::min<int64_t>((nnz + 255) / 256, 8192);
         hipLaunchKernelGGL(p1_count_kernel, dim3(grid), dim3(256), 0, s, row_ptr, indices, (long)nnz, (int)S, part_len, cnt, err);
@@ -713,7 +667,7 @@ int saev_probe1d_prepare(const int64_t* row_ptr, const int32_t* indices, const f
     else
         hipLaunchKernelGGL(p1_labels_ids_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, class_u8, class_i32, (int)N, (int)C, (int)L.words,
                            ybits, pos, err);
-    if (hipGetLastError() != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_probe1d_prepare: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_probe1d_prepare", "kernel launch failed");
     return SAEV_OK;
 }
 
@@ -721,9 +675,9 @@ int saev_probe1d_stats(int64_t N, int64_t S, int64_t C, int64_t nnz, const doubl
                        int64_t workspace_bytes, void* stream) {
     P1Ws W;
     if (const int rc = p1_open("saev_probe1d_stats", N, S, C, nnz, workspace, workspace_bytes, &W)) return rc;
-    if (!b || !w || !sums_out) return free_refuse(SAEV_INVALID_ARG, "saev_probe1d_stats: b, w and sums_out must not be NULL");
+    if (!b || !w || !sums_out) return entry_refuse(SAEV_INVALID_ARG, "saev_probe1d_stats", "b, w and sums_out must not be NULL");
     p1_launch_events<false>(W, S, C, b, w, nullptr, 1, 0.0, sums_out, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return free_refuse(SAEV_HIP_ERROR, "saev_probe1d_stats: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_probe1d_stats", "kernel launch failed");
     return SAEV_OK;
 }
 
@@ -734,7 +688,7 @@ int saev_probe1d_init(int64_t N, int64_t S, int64_t C, int64_t nnz, const saev_p
     if (const int rc = p1_open("saev_probe1d_init", N, S, C, nnz, workspace, workspace_bytes, &W)) return rc;
     if (const int rc = p1_cfg("saev_probe1d_init", cfg, &c)) return rc;
     p1_launch_init(W, N, S, C, c, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return free_refuse(SAEV_HIP_ERROR, "saev_probe1d_init: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_probe1d_init", "kernel launch failed");
     return SAEV_OK;
 }
 
@@ -745,7 +699,7 @@ int saev_probe1d_update(int64_t N, int64_t S, int64_t C, int64_t nnz, const saev
     if (const int rc = p1_open("saev_probe1d_update", N, S, C, nnz, workspace, workspace_bytes, &W)) return rc;
     if (const int rc = p1_cfg("saev_probe1d_update", cfg, &c)) return rc;
     p1_launch_update(W, N, S, C, c, sums ? sums : W.at<double>(W.L.off_sums), step_out, flags_out, (hipStream_t)stream);
-    if (hipGetLastError() != hipSuccess) return free_refuse(SAEV_HIP_ERROR, "saev_probe1d_update: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_probe1d_update", "kernel launch failed");
     return SAEV_OK;
 }
 
@@ -767,7 +721,7 @@ int saev_probe1d_fit(int64_t N, int64_t S, int64_t C, int64_t nnz, const saev_pr
             // results do not depend on whether or when the host looks
             int32_t live = 1;
             if (hipMemcpyAsync(&live, W.at<int32_t>(L.off_active), 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-                return free_refuse(SAEV_HIP_ERROR, "saev_probe1d_fit: reading the done counter failed");
+                return entry_refuse(SAEV_HIP_ERROR, "saev_probe1d_fit", "reading the done counter failed");
             if (live == 0) break;
         }
     }
@@ -778,7 +732,7 @@ int saev_probe1d_fit(int64_t N, int64_t S, int64_t C, int64_t nnz, const saev_pr
     else
         hipLaunchKernelGGL(p1_export_kernel<float>, dim3(grid), dim3(256), 0, s, W.at<double>(L.off_b), W.at<double>(L.off_w), (long)(S * C),
                            (float*)coef_out, (float*)intercept_out, W.at<int32_t>(L.off_n_iter), (int)C, c.class_slab_size, n_iter_out);
-    if (hipGetLastError() != hipSuccess) return free_refuse(SAEV_HIP_ERROR, "saev_probe1d_fit: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_probe1d_fit", "kernel launch failed");
     return SAEV_OK;
 }
 
@@ -786,9 +740,9 @@ int saev_probe1d_evaluate(int64_t N, int64_t S, int64_t C, int64_t nnz, const do
                           void* loss, void* tp, void* fp, void* tn, void* fn, void* workspace, int64_t workspace_bytes, void* stream) {
     P1Ws W;
     if (const int rc = p1_open("saev_probe1d_evaluate", N, S, C, nnz, workspace, workspace_bytes, &W)) return rc;
-    if (!b || !w) return free_refuse(SAEV_INVALID_ARG, "saev_probe1d_evaluate: b and w must not be NULL");
-    if (!(threshold > 0.0 && threshold < 1.0)) return free_refuse(SAEV_INVALID_ARG, "saev_probe1d_evaluate: threshold must lie in (0, 1)");
-    if (out_dtype != SAEV_PROBE1D_F32 && out_dtype != SAEV_PROBE1D_F64) return free_refuse(SAEV_INVALID_ARG, "saev_probe1d_evaluate: out_dtype must be SAEV_PROBE1D_F32 or SAEV_PROBE1D_F64");
+    if (!b || !w) return entry_refuse(SAEV_INVALID_ARG, "saev_probe1d_evaluate", "b and w must not be NULL");
+    if (!(threshold > 0.0 && threshold < 1.0)) return entry_refuse(SAEV_INVALID_ARG, "saev_probe1d_evaluate", "threshold must lie in (0, 1)");
+    if (out_dtype != SAEV_PROBE1D_F32 && out_dtype != SAEV_PROBE1D_F64) return entry_refuse(SAEV_INVALID_ARG, "saev_probe1d_evaluate", "out_dtype must be SAEV_PROBE1D_F32 or SAEV_PROBE1D_F64");
     hipStream_t s = (hipStream_t)stream;
     const saev_probe1d_layout& L = W.L;
     double* sums = W.at<double>(L.off_sums);
@@ -802,6 +756,6 @@ int saev_probe1d_evaluate(int64_t N, int64_t S, int64_t C, int64_t nnz, const do
         hipLaunchKernelGGL(p1_eval_finish_kernel<float>, dim3(grid), dim3(256), 0, s, sums, b, W.at<int64_t>(L.off_starts),
                            W.at<unsigned long long>(L.off_pos), (long)(S * C), (int)C, (double)N, threshold, (float*)loss, (float*)tp, (float*)fp,
                            (float*)tn, (float*)fn);
-    if (hipGetLastError() != hipSuccess) return free_refuse(SAEV_HIP_ERROR, "saev_probe1d_evaluate: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_probe1d_evaluate", "kernel launch failed");
     return SAEV_OK;
 }

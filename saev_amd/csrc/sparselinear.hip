@@ -19,12 +19,10 @@
 //              control  one workgroup: the sums in a fixed order and the decision -- done (KKT of y within tol), reject (L doubles,
 //                       the gradient is kept), restart (F rose under momentum: t = 1 from w) or accept (the three buffers rotate)
 //            No float atomics, every sum in an order fixed by the shape: two fits give the same bits.
-#include "common.h"
-#include "kernels.h"
+#include "entry_util.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 
 namespace {
@@ -32,8 +30,6 @@ namespace {
 constexpr int SL_MAX_K = 64;
 constexpr int SL_COLS = 256;      // columns of a grad / step workgroup
 constexpr int SL_MAX_CHUNKS = 32; // row chunks of the gradient
-
-int64_t sl_round256(int64_t b) { return (b + 255) / 256 * 256; }
 
 // ---------------------------------------------------------------- pooling -----------------------------------------------------------
 
@@ -396,18 +392,17 @@ void sl_layout(int64_t n, int64_t S, int64_t K, saev_l1_logistic_layout* L) {
     L->n_chunks = (n + L->chunk_rows - 1) / L->chunk_rows;
     L->col_blocks = (S + 1 + SL_COLS - 1) / SL_COLS;
     const int64_t Kc = L->coef_rows, S1 = S + 1;
-    int64_t at = 0;
-    const auto take = [&](int64_t bytes) { const int64_t o = at; at += sl_round256(std::max<int64_t>(bytes, 1)); return o; };
-    L->off_err = take(64);
-    L->off_state = take(8 * SAEV_L1_STATE_WORDS);
-    L->off_w = take(3 * sl_round256(8 * Kc * S1));
-    L->off_z = take(3 * sl_round256(8 * Kc * n));
-    L->off_g = take(8 * Kc * S1);
-    L->off_part = take(8 * L->n_chunks * Kc * S1);
-    L->off_r = take(8 * Kc * n);
-    L->off_loss = take(2 * sl_round256(8 * n));
-    L->off_bp = take(8 * 8 * L->col_blocks);
-    L->total_bytes = at;
+    WsCarve ws;
+    L->off_err = ws.take(64);
+    L->off_state = ws.take(8 * SAEV_L1_STATE_WORDS);
+    L->off_w = ws.take(3 * round256(8 * Kc * S1));
+    L->off_z = ws.take(3 * round256(8 * Kc * n));
+    L->off_g = ws.take(8 * Kc * S1);
+    L->off_part = ws.take(8 * L->n_chunks * Kc * S1);
+    L->off_r = ws.take(8 * Kc * n);
+    L->off_loss = ws.take(2 * round256(8 * n));
+    L->off_bp = ws.take(8 * 8 * L->col_blocks);
+    L->total_bytes = ws.at;
 }
 
 const char* sl_args(SlArgs* a, const float* X, const int32_t* y, int64_t n, int64_t S, int64_t K, double C, double tol, void* workspace,
@@ -429,14 +424,14 @@ const char* sl_args(SlArgs* a, const float* X, const int32_t* y, int64_t n, int6
     a->state = reinterpret_cast<double*>(ws + L->off_state);
     a->err = reinterpret_cast<int32_t*>(ws + L->off_err);
     for (int i = 0; i < 3; ++i) {
-        a->W[i] = reinterpret_cast<double*>(ws + L->off_w + i * sl_round256(8 * Kc * S1));
-        a->Z[i] = reinterpret_cast<double*>(ws + L->off_z + i * sl_round256(8 * Kc * n));
+        a->W[i] = reinterpret_cast<double*>(ws + L->off_w + i * round256(8 * Kc * S1));
+        a->Z[i] = reinterpret_cast<double*>(ws + L->off_z + i * round256(8 * Kc * n));
     }
     a->G = reinterpret_cast<double*>(ws + L->off_g);
     a->part = reinterpret_cast<double*>(ws + L->off_part);
     a->r = reinterpret_cast<double*>(ws + L->off_r);
     a->loss_y = reinterpret_cast<double*>(ws + L->off_loss);
-    a->loss_n = reinterpret_cast<double*>(ws + L->off_loss + sl_round256(8 * n));
+    a->loss_n = reinterpret_cast<double*>(ws + L->off_loss + round256(8 * n));
     a->bp = reinterpret_cast<double*>(ws + L->off_bp);
     return "";
 }
@@ -464,25 +459,24 @@ int64_t saev_pool_images_range(void) { return SL_POOL_RANGE; }
 
 int saev_pool_images(const int64_t* indptr, const int32_t* indices, const float* data, int64_t nnz, int64_t n_images,
                      int64_t tokens_per_image, int64_t n_latents, int32_t agg, float* out, int32_t* err, void* stream) {
-    const auto refuse = [](int code, const char* msg) { return free_refuse(code, msg); };
-    if (n_images < 0 || tokens_per_image < 0 || n_latents < 0) return refuse(SAEV_INVALID_ARG, "saev_pool_images: negative size");
+    if (n_images < 0 || tokens_per_image < 0 || n_latents < 0) return entry_refuse(SAEV_INVALID_ARG, "saev_pool_images", "negative size");
     if (n_images < 1 || tokens_per_image < 1 || n_latents < 1)
-        return refuse(SAEV_INVALID_ARG, "saev_pool_images: n_images, tokens_per_image and n_latents must be at least 1");
+        return entry_refuse(SAEV_INVALID_ARG, "saev_pool_images", "n_images, tokens_per_image and n_latents must be at least 1");
     if (n_images > 0x7fffffffLL || tokens_per_image > 0x7fffffffLL || n_latents > 0x7fffffffLL || n_images * tokens_per_image > 0x7fffffffLL)
-        return refuse(SAEV_UNSUPPORTED, "saev_pool_images: n_images * tokens_per_image and n_latents must stay below 2^31");
-    if ((n_latents + SL_POOL_RANGE - 1) / SL_POOL_RANGE > 65535) return refuse(SAEV_UNSUPPORTED, "saev_pool_images: more than 65535 latent ranges");
-    if (agg != SAEV_POOL_MAX && agg != SAEV_POOL_MEAN) return refuse(SAEV_INVALID_ARG, "saev_pool_images: agg is SAEV_POOL_MAX or SAEV_POOL_MEAN");
-    if (nnz < 0) return refuse(SAEV_INVALID_ARG, "saev_pool_images: negative nnz");
-    if (!indptr || !out || !err) return refuse(SAEV_INVALID_ARG, "saev_pool_images: indptr, out and err must not be NULL");
-    if (nnz > 0 && (!indices || !data)) return refuse(SAEV_INVALID_ARG, "saev_pool_images: indices and data come with nnz > 0");
+        return entry_refuse(SAEV_UNSUPPORTED, "saev_pool_images", "n_images * tokens_per_image and n_latents must stay below 2^31");
+    if ((n_latents + SL_POOL_RANGE - 1) / SL_POOL_RANGE > 65535) return entry_refuse(SAEV_UNSUPPORTED, "saev_pool_images", "more than 65535 latent ranges");
+    if (agg != SAEV_POOL_MAX && agg != SAEV_POOL_MEAN) return entry_refuse(SAEV_INVALID_ARG, "saev_pool_images", "agg is SAEV_POOL_MAX or SAEV_POOL_MEAN");
+    if (nnz < 0) return entry_refuse(SAEV_INVALID_ARG, "saev_pool_images", "negative nnz");
+    if (!indptr || !out || !err) return entry_refuse(SAEV_INVALID_ARG, "saev_pool_images", "indptr, out and err must not be NULL");
+    if (nnz > 0 && (!indices || !data)) return entry_refuse(SAEV_INVALID_ARG, "saev_pool_images", "indices and data come with nnz > 0");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(err, 0, 4, s) != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_pool_images: hipMemsetAsync failed");
+    if (hipMemsetAsync(err, 0, 4, s) != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_pool_images", "hipMemsetAsync failed");
     const dim3 grid((unsigned)n_images, (unsigned)((n_latents + SL_POOL_RANGE - 1) / SL_POOL_RANGE));
     if (agg == SAEV_POOL_MEAN)
         hipLaunchKernelGGL(sl_pool_kernel<1>, grid, dim3(256), 0, s, indptr, indices, data, nnz, (int)tokens_per_image, (int)n_latents, out, err);
     else
         hipLaunchKernelGGL(sl_pool_kernel<0>, grid, dim3(256), 0, s, indptr, indices, data, nnz, (int)tokens_per_image, (int)n_latents, out, err);
-    if (hipGetLastError() != hipSuccess) return refuse(SAEV_HIP_ERROR, "saev_pool_images: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_pool_images", "kernel launch failed");
     return SAEV_OK;
 }
 
@@ -494,8 +488,8 @@ int64_t saev_l1_logistic_workspace_bytes(int64_t n, int64_t S, int64_t K) {
 }
 
 int saev_l1_logistic_layout_of(int64_t n, int64_t S, int64_t K, saev_l1_logistic_layout* out) {
-    if (!out) return free_refuse(SAEV_INVALID_ARG, "saev_l1_logistic_layout_of: no saev_l1_logistic_layout");
-    if (!sl_shape_ok(n, S, K)) return free_refuse(SAEV_UNSUPPORTED, "saev_l1_logistic_layout_of: 1 <= n < 2^31, 1 <= S <= 2^30, 2 <= K <= 64");
+    if (!out) return entry_refuse(SAEV_INVALID_ARG, "saev_l1_logistic_layout_of", "no saev_l1_logistic_layout");
+    if (!sl_shape_ok(n, S, K)) return entry_refuse(SAEV_UNSUPPORTED, "saev_l1_logistic_layout_of", "1 <= n < 2^31, 1 <= S <= 2^30, 2 <= K <= 64");
     sl_layout(n, S, K, out);
     return SAEV_OK;
 }
@@ -505,9 +499,8 @@ int saev_l1_logistic_layout_of(int64_t n, int64_t S, int64_t K, saev_l1_logistic
     saev_l1_logistic_layout L;                                                                                                    \
     {                                                                                                                             \
         const char* why = sl_args(&a, X, y, n, S, K, C, kkt_tol, workspace, workspace_bytes, &L);                                 \
-        static thread_local char msg[160];                                                                                        \
-        if (!why) return free_refuse(SAEV_UNSUPPORTED, name ": 1 <= n < 2^31, 1 <= S <= 2^30, 2 <= K <= 64");                   \
-        if (why[0]) { std::snprintf(msg, sizeof msg, name ": %s", why); return free_refuse(SAEV_INVALID_ARG, msg); }              \
+        if (!why) return entry_refuse(SAEV_UNSUPPORTED, name, "1 <= n < 2^31, 1 <= S <= 2^30, 2 <= K <= 64");                     \
+        if (why[0]) return entry_refuse(SAEV_INVALID_ARG, name, why);                                                             \
     }                                                                                                                             \
     hipStream_t s = (hipStream_t)stream;
 
@@ -515,33 +508,33 @@ int saev_l1_logistic_init(const float* X, const int32_t* y, int64_t n, int64_t S
                           int64_t workspace_bytes, void* stream) {
     SL_ENTRY("saev_l1_logistic_init")
     // everything starts at 0: w = 0, so the logits are 0 and F = C n log(classes)
-    if (hipMemsetAsync(workspace, 0, (size_t)L.off_g, s) != hipSuccess) return free_refuse(SAEV_HIP_ERROR, "saev_l1_logistic_init: hipMemsetAsync failed");
+    if (hipMemsetAsync(workspace, 0, (size_t)L.off_g, s) != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_l1_logistic_init", "hipMemsetAsync failed");
     hipLaunchKernelGGL(sl_init_kernel, dim3(1), dim3(64), 0, s, a.state, C * (double)n * std::log((double)K));
     const size_t total = (size_t)n * (size_t)S;
     const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 8192);
     hipLaunchKernelGGL(sl_check_kernel, dim3(grid), dim3(256), 0, s, X, total, y, n, (int)K, a.err);
-    if (hipGetLastError() != hipSuccess) return free_refuse(SAEV_HIP_ERROR, "saev_l1_logistic_init: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_l1_logistic_init", "kernel launch failed");
     return SAEV_OK;
 }
 
 int saev_l1_logistic_iterate(const float* X, const int32_t* y, int64_t n, int64_t S, int64_t K, double C, double kkt_tol, int32_t n_iters,
                              void* workspace, int64_t workspace_bytes, void* stream) {
     SL_ENTRY("saev_l1_logistic_iterate")
-    if (n_iters < 0) return free_refuse(SAEV_INVALID_ARG, "saev_l1_logistic_iterate: negative n_iters");
+    if (n_iters < 0) return entry_refuse(SAEV_INVALID_ARG, "saev_l1_logistic_iterate", "negative n_iters");
     for (int it = 0; it < n_iters; ++it) sl_iteration(a, s, true, 0);
-    if (hipGetLastError() != hipSuccess) return free_refuse(SAEV_HIP_ERROR, "saev_l1_logistic_iterate: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_l1_logistic_iterate", "kernel launch failed");
     return SAEV_OK;
 }
 
 int saev_l1_logistic_result(const float* X, const int32_t* y, int64_t n, int64_t S, int64_t K, double C, double kkt_tol, double* coef,
                             double* intercept, double* scalars, void* workspace, int64_t workspace_bytes, void* stream) {
     SL_ENTRY("saev_l1_logistic_result")
-    if (!coef || !intercept || !scalars) return free_refuse(SAEV_INVALID_ARG, "saev_l1_logistic_result: coef, intercept and scalars must not be NULL");
+    if (!coef || !intercept || !scalars) return entry_refuse(SAEV_INVALID_ARG, "saev_l1_logistic_result", "coef, intercept and scalars must not be NULL");
     // a fit that is not done gives up its momentum: the residual and the objective are then those of the iterate itself
     hipLaunchKernelGGL(sl_unmomentum_kernel, dim3(1), dim3(1), 0, s, a.state);
     sl_iteration(a, s, false, 1);
     const size_t total = (size_t)a.Kc * (size_t)S;
     hipLaunchKernelGGL(sl_out_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, a, coef, intercept, scalars);
-    if (hipGetLastError() != hipSuccess) return free_refuse(SAEV_HIP_ERROR, "saev_l1_logistic_result: kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, "saev_l1_logistic_result", "kernel launch failed");
     return SAEV_OK;
 }

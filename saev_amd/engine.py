@@ -449,6 +449,67 @@ def row_norm_mean(W: torch.Tensor) -> float:
     return out.item()
 
 
+def _on(t, dtype, shape, what, device):
+    """``t`` made contiguous; ValueError unless it has this dtype and shape and lies on ``device``.  None passes through."""
+    if t is None:
+        return None
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device:
+        raise ValueError(f"{what} must be {dtype} of shape {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t.contiguous()
+
+
+def _hip_device(who: str, device) -> torch.device:
+    """``device`` with its index filled in; RuntimeError unless it is a HIP device."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{who} runs on a HIP device only (there is no CPU path)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _csr_on(indptr, indices, data, n_rows: int, stored: int, device):
+    """The CSR triple of the analysis entries: indptr (n_rows + 1) int64, indices and data (stored) int32 / float32."""
+    return (_on(indptr, torch.int64, (n_rows + 1,), "indptr", device), _on(indices, torch.int32, (stored,), "indices", device),
+            _on(data, torch.float32, (stored,), "data", device))
+
+
+def _class_labels(who: str, labels, remap, n_rows: int, device):
+    """``labels`` / ``remap`` of ``latent_ap`` as the C entry takes them: (class_u8, remap, class_i32), one label form set."""
+    if labels.dtype == torch.uint8:
+        return _on(labels, torch.uint8, (n_rows,), "labels", device), _on(remap, torch.int32, (256,), "remap", device), None
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"labels must be uint8, int32 or int64, got {labels.dtype}")
+    if remap is not None:
+        raise ValueError(f"{who}: remap goes with uint8 labels")
+    return None, None, _on(labels.to(torch.int32), torch.int32, (n_rows,), "labels", device)
+
+
+def _check_err_word(err, errors: dict, who: str) -> None:
+    """Reads the device's error word (one synchronisation); ValueError with the table's text if it is not 0."""
+    code = int(err.item())
+    if code != 0:
+        raise ValueError(f"{who}: {errors.get(code, code)} (found on the device)")
+
+
+class _Checked:
+    """Results of a call that reports bad input through an error word on the device: the first read of a result -- or ``check()``
+    -- reads the word once and raises ValueError if it is not 0; every later read of a bad call raises again."""
+
+    def __init__(self, out: dict, err, errors: dict, who: str):
+        self._out, self._err, self._errors, self._who = out, err, errors, who
+        self._checked = False
+
+    def check(self) -> None:
+        if not self._checked:
+            _check_err_word(self._err, self._errors, self._who)
+            self._checked = True
+
+    def _read(self, name):
+        self.check()
+        return self._out[name]
+
+
 @dataclasses.dataclass(frozen=True)
 class BatchStatsHost:
     """What ``BatchStats.read()`` brings back (CPU tensors; an output the accumulator was created without is None)."""
@@ -540,23 +601,17 @@ class BatchStats:
         """One batch: x, x_hat (n, D) float32; padded code rows idx (n, cap) int32 / val (n, cap) float32 with row_nnz (n) int32
         (None: full rows); keep (n) bool.  ``overwrite`` stores instead of adding (``live`` is never cleared);
         ``scalars=False`` leaves the scalar sums out of this batch."""
-        def chk(t, dtype, shape, what):
-            if t is None:
-                return None
-            if t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device:
-                raise ValueError(f"{what} must be {dtype} of shape {shape} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-            return t.contiguous()
         if x.ndim != 2:
             raise ValueError(f"x must be (n, {self.d_model}), got {tuple(x.shape)}")
         n = x.shape[0]
-        x = chk(x, torch.float32, (n, self.d_model), "x")
-        x_hat = chk(x_hat, torch.float32, (n, self.d_model), "x_hat")
+        x = _on(x, torch.float32, (n, self.d_model), "x", self.device)
+        x_hat = _on(x_hat, torch.float32, (n, self.d_model), "x_hat", self.device)
         if (idx is None) != (val is None):
             raise ValueError("idx and val come together")
         cap = 0 if idx is None else idx.shape[-1]
-        idx = chk(idx, torch.int32, (n, cap), "idx")
-        val = chk(val, torch.float32, (n, cap), "val")
-        row_nnz = chk(row_nnz, torch.int32, (n,), "row_nnz")
+        idx = _on(idx, torch.int32, (n, cap), "idx", self.device)
+        val = _on(val, torch.float32, (n, cap), "val", self.device)
+        row_nnz = _on(row_nnz, torch.int32, (n,), "row_nnz", self.device)
         self._add_ptrs(_ptr(x), _ptr(x_hat), _ptr(idx), _ptr(val), _ptr(row_nnz), keep, n, cap, overwrite, scalars)
 
     def read(self) -> BatchStatsHost:
@@ -590,11 +645,7 @@ class LatentTopK:
             raise ValueError(f"LatentTopK: unsupported k {k} (1 <= k <= {self.MAX_K})")
         if d_sae < 1 or d_sae >= 2**31:
             raise ValueError(f"LatentTopK: unsupported d_sae {d_sae}")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("LatentTopK runs on a HIP device only (there is no CPU path)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _hip_device("LatentTopK", device)
         self.lib = _lib.load()
         self.d_sae, self.k = d_sae, k
         self.top_val = torch.zeros(d_sae, k, device=self.device, dtype=torch.float32)
@@ -616,13 +667,6 @@ class LatentTopK:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
         return self._ws
-
-    def _chk(self, t, dtype, shape, what):
-        if t is None:
-            return None
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device:
-            raise ValueError(f"{what} must be {dtype} of shape {shape} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        return t.contiguous()
 
     def _keep(self, keep, n: int):
         if keep is None:
@@ -649,9 +693,9 @@ class LatentTopK:
         if idx.ndim != 2:
             raise ValueError(f"idx must be (n, cap), got {tuple(idx.shape)}")
         n, cap = idx.shape
-        idx = self._chk(idx, torch.int32, (n, cap), "idx")
-        val = self._chk(val, torch.float32, (n, cap), "val")
-        row_nnz = self._chk(row_nnz, torch.int32, (n,), "row_nnz")
+        idx = _on(idx, torch.int32, (n, cap), "idx", self.device)
+        val = _on(val, torch.float32, (n, cap), "val", self.device)
+        row_nnz = _on(row_nnz, torch.int32, (n,), "row_nnz", self.device)
         if n == 0 or cap == 0:
             return
         self._update(_ptr(idx), _ptr(val), _ptr(row_nnz), cap, None, None, None, 0, keep, n, row_base)
@@ -662,9 +706,7 @@ class LatentTopK:
         if indptr.ndim != 1 or indptr.numel() < 1:
             raise ValueError(f"indptr must be a vector of n + 1 offsets, got {tuple(indptr.shape)}")
         n, nnz = indptr.numel() - 1, indices.numel()
-        indptr = self._chk(indptr, torch.int64, (n + 1,), "indptr")
-        indices = self._chk(indices, torch.int32, (nnz,), "indices")
-        data = self._chk(data, torch.float32, (nnz,), "data")
+        indptr, indices, data = _csr_on(indptr, indices, data, n, nnz, self.device)
         if n == 0 or nnz == 0:
             return
         self._update(None, None, None, 0, _ptr(indptr), _ptr(indices), _ptr(data), nnz, keep, n, row_base)
@@ -706,11 +748,7 @@ class Probe1D:
                 raise ValueError(f"Probe1D: unsupported {name} {v} (1 <= {name} < {hi})")
         if not 0 <= nnz < 2**31:
             raise ValueError(f"Probe1D: unsupported nnz {nnz} (0 <= nnz < 2^31)")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("Probe1D runs on a HIP device only (there is no CPU path)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _hip_device("Probe1D", device)
         self.lib = _lib.load()
         self.shape = (n_rows, n_latents, n_classes, nnz)
         self.layout = _lib.SaevProbe1DLayout()
@@ -743,11 +781,6 @@ class Probe1D:
             rc = getattr(self.lib, name)(*args, _ptr(self._ws), self._ws.numel(), _stream())
         _lib.check(self.lib, None, rc, name)
 
-    def _on(self, t, dtype, shape, what):
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != self.device:
-            raise ValueError(f"{what} must be {dtype} of shape {tuple(shape)} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        return t.contiguous()
-
     def prepare(self, indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, *, labels: torch.Tensor | None = None,
                 y: torch.Tensor | None = None) -> "Probe1D":
         """x as CSR on the device (indptr (N + 1) int64 from 0, indices (nnz) int32, data (nnz) float32) and the labels in ONE form:
@@ -755,25 +788,21 @@ class Probe1D:
         n, s, c, nnz = self.shape
         if (labels is None) == (y is None):
             raise ValueError("Probe1D.prepare: give the labels as class ids (labels=) or as an N x C matrix (y=), one of the two")
-        indptr = self._on(indptr, torch.int64, (n + 1,), "indptr")
-        indices = self._on(indices, torch.int32, (nnz,), "indices")
-        data = self._on(data, torch.float32, (nnz,), "data")
+        indptr, indices, data = _csr_on(indptr, indices, data, n, nnz, self.device)
         u8 = i32 = mat = None
         if labels is not None:
             if labels.dtype == torch.uint8 and c <= 256:
-                u8 = self._on(labels, torch.uint8, (n,), "labels")
+                u8 = _on(labels, torch.uint8, (n,), "labels", self.device)
             elif labels.dtype in (torch.uint8, torch.int32, torch.int64):
-                i32 = self._on(labels.to(torch.int32), torch.int32, (n,), "labels")
+                i32 = _on(labels.to(torch.int32), torch.int32, (n,), "labels", self.device)
             else:
                 raise ValueError(f"labels must be uint8, int32 or int64 class ids, got {labels.dtype}")
         else:
             if y.dtype == torch.bool:
                 y = y.view(torch.uint8)
-            mat = self._on(y, torch.uint8, (n, c), "y")
+            mat = _on(y, torch.uint8, (n, c), "y", self.device)
         self._call("saev_probe1d_prepare", _ptr(indptr), _ptr(indices), _ptr(data), nnz, n, s, c, _ptr(u8), _ptr(i32), _ptr(mat))
-        code = int(self.err.item())
-        if code != 0:
-            raise ValueError(f"Probe1D.prepare: {self._ERRORS.get(code, code)} (found on the device)")
+        _check_err_word(self.err, self._ERRORS, "Probe1D.prepare")
         self.prepared = True
         return self
 
@@ -792,7 +821,7 @@ class Probe1D:
         """The event sums (S, 7, C) float64 of every pair at (b, w), each (S, C) float64: mu, (mu - y) v, s, s v, s v^2, loss, y."""
         self._need()
         n, s, c, nnz = self.shape
-        b, w = self._on(b, torch.float64, (s, c), "b"), self._on(w, torch.float64, (s, c), "w")
+        b, w = _on(b, torch.float64, (s, c), "b", self.device), _on(w, torch.float64, (s, c), "w", self.device)
         out = torch.empty(s, 7, c, device=self.device, dtype=torch.float64)
         self._call("saev_probe1d_stats", n, s, c, nnz, _ptr(b), _ptr(w), _ptr(out))
         return out
@@ -806,8 +835,7 @@ class Probe1D:
         (step (S, C, 4) float64: db, dw, pred, lam; flags (S, C) int32: SAEV_PROBE1D_STEP_* | tries << 8)."""
         self._need()
         n, s, c, nnz = self.shape
-        if sums is not None:
-            sums = self._on(sums, torch.float64, (s, 7, c), "sums")
+        sums = _on(sums, torch.float64, (s, 7, c), "sums", self.device)
         step = torch.zeros(s, c, 4, device=self.device, dtype=torch.float64) if debug else None
         flags = torch.zeros(s, c, device=self.device, dtype=torch.int32) if debug else None
         self._call("saev_probe1d_update", n, s, c, nnz, C.byref(self._cfg(hp)), _ptr(sums), _ptr(step), _ptr(flags))
@@ -832,37 +860,18 @@ class Probe1D:
         if dtype not in self._DTYPES:
             raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype}")
         n, s, c, nnz = self.shape
-        b, w = self._on(b, torch.float64, (s, c), "b"), self._on(w, torch.float64, (s, c), "w")
+        b, w = _on(b, torch.float64, (s, c), "b", self.device), _on(w, torch.float64, (s, c), "w", self.device)
         outs = [torch.empty(s, c, device=self.device, dtype=dtype) for _ in range(5)]
         self._call("saev_probe1d_evaluate", n, s, c, nnz, _ptr(b), _ptr(w), float(threshold), self._DTYPES[dtype], *map(_ptr, outs))
         return tuple(outs)
 
 
-class LatentAPResult:
-    """What ``latent_ap`` leaves on the device: ``ap`` (S, C) float64, ``n_pos`` (C) int64, ``best_ap`` (S) float64 and ``best_class``
-    (S) int32, the lowest column that attains the row maximum.  The call itself does not synchronise; the first read of any of the
-    four reads the device's error word (one synchronisation) and raises ValueError if it is not 0.  ``sorted_events()`` gives the
-    workspace's sorted entries (include/saev_amd.h: LATENT AP)."""
+class _APResult(_Checked):
+    """What ``latent_ap`` and ``probe_ap`` both leave: the results, and the workspace with its error word and its sorted events."""
 
-    _ERRORS = {1: "a class id lies outside [-1, n_classes)", 2: "a column index lies outside [0, n_latents)"}
-
-    def __init__(self, ap, n_pos, best_ap, best_class, ws, layout, shape):
-        self._out = dict(ap=ap, n_pos=n_pos, best_ap=best_ap, best_class=best_class)
+    def __init__(self, out: dict, ws, layout, shape):
+        super().__init__(out, ws[layout.off_err:layout.off_err + 4].view(torch.int32), self._ERRORS, self._WHO)
         self._ws, self.layout, self.shape = ws, layout, shape
-        self._checked = False
-
-    def _read(self, name):
-        if not self._checked:
-            code = int(self._ws[self.layout.off_err:self.layout.off_err + 4].view(torch.int32).item())
-            if code != 0:
-                raise ValueError(f"latent_ap: {self._ERRORS.get(code, code)} (found on the device)")
-            self._checked = True
-        return self._out[name]
-
-    ap = property(lambda self: self._read("ap"))
-    n_pos = property(lambda self: self._read("n_pos"))
-    best_ap = property(lambda self: self._read("best_ap"))
-    best_class = property(lambda self: self._read("best_class"))
 
     def sorted_events(self):
         """(starts (S + 1) int64, key (E) int32 bit patterns of the uint32 keys, latent (E) int32, row (E) int32) of the E events in
@@ -875,6 +884,43 @@ class LatentAPResult:
         return starts, view(lay.off_key, torch.int32, nnz)[:e], view(lay.off_latent, torch.int32, nnz)[:e], view(lay.off_row, torch.int32, nnz)[:e]
 
 
+class LatentAPResult(_APResult):
+    """What ``latent_ap`` leaves on the device: ``ap`` (S, C) float64, ``n_pos`` (C) int64, ``best_ap`` (S) float64 and ``best_class``
+    (S) int32, the lowest column that attains the row maximum.  The call itself does not synchronise; the first read of any of the
+    four reads the device's error word (one synchronisation) and raises ValueError if it is not 0.  ``sorted_events()`` gives the
+    workspace's sorted entries (include/saev_amd.h: LATENT AP)."""
+
+    _WHO = "latent_ap"
+    _ERRORS = {1: "a class id lies outside [-1, n_classes)", 2: "a column index lies outside [0, n_latents)"}
+
+    ap = property(lambda self: self._read("ap"))
+    n_pos = property(lambda self: self._read("n_pos"))
+    best_ap = property(lambda self: self._read("best_ap"))
+    best_class = property(lambda self: self._read("best_class"))
+
+
+def _ap_open(who: str, indptr, indices, data, n_rows: int, n_latents: int, n_classes: int, labels, remap, nnz, top_k: int = 0):
+    """What ``latent_ap`` and ``probe_ap`` do before their C entry: the size checks, the nnz rule, the CSR triple and the labels on the
+    device, the layout and a workspace of its size.  Returns (lib, device, nnz, the ten leading arguments of either entry, ws, layout)."""
+    for name, v, hi in (("n_rows", n_rows, 2**31), ("n_latents", n_latents, 2**31), ("n_classes", n_classes, 4097)):
+        if not 1 <= v < hi:
+            raise ValueError(f"{who}: unsupported {name} {v} (1 <= {name} < {hi})")
+    if not 0 <= top_k <= n_rows:
+        raise ValueError(f"{who}: top_k {top_k} must lie in [0, n_rows = {n_rows}]")
+    device = _hip_device(who, indptr.device)
+    stored = indices.numel()
+    nnz = stored if nnz is None else int(nnz)
+    if not 0 <= nnz < 2**31 or nnz > stored:
+        raise ValueError(f"{who}: unsupported nnz {nnz} (0 <= nnz < 2^31, and at most the {stored} entries of indices)")
+    csr = _csr_on(indptr, indices, data, n_rows, stored, device)
+    classes = _class_labels(who, labels, remap, n_rows, device)
+    lib = _lib.load()
+    layout = _lib.SaevLatentAPLayout()
+    _lib.check(lib, None, lib.saev_latent_ap_layout_of(n_rows, n_latents, n_classes, nnz, C.byref(layout)), "saev_latent_ap_layout_of")
+    ws = torch.empty(layout.total_bytes, device=device, dtype=torch.uint8)
+    return lib, device, nnz, csr, classes, ws, layout
+
+
 def latent_ap(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_rows: int, n_latents: int, n_classes: int, *,
               labels: torch.Tensor, remap: torch.Tensor | None = None, nnz: int | None = None) -> LatentAPResult:
     """Exact tie-aware average precision of every latent against every class (include/saev_amd.h: LATENT AP).
@@ -884,83 +930,33 @@ def latent_ap(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n
     ``nnz = indptr[-1] - indptr[0]``, which is otherwise taken to be ``indices.numel()`` -- the call reads no device value back to
     find it out, and ``indices`` and ``data`` must hold ``indptr[-1]`` entries.  One call, one workspace, no synchronisation; there
     is no CPU path."""
-    for name, v, hi in (("n_rows", n_rows, 2**31), ("n_latents", n_latents, 2**31), ("n_classes", n_classes, 4097)):
-        if not 1 <= v < hi:
-            raise ValueError(f"latent_ap: unsupported {name} {v} (1 <= {name} < {hi})")
-    device = indptr.device
-    if device.type != "cuda":
-        raise RuntimeError("latent_ap runs on a HIP device only (there is no CPU path)")
-    stored = indices.numel()
-    nnz = stored if nnz is None else int(nnz)
-    if not 0 <= nnz < 2**31 or nnz > stored:
-        raise ValueError(f"latent_ap: unsupported nnz {nnz} (0 <= nnz < 2^31, and at most the {stored} entries of indices)")
-
-    def on(t, dtype, shape, what):
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device:
-            raise ValueError(f"{what} must be {dtype} of shape {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        return t.contiguous()
-
-    indptr = on(indptr, torch.int64, (n_rows + 1,), "indptr")
-    indices = on(indices, torch.int32, (stored,), "indices")
-    data = on(data, torch.float32, (stored,), "data")
-    u8 = i32 = None
-    if labels.dtype == torch.uint8:
-        u8 = on(labels, torch.uint8, (n_rows,), "labels")
-        if remap is not None:
-            remap = on(remap, torch.int32, (256,), "remap")
-    elif labels.dtype in (torch.int32, torch.int64):
-        if remap is not None:
-            raise ValueError("latent_ap: remap goes with uint8 labels")
-        i32 = on(labels.to(torch.int32), torch.int32, (n_rows,), "labels")
-    else:
-        raise ValueError(f"labels must be uint8, int32 or int64, got {labels.dtype}")
-    lib = _lib.load()
-    layout = _lib.SaevLatentAPLayout()
-    _lib.check(lib, None, lib.saev_latent_ap_layout_of(n_rows, n_latents, n_classes, nnz, C.byref(layout)), "saev_latent_ap_layout_of")
-    ws = torch.empty(layout.total_bytes, device=device, dtype=torch.uint8)
-    ap = torch.empty(n_latents, n_classes, device=device, dtype=torch.float64)
-    n_pos = torch.empty(n_classes, device=device, dtype=torch.int64)
-    best_ap = torch.empty(n_latents, device=device, dtype=torch.float64)
-    best_class = torch.empty(n_latents, device=device, dtype=torch.int32)
+    lib, device, nnz, csr, classes, ws, layout = _ap_open("latent_ap", indptr, indices, data, n_rows, n_latents, n_classes, labels, remap, nnz)
+    out = dict(ap=torch.empty(n_latents, n_classes, device=device, dtype=torch.float64),
+               n_pos=torch.empty(n_classes, device=device, dtype=torch.int64),
+               best_ap=torch.empty(n_latents, device=device, dtype=torch.float64),
+               best_class=torch.empty(n_latents, device=device, dtype=torch.int32))
     with torch.cuda.device(device):
-        rc = lib.saev_latent_ap(_ptr(indptr), _ptr(indices), _ptr(data), nnz, n_rows, n_latents, n_classes, _ptr(u8), _ptr(remap), _ptr(i32),
-                                _ptr(ap), _ptr(n_pos), _ptr(best_ap), _ptr(best_class), _ptr(ws), ws.numel(), _stream())
+        rc = lib.saev_latent_ap(*map(_ptr, csr), nnz, n_rows, n_latents, n_classes, *map(_ptr, classes), *map(_ptr, out.values()), _ptr(ws),
+                                ws.numel(), _stream())
     _lib.check(lib, None, rc, "saev_latent_ap")
-    return LatentAPResult(ap, n_pos, best_ap, best_class, ws, layout, (n_rows, n_latents, n_classes, nnz))
+    return LatentAPResult(out, ws, layout, (n_rows, n_latents, n_classes, nnz))
 
 
-class ProbeAPResult:
+class ProbeAPResult(_APResult):
     """What ``probe_ap`` leaves on the device: ``ap`` (S, C) float64 (NaN for a pair whose w or b is not finite), ``n_pos`` (C) int64,
     ``tp`` and ``n_pred_pos`` (S, C) int64 (rows with score > 0, and those of them in the class) and ``top_rows`` (S, top_k) int64 or
     None.  The call itself does not synchronise; the first read of a result -- or ``check()`` -- reads the device's error word (one
     synchronisation) and raises ValueError if it is not 0.  ``layout`` is the workspace's, as of ``latent_ap``
     (include/saev_amd.h: PROBE AP)."""
 
+    _WHO = "probe_ap"
     _ERRORS = {**LatentAPResult._ERRORS, 3: "a stored value is not finite"}
-
-    def __init__(self, ap, n_pos, tp, n_pred_pos, top_rows, ws, layout, shape):
-        self._out = dict(ap=ap, n_pos=n_pos, tp=tp, n_pred_pos=n_pred_pos, top_rows=top_rows)
-        self._ws, self.layout, self.shape = ws, layout, shape
-        self._checked = False
-
-    def check(self) -> None:
-        if not self._checked:
-            code = int(self._ws[self.layout.off_err:self.layout.off_err + 4].view(torch.int32).item())
-            if code != 0:
-                raise ValueError(f"probe_ap: {self._ERRORS.get(code, code)} (found on the device)")
-            self._checked = True
-
-    def _read(self, name):
-        self.check()
-        return self._out[name]
 
     ap = property(lambda self: self._read("ap"))
     n_pos = property(lambda self: self._read("n_pos"))
     tp = property(lambda self: self._read("tp"))
     n_pred_pos = property(lambda self: self._read("n_pred_pos"))
     top_rows = property(lambda self: self._read("top_rows"))
-
-    sorted_events = LatentAPResult.sorted_events
 
 
 def probe_ap(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_rows: int, n_latents: int, n_classes: int, *,
@@ -970,60 +966,26 @@ def probe_ap(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_
     recall at score > 0, and the ``top_k`` highest rows of every latent (include/saev_amd.h: PROBE AP).  x, ``labels``,
     ``remap`` and ``nnz`` as for ``latent_ap``; ``weights`` and ``biases`` (S, C), both float32 or both float64: their dtype is the
     arithmetic the score is rounded in.  One call, one workspace, no synchronisation; there is no CPU path."""
-    for name, v, hi in (("n_rows", n_rows, 2**31), ("n_latents", n_latents, 2**31), ("n_classes", n_classes, 4097)):
-        if not 1 <= v < hi:
-            raise ValueError(f"probe_ap: unsupported {name} {v} (1 <= {name} < {hi})")
-    if not 0 <= top_k <= n_rows:
-        raise ValueError(f"probe_ap: top_k {top_k} must lie in [0, n_rows = {n_rows}]")
-    device = indptr.device
-    if device.type != "cuda":
-        raise RuntimeError("probe_ap runs on a HIP device only (there is no CPU path)")
-    stored = indices.numel()
-    nnz = stored if nnz is None else int(nnz)
-    if not 0 <= nnz < 2**31 or nnz > stored:
-        raise ValueError(f"probe_ap: unsupported nnz {nnz} (0 <= nnz < 2^31, and at most the {stored} entries of indices)")
-
-    def on(t, dtype, shape, what):
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device:
-            raise ValueError(f"{what} must be {dtype} of shape {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        return t.contiguous()
-
-    indptr = on(indptr, torch.int64, (n_rows + 1,), "indptr")
-    indices = on(indices, torch.int32, (stored,), "indices")
-    data = on(data, torch.float32, (stored,), "data")
+    lib, device, nnz, csr, classes, ws, layout = _ap_open("probe_ap", indptr, indices, data, n_rows, n_latents, n_classes, labels, remap, nnz,
+                                                          top_k)
     if weights.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"weights must be float32 or float64, got {weights.dtype}")
-    weights = on(weights, weights.dtype, (n_latents, n_classes), "weights")
-    biases = on(biases, weights.dtype, (n_latents, n_classes), "biases")
-    u8 = i32 = None
-    if labels.dtype == torch.uint8:
-        u8 = on(labels, torch.uint8, (n_rows,), "labels")
-        if remap is not None:
-            remap = on(remap, torch.int32, (256,), "remap")
-    elif labels.dtype in (torch.int32, torch.int64):
-        if remap is not None:
-            raise ValueError("probe_ap: remap goes with uint8 labels")
-        i32 = on(labels.to(torch.int32), torch.int32, (n_rows,), "labels")
-    else:
-        raise ValueError(f"labels must be uint8, int32 or int64, got {labels.dtype}")
-    lib = _lib.load()
-    layout = _lib.SaevLatentAPLayout()
-    _lib.check(lib, None, lib.saev_latent_ap_layout_of(n_rows, n_latents, n_classes, nnz, C.byref(layout)), "saev_latent_ap_layout_of")
-    ws = torch.empty(layout.total_bytes, device=device, dtype=torch.uint8)
-    ap = torch.empty(n_latents, n_classes, device=device, dtype=torch.float64)
-    n_pos = torch.empty(n_classes, device=device, dtype=torch.int64)
-    tp = torch.empty(n_latents, n_classes, device=device, dtype=torch.int64)
-    n_pred_pos = torch.empty(n_latents, n_classes, device=device, dtype=torch.int64)
-    top_rows = torch.empty(n_latents, top_k, device=device, dtype=torch.int64) if top_k > 0 else None
+    weights = _on(weights, weights.dtype, (n_latents, n_classes), "weights", device)
+    biases = _on(biases, weights.dtype, (n_latents, n_classes), "biases", device)
+    pairs = dict(device=device, dtype=torch.int64)
+    out = dict(ap=torch.empty(n_latents, n_classes, device=device, dtype=torch.float64),
+               n_pos=torch.empty(n_classes, device=device, dtype=torch.int64),
+               tp=torch.empty(n_latents, n_classes, **pairs), n_pred_pos=torch.empty(n_latents, n_classes, **pairs),
+               top_rows=torch.empty(n_latents, top_k, **pairs) if top_k > 0 else None)
     with torch.cuda.device(device):
-        rc = lib.saev_probe_ap(_ptr(indptr), _ptr(indices), _ptr(data), nnz, n_rows, n_latents, n_classes, _ptr(u8), _ptr(remap), _ptr(i32),
-                               _ptr(weights), _ptr(biases), 0 if weights.dtype == torch.float32 else 1, _ptr(ap), _ptr(n_pos), _ptr(tp),
-                               _ptr(n_pred_pos), top_k, _ptr(top_rows), _ptr(ws), ws.numel(), _stream())
+        rc = lib.saev_probe_ap(*map(_ptr, csr), nnz, n_rows, n_latents, n_classes, *map(_ptr, classes), _ptr(weights), _ptr(biases),
+                               0 if weights.dtype == torch.float32 else 1, _ptr(out["ap"]), _ptr(out["n_pos"]), _ptr(out["tp"]),
+                               _ptr(out["n_pred_pos"]), top_k, _ptr(out["top_rows"]), _ptr(ws), ws.numel(), _stream())
     _lib.check(lib, None, rc, "saev_probe_ap")
-    return ProbeAPResult(ap, n_pos, tp, n_pred_pos, top_rows, ws, layout, (n_rows, n_latents, n_classes, nnz))
+    return ProbeAPResult(out, ws, layout, (n_rows, n_latents, n_classes, nnz))
 
 
-class PoolResult:
+class PoolResult(_Checked):
     """What ``pool_images`` leaves on the device: ``pooled`` (n_images, n_latents) float32.  The call itself does not synchronise; the
     first read of ``pooled`` reads the device's error word (one synchronisation) and raises ValueError if it is not 0.  ``ranges`` is
     the number of latent ranges (workgroups per image) the launch ran, ``range_len`` the latents of one."""
@@ -1031,17 +993,10 @@ class PoolResult:
     _ERRORS = {1: "a column index lies outside [0, n_latents)", 2: "a stored value is not finite", 3: "indptr is not a non-decreasing sequence of positions into indices"}
 
     def __init__(self, out, err, ranges, range_len):
-        self._out, self._err, self.ranges, self.range_len = out, err, ranges, range_len
-        self._checked = False
+        super().__init__(dict(pooled=out), err, self._ERRORS, "pool_images")
+        self.ranges, self.range_len = ranges, range_len
 
-    @property
-    def pooled(self) -> torch.Tensor:
-        if not self._checked:
-            code = int(self._err.item())
-            if code != 0:
-                raise ValueError(f"pool_images: {self._ERRORS.get(code, code)} (found on the device)")
-            self._checked = True
-        return self._out
+    pooled = property(lambda self: self._read("pooled"))
 
 
 def pool_images(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_images: int, tokens_per_image: int, n_latents: int,
@@ -1061,19 +1016,9 @@ def pool_images(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor,
             raise ValueError(f"pool_images: unsupported {name} {v} (1 <= {name} < 2^31)")
     if n_images * tokens_per_image >= 2**31:
         raise ValueError(f"pool_images: unsupported n_images * tokens_per_image {n_images * tokens_per_image} (below 2^31)")
-    device = indptr.device
-    if device.type != "cuda":
-        raise RuntimeError("pool_images runs on a HIP device only (there is no CPU path)")
+    device = _hip_device("pool_images", indptr.device)
     nnz = indices.numel()
-
-    def on(t, dtype, shape, what):
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device:
-            raise ValueError(f"{what} must be {dtype} of shape {tuple(shape)} on {device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        return t.contiguous()
-
-    indptr = on(indptr, torch.int64, (n_images * tokens_per_image + 1,), "indptr")
-    indices = on(indices, torch.int32, (nnz,), "indices")
-    data = on(data, torch.float32, (nnz,), "data")
+    indptr, indices, data = _csr_on(indptr, indices, data, n_images * tokens_per_image, nnz, device)
     lib = _lib.load()
     out = torch.empty(n_images, n_latents, device=device, dtype=torch.float32)
     err = torch.empty(1, device=device, dtype=torch.int32)
@@ -1145,9 +1090,8 @@ def l1_logistic(X: torch.Tensor, y: torch.Tensor, C: float, *, kkt_tol: float = 
     state = ws[layout.off_state:layout.off_state + 128].view(torch.float64)
     with torch.cuda.device(device):
         _lib.check(lib, None, lib.saev_l1_logistic_init(*common, _ptr(ws), ws.numel(), _stream()), "saev_l1_logistic_init")
-        code = int(ws[layout.off_err:layout.off_err + 4].view(torch.int32).item())
-        if code != 0:
-            raise ValueError("l1_logistic: " + {1: "X holds a value that is not finite", 2: "a class index lies outside [0, K)"}.get(code, str(code)) + " (found on the device)")
+        _check_err_word(ws[layout.off_err:layout.off_err + 4].view(torch.int32),
+                        {1: "X holds a value that is not finite", 2: "a class index lies outside [0, K)"}, "l1_logistic")
         left = max_iter
         while left > 0:
             step = min(check_every, left)

@@ -17,6 +17,7 @@ import pytest
 import scipy.sparse
 import torch
 
+import csr_cases
 import latent_ap_cases as K
 import latent_ap_restatement as R
 from conftest import GOLDEN
@@ -138,6 +139,20 @@ def test_sorted_events_equal_numpys_lexsort(designs, name):
     np.testing.assert_array_equal(latent, w_lat.astype(np.int32))
     np.testing.assert_array_equal(key.view(np.uint32), R.value_key(w_val))
     np.testing.assert_array_equal(row, w_row.astype(np.int32))
+
+
+@pytest.mark.parametrize("shift", [0, 333])
+def test_sorted_rows_across_empty_rows_and_a_block_that_does_not_start_at_0(shift):
+    """The row of a stored entry where indptr repeats (empty rows first, last and three in a run) and where it starts at ``shift``."""
+    d = csr_cases.empty_rows_block(shift)
+    res = _run(dict(d, c=3, cls=np.arange(d["n"], dtype=np.int32) % 3))
+    starts, key, latent, row = (t.cpu().numpy() for t in res.sorted_events())
+    order = csr_cases.by_latent(d, by_value=True)
+    np.testing.assert_array_equal(starts, np.concatenate([[0], np.cumsum(np.bincount(d["cols"], minlength=d["s"]))]))
+    np.testing.assert_array_equal(row, d["rows"][order])
+    np.testing.assert_array_equal(latent, d["cols"][order])
+    np.testing.assert_array_equal(key.view(np.uint32), R.value_key(d["vals"][order]))
+    res.ap  # (the error word is 0: the entries in front of the block were not read)
 
 
 def test_the_error_word_is_set_and_python_raises():

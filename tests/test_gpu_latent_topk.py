@@ -7,6 +7,7 @@ import pytest
 import scipy.sparse
 import torch
 
+import csr_cases
 import sae_ref as R
 from conftest import GOLDEN, load_golden
 from latent_topk_restatement import restate, restate_csr, restate_padded
@@ -135,6 +136,24 @@ def test_more_latents_than_the_scan_has_threads(S):
     for lo, hi in ((600, 1200), (0, 600)):
         acc.add(dev(idx[lo:hi]), dev(val[lo:hi]), dev(row_nnz[lo:hi]), dev(keep[lo:hi]), row_base=lo)
     same(acc.read(), restate_padded(idx, val, S, k, row_nnz=row_nnz, keep=keep))
+
+
+@pytest.mark.parametrize("shift", [0, 333])
+def test_csr_rows_across_empty_rows_and_a_block_that_does_not_start_at_0(shift):
+    """The row of a stored entry where indptr repeats (empty rows first, last and three in a run) and where it starts at ``shift``:
+    with k = 64 every entry of a latent is in its list, so top_row names the row of each."""
+    d = csr_cases.empty_rows_block(shift)
+    acc = lists(d["s"], 64)
+    acc.add_csr(dev(d["indptr"]), dev(d["indices"]), dev(d["data"]), row_base=0)
+    got = acc.read()
+    order = csr_cases.by_latent(d, by_value=True)
+    counts = np.bincount(d["cols"], minlength=d["s"])
+    np.testing.assert_array_equal(got.counts.numpy(), counts)
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    for j in range(d["s"]):
+        mine = order[starts[j]:starts[j + 1]]
+        np.testing.assert_array_equal(got.indices.numpy()[:counts[j], j], d["rows"][mine])
+        np.testing.assert_array_equal(got.values.numpy()[:counts[j], j].view(np.int32), d["vals"][mine].view(np.int32))
 
 
 def test_eight_updates_one_update_and_the_csr_form_give_the_same_bits():

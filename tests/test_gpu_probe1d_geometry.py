@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import csr_cases
 import probe1d_cases as K
 import probe1d_restatement as R
 
@@ -126,6 +127,42 @@ def test_row_ptr_holds_absolute_positions(placed):
     q._call("saev_probe1d_prepare", engine._ptr(indptr), engine._ptr(indices), engine._ptr(data), d.nnz, d.n, d.s, d.c, engine._ptr(ids), None, None)
     assert int(q.err.item()) == 0
     _same_bits(_left_by_prepare(q), _left_by_prepare(p))
+
+
+def _prepare_raw(d):
+    """saev_probe1d_prepare on a block whose indptr holds absolute positions, two classes, every row in class 0."""
+    engine = _engine()
+    q = engine.Probe1D(d["n"], d["s"], 2, d["nnz"], "cuda")
+    csr = [_cuda(d[k]) for k in ("indptr", "indices", "data")]
+    ids = _cuda(np.zeros(d["n"], dtype=np.uint8))
+    q._call("saev_probe1d_prepare", *map(engine._ptr, csr), d["nnz"], d["n"], d["s"], 2, engine._ptr(ids), None, None)
+    assert int(q.err.item()) == 0
+    return q
+
+
+@pytest.mark.parametrize("shift", [0, 333])
+def test_rows_across_empty_rows_and_a_block_that_does_not_start_at_0(shift):
+    """The row of a stored entry where indptr repeats (empty rows first, last and three in a run) and where it starts at ``shift``."""
+    d = csr_cases.empty_rows_block(shift)
+    q = _prepare_raw(d)
+    order = csr_cases.by_latent(d, by_value=False)
+    np.testing.assert_array_equal(q.starts.cpu().numpy(), np.concatenate([[0], np.cumsum(np.bincount(d["cols"], minlength=d["s"]))]))
+    np.testing.assert_array_equal(q.row.cpu().numpy(), d["rows"][order])
+    np.testing.assert_array_equal(q.val.cpu().numpy().view(np.uint32), d["vals"][order].view(np.uint32))
+
+
+@pytest.mark.parametrize("s", [1023, 1024, 1025, 2049])
+def test_starts_where_the_scan_ends_a_round(s):
+    """One latent short of a round of 1 024, exactly one, one more, and one more than two: starts and chunk_starts are the running
+    sums of the counts and of the chunk counts, the last latent holding two chunks."""
+    d = csr_cases.scan_rounds_block(s)
+    q = _prepare_raw(d)
+    counts = np.bincount(d["indices"], minlength=s)
+    assert counts[s - 1] == d["n"] > K.CHUNK
+    np.testing.assert_array_equal(q.starts.cpu().numpy(), np.concatenate([[0], np.cumsum(counts)]))
+    np.testing.assert_array_equal(q.chunk_starts.cpu().numpy(), np.concatenate([[0], np.cumsum(-(-counts // K.CHUNK))]))
+    rows = np.repeat(np.arange(d["n"]), 6)
+    np.testing.assert_array_equal(q.row.cpu().numpy(), rows[np.lexsort((rows, d["indices"]))])
 
 
 def test_a_second_prepare_leaves_what_a_first_one_would(placed):

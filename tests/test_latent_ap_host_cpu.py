@@ -123,18 +123,51 @@ BAD = [
 ]
 
 
-@pytest.mark.parametrize("case", BAD, ids=[c[0] for c in BAD])
-def test_the_call_refuses_bad_arguments_without_a_device(case):
-    _, lib = _lib()
-    _, over, status = case
+def _call(lib, over):
     a = dict(SHAPE, row_ptr=_fake(0), indices=_fake(1), data=_fake(2), u8=_fake(3), remap=None, i32=None, ap=_fake(4), pos=_fake(5), best_ap=_fake(6),
              best_class=_fake(7), ws=C.c_void_p(1 << 20), ws_short=0)
     a.update(over)
     need = lib.saev_latent_ap_workspace_bytes(100, 64, 11, 800)
-    rc = lib.saev_latent_ap(a["row_ptr"], a["indices"], a["data"], a["nnz"], a["N"], a["S"], a["C"], a["u8"], a["remap"], a["i32"], a["ap"], a["pos"],
-                            a["best_ap"], a["best_class"], a["ws"], need - a["ws_short"], None)
+    return lib.saev_latent_ap(a["row_ptr"], a["indices"], a["data"], a["nnz"], a["N"], a["S"], a["C"], a["u8"], a["remap"], a["i32"], a["ap"], a["pos"],
+                              a["best_ap"], a["best_class"], a["ws"], need - a["ws_short"], None)
+
+
+@pytest.mark.parametrize("case", BAD, ids=[c[0] for c in BAD])
+def test_the_call_refuses_bad_arguments_without_a_device(case):
+    _, lib = _lib()
+    _, over, status = case
+    rc = _call(lib, over)
     assert rc == status, (rc, lib.saev_last_error(None))
     assert lib.saev_last_error(None).startswith(b"saev_latent_ap:")
+
+
+# status and saev_last_error(NULL) of the refusals this entry shares with saev_probe_ap and the saev_probe1d_* entries, word for word as
+# the library gave them when every entry made these checks itself; the last three are the FIRST refusal of two bad arguments at once
+EXACT = [
+    ("negative_n", dict(N=-1), INVALID, "negative size"),
+    ("latents_2_31", dict(S=1 << 31), UNSUPPORTED, "N, S and nnz must stay below 2^31"),
+    ("zero_rows", dict(N=0), INVALID, "N and S must be at least 1"),
+    ("too_many_classes", dict(C=4097), UNSUPPORTED, "the number of classes must lie in [1, 4096]"),
+    ("null_row_ptr", dict(row_ptr=None), INVALID, "row_ptr is NULL"),
+    ("null_data", dict(data=None), INVALID, "indices and data come with nnz > 0"),
+    ("both_label_forms", dict(i32=_fake(8)), INVALID, "give the classes as class_u8 (with an optional remap) or as class_i32, one of the two"),
+    ("remap_without_bytes", dict(u8=None, i32=_fake(8), remap=_fake(9)), INVALID, "remap goes with class_u8"),
+    ("null_ap", dict(ap=None), INVALID, "ap and pos must not be NULL"),
+    ("workspace_null", dict(ws=None), INVALID, "workspace smaller than saev_latent_ap_workspace_bytes(N, S, C, nnz)"),
+    ("workspace_too_small", dict(ws_short=1), INVALID, "workspace smaller than saev_latent_ap_workspace_bytes(N, S, C, nnz)"),
+    ("workspace_misaligned", dict(ws=C.c_void_p((1 << 20) + 8)), INVALID, "workspace must be 256-byte aligned"),
+    ("size_before_pointers", dict(C=4097, row_ptr=None, ws=None), UNSUPPORTED, "the number of classes must lie in [1, 4096]"),
+    ("labels_before_outputs", dict(i32=_fake(8), ap=None), INVALID, "give the classes as class_u8 (with an optional remap) or as class_i32, one of the two"),
+    ("outputs_before_workspace", dict(pos=None, ws_short=1), INVALID, "ap and pos must not be NULL"),
+]
+
+
+@pytest.mark.parametrize("case", EXACT, ids=[c[0] for c in EXACT])
+def test_shared_refusals_keep_their_status_and_their_text(case):
+    _, lib = _lib()
+    _, over, status, text = case
+    assert _call(lib, over) == status
+    assert lib.saev_last_error(None).decode() == "saev_latent_ap: " + text
 
 
 def test_python_surface_refuses_host_tensors_and_bad_labels():

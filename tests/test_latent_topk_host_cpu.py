@@ -119,10 +119,7 @@ BAD_CALLS = [
 ]
 
 
-@pytest.mark.parametrize("case", BAD_CALLS, ids=[c[0] for c in BAD_CALLS])
-def test_update_refuses_bad_arguments_without_a_device(case):
-    lib_mod, lib = _lib()
-    _, over, status = case
+def _update(lib_mod, lib, over):
     a = dict(PADDED, row_nnz=None, cap=8, row_ptr=None, indices=None, data=None, nnz=0, keep=None, n=100, S=512, row_base=0, k=5,
              ws=C.c_void_p(1 << 20), ws_short=0, top_val=_fake(0), top_row=_fake(1), top_cnt=_fake(2))
     a.update(over)
@@ -130,11 +127,44 @@ def test_update_refuses_bad_arguments_without_a_device(case):
     state = a.get("state", C.byref(st))
     need = lib.saev_latent_topk_workspace_bytes(800, 512)
     assert need > 0
-    rc = lib.saev_latent_topk_update(a["idx"], a["val"], a["row_nnz"], a["cap"], a["row_ptr"], a["indices"], a["data"], a["nnz"], a["keep"],
-                                     a["n"], a["S"], a["row_base"], state, a["ws"], need - a["ws_short"], None)
+    return lib.saev_latent_topk_update(a["idx"], a["val"], a["row_nnz"], a["cap"], a["row_ptr"], a["indices"], a["data"], a["nnz"], a["keep"],
+                                       a["n"], a["S"], a["row_base"], state, a["ws"], need - a["ws_short"], None)
+
+
+@pytest.mark.parametrize("case", BAD_CALLS, ids=[c[0] for c in BAD_CALLS])
+def test_update_refuses_bad_arguments_without_a_device(case):
+    lib_mod, lib = _lib()
+    _, over, status = case
+    rc = _update(lib_mod, lib, over)
     assert rc == status, case[0]
     msg = lib.saev_last_error(None).decode()
     assert msg.startswith("saev_latent_topk_update:"), msg  # refused with a message
+
+
+# status and saev_last_error(NULL) word for word, as the library gave them when the entry carried the whole message in each check
+EXACT = {
+    "negative_n": "negative size", "k_65": "k must lie in [1, 64]", "null_state": "no saev_latent_topk_state (or its struct_size is unset)",
+    "null_top_row": "a state pointer is NULL",
+    "both_forms": "give the codes as padded rows (idx, val) or as CSR (row_ptr, indices, data), one of the two",
+    "idx_without_val": "idx and val come together", "csr_without_data": "row_ptr, indices and data come together",
+    "row_nnz_with_csr": "row_nnz belongs to the padded form", "negative_row_base": "row_base + n leaves int64",
+    "too_many_entries": "more than 2^31 - 1 entries in one batch",
+    "workspace_too_small": "workspace smaller than saev_latent_topk_workspace_bytes(entries, S)",
+    "workspace_too_small_csr": "workspace smaller than saev_latent_topk_workspace_bytes(entries, S)",
+    "workspace_null": "workspace smaller than saev_latent_topk_workspace_bytes(entries, S)",
+    "workspace_misaligned": "workspace must be 256-byte aligned",
+}
+
+
+def test_refusals_keep_their_status_and_their_text():
+    lib_mod, lib = _lib()
+    cases = {name: (over, status) for name, over, status in BAD_CALLS}
+    for name, text in EXACT.items():
+        over, status = cases[name]
+        assert _update(lib_mod, lib, over) == status, name
+        assert lib.saev_last_error(None).decode() == "saev_latent_topk_update: " + text, name
+    assert _update(lib_mod, lib, dict(S=1 << 31)) == INVALID
+    assert lib.saev_last_error(None).decode() == "saev_latent_topk_update: size above 2^31 - 1"
 
 
 def test_an_empty_batch_is_accepted_and_touches_nothing():

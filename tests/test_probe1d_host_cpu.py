@@ -169,6 +169,73 @@ def test_stats_and_evaluate_refuse_bad_arguments_without_a_device():
     assert lib.saev_probe1d_layout_of(4, 4, 4097, 0, C.byref(lib_mod.SaevProbe1DLayout())) == UNSUPPORTED
 
 
+# status and saev_last_error(NULL) word for word, as the library gave them when p1_open and p1_cfg formatted their own messages
+P1_EXACT = [
+    (dict(N=-1), INVALID, "negative size"),
+    (dict(S=1 << 31), UNSUPPORTED, "N, S and nnz must stay below 2^31"),
+    (dict(N=0), INVALID, "N and S must be at least 1"),
+    (dict(C=4097), UNSUPPORTED, "the number of classes must lie in [1, 4096]"),
+    (dict(ws=None), INVALID, "workspace smaller than saev_probe1d_workspace_bytes(N, S, C, nnz)"),
+    (dict(ws_short=1), INVALID, "workspace smaller than saev_probe1d_workspace_bytes(N, S, C, nnz)"),
+    (dict(ws=C.c_void_p((1 << 20) + 8)), INVALID, "workspace must be 256-byte aligned"),
+]
+P1_ENTRIES = ("prepare", "stats", "init", "update", "fit", "evaluate")
+
+
+@pytest.mark.parametrize("entry", P1_ENTRIES)
+def test_every_entry_keeps_the_status_and_the_text_of_the_shared_refusals(entry):
+    lib_mod, lib = _lib()
+    cfg = C.byref(_cfg(lib_mod))
+    for over, status, text in P1_EXACT:
+        a = dict(SHAPE, ws=C.c_void_p(1 << 20), ws_short=0)
+        a.update(over)
+        shape = (a["N"], a["S"], a["C"], a["nnz"])
+        tail = (a["ws"], lib.saev_probe1d_workspace_bytes(*SHAPE.values()) - a["ws_short"], None)
+        if entry == "prepare":  # (its own arguments are all bad: the shared checks come first)
+            rc = lib.saev_probe1d_prepare(None, None, None, a["nnz"], a["N"], a["S"], a["C"], None, None, None, *tail)
+        elif entry == "stats":
+            rc = lib.saev_probe1d_stats(*shape, None, None, None, *tail)
+        elif entry == "init":
+            rc = lib.saev_probe1d_init(*shape, None, *tail)
+        elif entry == "update":
+            rc = lib.saev_probe1d_update(*shape, None, None, None, None, *tail)
+        elif entry == "fit":
+            rc = lib.saev_probe1d_fit(*shape, cfg, _fake(0), _fake(1), _fake(2), *tail)
+        else:
+            rc = lib.saev_probe1d_evaluate(*shape, None, None, 2.0, 7, None, None, None, None, None, *tail)
+        assert rc == status, (entry, over)
+        assert lib.saev_last_error(None).decode() == f"saev_probe1d_{entry}: {text}", (entry, over)
+
+
+def test_prepare_and_cfg_refusals_keep_their_text():
+    lib_mod, lib = _lib()
+    shape = tuple(SHAPE.values())
+    ws, nb = C.c_void_p(1 << 20), lib.saev_probe1d_workspace_bytes(*shape)
+    n, s, c, nnz = shape
+    for args, text in [
+        ((None, _fake(1), _fake(2), nnz, n, s, c, _fake(3), None, None), "row_ptr is NULL"),
+        ((_fake(0), None, _fake(2), nnz, n, s, c, _fake(3), None, None), "indices and data come with nnz > 0"),
+        ((_fake(0), _fake(1), _fake(2), nnz, n, s, c, _fake(3), _fake(8), None),
+         "give the labels as class ids (uint8 or int32) or as an N x C 0/1 matrix, one of the three"),
+        ((_fake(0), _fake(1), _fake(2), nnz, n, s, 300, _fake(3), None, None), "uint8 class ids cannot name more than 256 classes"),
+    ]:
+        need = lib.saev_probe1d_workspace_bytes(*args[4:7], nnz)
+        assert lib.saev_probe1d_prepare(*args, ws, need, None) == INVALID
+        assert lib.saev_last_error(None).decode() == "saev_probe1d_prepare: " + text
+    for over, text in [(None, "no saev_probe1d_cfg (or its struct_size is unset)"), (dict(max_iter=-1), "max_iter must be >= 0"),
+                       (dict(out_dtype=2), "out_dtype must be SAEV_PROBE1D_F32 or SAEV_PROBE1D_F64"), (dict(lam_shrink=1.0), "lam_shrink must lie in (0, 1)"),
+                       (dict(lam_init=0.0), "ridge and tol must be >= 0 and lam_init > 0")]:
+        cfg = None if over is None else C.byref(_cfg(lib_mod, **over))
+        assert lib.saev_probe1d_init(*shape, cfg, ws, nb, None) == INVALID
+        assert lib.saev_last_error(None).decode() == "saev_probe1d_init: " + text
+        assert lib.saev_probe1d_update(*shape, cfg, None, None, None, ws, nb, None) == INVALID
+        assert lib.saev_last_error(None).decode() == "saev_probe1d_update: " + text
+        assert lib.saev_probe1d_fit(*shape, cfg, _fake(0), _fake(1), _fake(2), ws, nb, None) == INVALID
+        assert lib.saev_last_error(None).decode() == "saev_probe1d_fit: " + text
+    assert lib.saev_probe1d_layout_of(4, 4, 4097, 0, C.byref(lib_mod.SaevProbe1DLayout())) == UNSUPPORTED
+    assert lib.saev_last_error(None).decode() == "saev_probe1d_layout_of: 1 <= N, S < 2^31, 1 <= C <= 4096, 0 <= nnz < 2^31"
+
+
 def test_python_entries_refuse_bad_arguments():
     _lib()
     from saev_amd import probe1d

@@ -80,18 +80,57 @@ BAD = [
 ]
 
 
-@pytest.mark.parametrize("case", BAD, ids=[c[0] for c in BAD])
-def test_the_call_refuses_bad_arguments_without_a_device(case):
-    _, lib = _lib()
-    _, over, status = case
+def _call(lib, over):
     a = dict(SHAPE, row_ptr=_fake(0), indices=_fake(1), data=_fake(2), u8=_fake(3), remap=None, i32=None, w=_fake(10), b=_fake(11), score_dtype=0,
              ap=_fake(4), pos=_fake(5), tp=_fake(6), pred_pos=_fake(7), top_k=0, top_row=_fake(12), ws=C.c_void_p(1 << 20), ws_short=0)
     a.update(over)
     need = lib.saev_latent_ap_workspace_bytes(100, 64, 11, 800)
-    rc = lib.saev_probe_ap(a["row_ptr"], a["indices"], a["data"], a["nnz"], a["N"], a["S"], a["C"], a["u8"], a["remap"], a["i32"], a["w"], a["b"],
-                           a["score_dtype"], a["ap"], a["pos"], a["tp"], a["pred_pos"], a["top_k"], a["top_row"], a["ws"], need - a["ws_short"], None)
+    return lib.saev_probe_ap(a["row_ptr"], a["indices"], a["data"], a["nnz"], a["N"], a["S"], a["C"], a["u8"], a["remap"], a["i32"], a["w"], a["b"],
+                             a["score_dtype"], a["ap"], a["pos"], a["tp"], a["pred_pos"], a["top_k"], a["top_row"], a["ws"], need - a["ws_short"], None)
+
+
+@pytest.mark.parametrize("case", BAD, ids=[c[0] for c in BAD])
+def test_the_call_refuses_bad_arguments_without_a_device(case):
+    _, lib = _lib()
+    _, over, status = case
+    rc = _call(lib, over)
     assert rc == status, (rc, lib.saev_last_error(None))
     assert lib.saev_last_error(None).startswith(b"saev_probe_ap:")
+
+
+# status and saev_last_error(NULL), word for word as the library gave them when this entry made every check itself: the refusals it
+# shares with saev_latent_ap, its own where they sit among those, and the FIRST refusal of two bad arguments at once
+EXACT = [
+    ("negative_nnz", dict(nnz=-1), INVALID, "negative size"),
+    ("latents_2_31", dict(S=1 << 31), UNSUPPORTED, "N, S and nnz must stay below 2^31"),
+    ("zero_latents", dict(S=0), INVALID, "N and S must be at least 1"),
+    ("too_many_classes", dict(C=4097), UNSUPPORTED, "the number of classes must lie in [1, 4096]"),
+    ("null_row_ptr", dict(row_ptr=None), INVALID, "row_ptr is NULL"),
+    ("null_indices", dict(indices=None), INVALID, "indices and data come with nnz > 0"),
+    ("both_label_forms", dict(i32=_fake(8)), INVALID, "give the classes as class_u8 (with an optional remap) or as class_i32, one of the two"),
+    ("remap_without_bytes", dict(u8=None, i32=_fake(8), remap=_fake(9)), INVALID, "remap goes with class_u8"),
+    ("null_w", dict(w=None), INVALID, "w and b must not be NULL"),
+    ("score_dtype_2", dict(score_dtype=2), INVALID, "score_dtype is 0 (fp32) or 1 (fp64)"),
+    ("null_tp", dict(tp=None), INVALID, "ap, pos, tp and pred_pos must not be NULL"),
+    ("top_k_above_n", dict(top_k=101), INVALID, "top_k must lie in [0, N]"),
+    ("top_k_without_top_row", dict(top_k=5, top_row=None), INVALID, "top_row comes with top_k > 0"),
+    ("workspace_null", dict(ws=None), INVALID, "workspace smaller than saev_latent_ap_workspace_bytes(N, S, C, nnz)"),
+    ("workspace_too_small", dict(ws_short=1), INVALID, "workspace smaller than saev_latent_ap_workspace_bytes(N, S, C, nnz)"),
+    ("workspace_misaligned", dict(ws=C.c_void_p((1 << 20) + 8)), INVALID, "workspace must be 256-byte aligned"),
+    ("size_before_top_k", dict(N=0, top_k=5), INVALID, "N and S must be at least 1"),
+    ("labels_before_weights", dict(u8=None, w=None), INVALID, "give the classes as class_u8 (with an optional remap) or as class_i32, one of the two"),
+    ("weights_before_dtype", dict(b=None, score_dtype=2), INVALID, "w and b must not be NULL"),
+    ("dtype_before_outputs", dict(score_dtype=-1, ap=None), INVALID, "score_dtype is 0 (fp32) or 1 (fp64)"),
+    ("top_k_before_workspace", dict(top_k=-1, ws_short=1), INVALID, "top_k must lie in [0, N]"),
+]
+
+
+@pytest.mark.parametrize("case", EXACT, ids=[c[0] for c in EXACT])
+def test_refusals_keep_their_status_their_text_and_their_order(case):
+    _, lib = _lib()
+    _, over, status, text = case
+    assert _call(lib, over) == status
+    assert lib.saev_last_error(None).decode() == "saev_probe_ap: " + text
 
 
 def test_python_surface_refuses_host_tensors_and_bad_arguments():

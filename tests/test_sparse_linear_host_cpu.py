@@ -160,6 +160,50 @@ def test_l1_logistic_refuses_bad_arguments_without_a_device(case, entry):
     assert lib.saev_last_error(None).startswith(b"saev_l1_logistic_" + entry.encode() + b":")
 
 
+# status and saev_last_error(NULL) word for word, as the library gave them when each entry formatted its own message
+L1_EXACT = {
+    "negative_n": "negative size", "one_class": "fewer than two classes", "too_many_classes": "1 <= n < 2^31, 1 <= S <= 2^30, 2 <= K <= 64",
+    "rows_2_31": "1 <= n < 2^31, 1 <= S <= 2^30, 2 <= K <= 64", "nan_C": "C must be positive and finite", "negative_tol": "kkt_tol must not be negative",
+    "null_y": "X and y must not be NULL", "workspace_null": "workspace smaller than saev_l1_logistic_workspace_bytes(n, S, K)",
+    "workspace_too_small": "workspace smaller than saev_l1_logistic_workspace_bytes(n, S, K)", "workspace_misaligned": "workspace must be 256-byte aligned",
+}
+POOL_EXACT = {
+    "negative_images": "negative size", "zero_tpi": "n_images, tokens_per_image and n_latents must be at least 1",
+    "rows_2_31": "n_images * tokens_per_image and n_latents must stay below 2^31", "too_many_ranges": "more than 65535 latent ranges",
+    "bad_agg": "agg is SAEV_POOL_MAX or SAEV_POOL_MEAN", "negative_nnz": "negative nnz", "null_indptr": "indptr, out and err must not be NULL",
+    "null_data": "indices and data come with nnz > 0",
+}
+
+
+def test_refusals_keep_their_status_and_their_text():
+    _, lib = _lib()
+    need = lib.saev_l1_logistic_workspace_bytes(100, 64, 3)
+    cases = {name: (over, status) for name, over, status in L1_BAD}
+    for name, text in L1_EXACT.items():
+        over, status = cases[name]
+        a = dict(X=_fake(0), y=_fake(1), n=100, S=64, K=3, C=0.01, tol=1e-4, ws=C.c_void_p(1 << 20), ws_short=0)
+        a.update(over)
+        common = (a["X"], a["y"], a["n"], a["S"], a["K"], a["C"], a["tol"])
+        tail = (a["ws"], need - a["ws_short"], None)
+        for entry, call in (("init", lambda: lib.saev_l1_logistic_init(*common, *tail)), ("iterate", lambda: lib.saev_l1_logistic_iterate(*common, -1, *tail)),
+                            ("result", lambda: lib.saev_l1_logistic_result(*common, None, None, None, *tail))):
+            assert call() == status, (name, entry)
+            assert lib.saev_last_error(None).decode() == f"saev_l1_logistic_{entry}: {text}", (name, entry)
+    common = (_fake(0), _fake(1), 100, 64, 3, 0.01, 1e-4)
+    assert lib.saev_l1_logistic_iterate(*common, -1, C.c_void_p(1 << 20), need, None) == INVALID
+    assert lib.saev_last_error(None).decode() == "saev_l1_logistic_iterate: negative n_iters"
+    assert lib.saev_l1_logistic_result(*common, _fake(2), None, _fake(4), C.c_void_p(1 << 20), need, None) == INVALID
+    assert lib.saev_last_error(None).decode() == "saev_l1_logistic_result: coef, intercept and scalars must not be NULL"
+    cases = {name: (over, status) for name, over, status in POOL_BAD}
+    for name, text in POOL_EXACT.items():
+        over, status = cases[name]
+        a = dict(indptr=_fake(0), indices=_fake(1), data=_fake(2), nnz=800, n_images=10, tpi=4, S=64, agg=0, out=_fake(3), err=_fake(4))
+        a.update(over)
+        rc = lib.saev_pool_images(a["indptr"], a["indices"], a["data"], a["nnz"], a["n_images"], a["tpi"], a["S"], a["agg"], a["out"], a["err"], None)
+        assert rc == status, name
+        assert lib.saev_last_error(None).decode() == "saev_pool_images: " + text, name
+
+
 def test_iterate_and_result_refuse_their_own_arguments():
     _, lib = _lib()
     need = lib.saev_l1_logistic_workspace_bytes(100, 64, 3)
