@@ -426,7 +426,9 @@ int saev_backward_end(saev_ctx* ctx, void* stream);
  *   saev_aux_compact_rows / _export / _import.
  * Gradients carry the local 1/(n_local d_model) factor as in every data-parallel mode: tail with grad_scale = 1/world.
  * saev_trust_gradients(1) lets saev_step_tail use what the backward left behind (row statistics, tile squares) as
- * saev_train_step does -- the caller vouches that nothing writes the gradient between saev_backward_end and the tail. */
+ * saev_train_step does -- the caller vouches that nothing writes the gradient between saev_backward_end and the tail.
+ * All of this follows saev_step_forward: the forward inside saev_train_step keeps dL/dx_hat in the column-slice layout its own
+ * backward reads and writes no row-major copy, so g_out and a ranged backward behind it are SAEV_INVALID_ARG. */
 int saev_copy_step_state(saev_ctx* ctx, int32_t n_rows, float* g_out, int32_t* idx_out, float* val_out, void* stream);
 int saev_backward_override(saev_ctx* ctx, const float* x_all, const float* g_all, const int32_t* idx_all,
                            const float* val_all, int32_t n_all);

@@ -112,6 +112,8 @@ struct saev_ctx {
     bool wn2_fresh = false;  // wn2 describes W_dec as it is now (set by the training forward, cleared by whatever writes W_dec)
     bool dval_pairs_ready = false;  // the CSC build of this backward has written pv2 from it
     bool fused_forward = false;     // saev_train_step's forward: Matryoshka G blocks past the first are not needed row-major
+    // saev_train_step's plain forward on the slice route leaves dL/dx_hat slice-major alone (gS): its backward reads nothing else
+    bool g_rows_valid = true;       // the row-major g describes the training forward in flight
     // exact refinement of the f16r encoder from 32-column slices (select.hip: refine_slices_kernel): split_f16r leaves x and
     // W_enc^T slice-major (xS; dW_encT in that layout), rs_part holds the per-slice shares of the survivors' dot products
     bool fwd_slices = false;     // geometry fits and not switched off (saev_debug_cfg.fwd_route)

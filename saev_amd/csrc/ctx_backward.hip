@@ -52,10 +52,16 @@ int saev_backward_begin(saev_ctx* c, void* stream) {
     // db_dec = column sums of dL/dx_hat (Matryoshka: of the suffix sums C_0), formed in the grids of the CSC build's first two
     // launches; the AuxK contractions add theirs
     const float* gmat = ov ? c->ov_g : (c->P_last > 1 ? c->G : c->g);
+    // (saev_train_step's plain forward leaves dL/dx_hat slice-major alone: the same values, the same rows per partial, the same order)
+    const bool g_slices = !ov && c->P_last == 1 && !c->g_rows_valid;
+    if (g_slices) {
+        REQUIRE(c, c->dws_rows == n, SAEV_INVALID_ARG, "saev_backward_begin: the forward in flight left no gradient rows");
+        gmat = c->gS;
+    }
     // (prefilled: this forward's decode has set the bits of exactly these codes: no clear, no fill pass)
     const bool prefilled = !ov && c->bitmap_prefill_words == words && c->bitmap_prefill_rows == n;
     HIPCHK(c, launch_csc_build(a, s, c->bitmap_clean && words <= c->bitmap_clean_words, gmat, D, (long)c->P_last * D,
-                               c->colsum_partials, c->grads + c->off_b_dec, prefilled));
+                               c->colsum_partials, c->grads + c->off_b_dec, prefilled, g_slices));
     c->bitmap_prefill_words = 0;
     c->last_backward_gathered = ov;
     c->bitmap_clean = false;
@@ -87,6 +93,9 @@ int saev_backward_rows_part(saev_ctx* c, int32_t lat_lo, int32_t lat_hi, int32_t
     a.starts = c->starts; a.chunk_starts = c->chunk_starts; a.work_latent = c->work_latent;
     a.part_starts = c->part_starts; a.pairs = c->pairs; a.val = ov ? c->ov_val : c->val; a.W_dec = c->params + c->off_W_dec;
     a.g = ov ? c->ov_g : (c->P_last > 1 ? c->G : c->g);  // Matryoshka: rows receive the suffix-summed gradients C_p
+    const bool slices_all = lat_lo == 0 && lat_hi == S && c->dws_pairs && (ov || c->dws_rows == n);
+    REQUIRE(c, ov || c->P_last > 1 || c->g_rows_valid || slices_all, SAEV_INVALID_ARG,
+            "saev_backward_rows: the fused step's forward keeps no row-major gradient (a latent range needs the phase forward)");
     a.x = ov ? c->ov_x : c->x_last;
     a.D = D; a.S = S; a.k_dev = nullptr; a.accumulate = 0;
     a.P = c->P_last;
@@ -103,7 +112,7 @@ int saev_backward_rows_part(saev_ctx* c, int32_t lat_lo, int32_t lat_hi, int32_t
     a.enc_sq = all_rows ? c->enc_sq : nullptr;
     // upper bound of the work items of the range (one per latent + one per 64 pairs): the kernel knows the exact count
     const int max_work = (lat_hi - lat_lo) + (int)(((long)n * K + DW_CHUNK - 1) / DW_CHUNK);
-    if (lat_lo == 0 && lat_hi == S && c->dws_pairs && (ov || c->dws_rows == n)) {
+    if (slices_all) {
         // all latents of this context's own batch (in one pass or as the decoder / encoder halves of a two-pass backward): column slices out of the XCD L2s (kernels.h: DwSlicesArgs)
         DwSlicesArgs w{};
         w.starts = c->starts; w.pv = c->pv; w.pv2 = c->pv2; w.plat = c->plat; w.gS = c->P_last > 1 ? c->GS : c->gS; w.W_dec = a.W_dec; w.P = c->P_last;
@@ -167,6 +176,8 @@ int saev_copy_step_state(saev_ctx* c, int32_t n_rows, float* g_out, int32_t* idx
     hipStream_t s = (hipStream_t)stream;
     // (Matryoshka: P suffix-summed gradients per row, (n_rows, P, d_model) -- what the backward consumes in that case)
     const size_t nk = (size_t)n_rows * c->cfg.top_k, nd = (size_t)n_rows * c->cfg.d_model * (size_t)c->P_last;
+    REQUIRE(c, !g_out || c->P_last > 1 || c->g_rows_valid, SAEV_INVALID_ARG,
+            "saev_copy_step_state: the fused step's forward keeps no row-major gradient (use saev_step_forward)");
     if (g_out) HIPCHK(c, hipMemcpyAsync(g_out, c->P_last > 1 ? c->G : c->g, nd * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (idx_out) HIPCHK(c, hipMemcpyAsync(idx_out, c->idx, nk * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     if (val_out) HIPCHK(c, hipMemcpyAsync(val_out, c->val, nk * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -329,6 +329,9 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
     sd.h = c->h_dense; sd.n_rows = n; sd.S = c->cfg.d_sae; sd.k = K;
     sd.idx_out = idx_out; sd.val_out = val_out; sd.out_stride = K;
     sd.enable_flag = need_dense; sd.enable_when = 1;
+    // (behind the fused encoder this launch is a fallback that a healthy step leaves at its first instruction: four workgroups per
+    // CU that walk the rows retire in one round instead of n rounds' worth of empty workgroups; armed, the rows are the same)
+    if (fused_supported(c->cfg)) sd.walk_grid = 4 * 256;
     HIPCHK(c, launch_select_dense(sd, s));
     return SAEV_OK;
 }
@@ -653,6 +656,10 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
     if (training && c->dws_ok && (c->P == 1 || c->GS != nullptr)) { a.gS = c->P == 1 ? c->gS : c->GS; a.xS = c->fwd_step ? nullptr : c->xS; c->dws_rows = n; }
     // (... and the products dval, from the decoder rows while the decode holds them in registers)
     if (c->dws_rows == n && c->dval_rows != nullptr && (c->P == 1 || decode_matry_forms_dval(D, K))) { a.dval_out = c->dval_rows; c->dval_fwd = true; }
+    // (saev_train_step's own backward takes the column slices over all latents and the column sums of db_dec from gS as well: the
+    // plain decode writes no row-major g then -- n x d_model floats nobody reads.  The phases keep it: saev_copy_step_state, dw_rows)
+    c->g_rows_valid = !(c->train_fused && training && c->P == 1 && c->dws_rows == n);
+    if (!c->g_rows_valid) a.g = nullptr;
     // The decode reads every code anyway: it sets the (latent, row) bits of the backward's pair-list build (0.5 M scattered atomics
     // that csc_fill paid 35 us for on their own), provided the bit map is clean at this row pitch -- the previous full backward
     // cleared it behind itself -- and this context's backwards run over its own rows.

@@ -48,6 +48,8 @@ struct SelectDenseArgs {
     int out_stride;
     const int32_t* enable_flag;
     int enable_when;
+    int walk_grid;         // > 0: at most this many workgroups, each walking rows blockIdx.x, + gridDim.x, ... (a predicated launch
+                           // that is rarely armed then retires in one round of workgroups); 0: one workgroup per row
 };
 hipError_t launch_select_dense(const SelectDenseArgs& a, hipStream_t stream);
 
@@ -226,7 +228,8 @@ struct CscArgs {
 // grids of the fill / count launches (db_dec of the same backward: two launches instead of four)
 hipError_t launch_csc_build(const CscArgs& a, hipStream_t stream, bool bitmap_clean = false, const float* colsum_m = nullptr,
                             int colsum_D = 0, long colsum_row_stride = 0, float* colsum_partials = nullptr,
-                            float* colsum_out = nullptr, bool prefilled = false);  // prefilled: the decode has set the bits (DecodeArgs::csc_bitmap)
+                            float* colsum_out = nullptr, bool prefilled = false,  // prefilled: the decode has set the bits (DecodeArgs::csc_bitmap)
+                            bool colsum_slice_major = false);  // colsum_m is DecodeArgs::gS ([D / 32][n_rows][32 floats]), not a row-major matrix
 
 constexpr int DW_CHUNK = 64;   // pairs per work item of the weight-gradient kernels
 

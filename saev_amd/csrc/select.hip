@@ -47,13 +47,14 @@ __global__ __launch_bounds__(SD_THREADS) void select_dense_kernel(SelectDenseArg
     __shared__ int sh_digit, sh_need;
     __shared__ int wave_tot[4];
 
-    const int row = blockIdx.x;
     const int S = a.S;
     int k = a.k_dev ? min(*a.k_dev, a.k) : a.k;
     if (a.k_dev && k <= 0) return;
-    const float* h = a.h + (size_t)row * S;
     const int tid = threadIdx.x;
     const int S4 = S >> 2;
+    // (one row per workgroup, or -- SelectDenseArgs::walk_grid -- a short grid whose workgroups walk the rows)
+    for (int row = blockIdx.x; row < a.n_rows; row += gridDim.x) {
+    const float* h = a.h + (size_t)row * S;
 
     // number of eligible elements (mask) bounds k
     // (without a mask, k <= S is enforced by the host)
@@ -151,6 +152,8 @@ __global__ __launch_bounds__(SD_THREADS) void select_dense_kernel(SelectDenseArg
         }
         base_gt += tot & 0xFFFF;
         base_eq += tot >> 16;
+    }
+    __syncthreads();  // (the next row's histogram)
     }
 }
 
@@ -1062,7 +1065,8 @@ __global__ void heur_update_kernel(float* state, const int32_t* bad, const float
 
 hipError_t launch_select_dense(const SelectDenseArgs& a, hipStream_t stream) {
     if (a.n_rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(select_dense_kernel, dim3(a.n_rows), dim3(SD_THREADS), 0, stream, a);
+    const int grid = (a.walk_grid > 0 && a.walk_grid < a.n_rows) ? a.walk_grid : a.n_rows;
+    hipLaunchKernelGGL(select_dense_kernel, dim3(grid), dim3(SD_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 

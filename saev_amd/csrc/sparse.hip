@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs a) {
                 sse64 += (double)r * (double)r;
                 sumsq64 += (double)xv[e] * (double)xv[e];
             }
-            if (a.training) reinterpret_cast<f32x4*>(a.g + (size_t)row * D)[q] = g[n];
+            if (a.training && a.g != nullptr) reinterpret_cast<f32x4*>(a.g + (size_t)row * D)[q] = g[n];
             if (a.training && a.gS != nullptr) {  // slice-major copies for launch_dw_slices: [q / 8][row][8 float4]
                 const size_t o = ((size_t)(q >> 3) * a.n_rows + row) * 8 + (q & 7);
                 reinterpret_cast<f32x4*>(a.gS)[o] = g[n];
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(64 * NW) void decode_q_kernel(DecodeArgs a) {
         sumsq64 += (double)xv[e] * (double)xv[e];
     }
     if (a.training) {
-        reinterpret_cast<f32x4*>(a.g + (size_t)row * a.D)[q] = g;
+        if (a.g != nullptr) reinterpret_cast<f32x4*>(a.g + (size_t)row * a.D)[q] = g;  // (NULL: the caller reads gS alone)
         if (a.gS != nullptr) {
             const size_t o = ((size_t)(q >> 3) * a.n_rows + row) * 8 + (q & 7);
             reinterpret_cast<f32x4*>(a.gS)[o] = g;
@@ -1618,19 +1618,24 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* partials
 // ---- backward begin in two launches instead of four ---------------------------------------------------------------------
 // The column sums of dL/dx_hat (db_dec) are independent of the CSC build that runs next to them: their two passes ride in
 // the grids of csc_fill / csc_count (workgroups past the CSC part), so that the small kernels overlap instead of queueing.
-struct ColsumPlain { const float* m; int n_rows, D; float* partials; long row_stride; float* out; int n_blocks; };
+// (slice_major: m is DecodeArgs::gS, [D / 32][n_rows][8 float4], the same values as the row-major matrix: same rows per partial, same order)
+struct ColsumPlain { const float* m; int n_rows, D; float* partials; long row_stride; float* out; int n_blocks; int slice_major; };
 __device__ __forceinline__ void colsum_partial_plain(const ColsumPlain& c, int bid) {  // = colsum_partial_kernel<false>, k_dev = NULL
     const int r0 = bid * 64, r1 = min(c.n_rows, r0 + 64);
     for (int q = threadIdx.x; q < (c.D >> 2); q += 256) {
+        // float4 q of row r: base[r * pitch]
+        const f32x4* const base = c.slice_major ? reinterpret_cast<const f32x4*>(c.m) + (size_t)(q >> 3) * c.n_rows * 8 + (q & 7)
+                                                : reinterpret_cast<const f32x4*>(c.m) + q;
+        const size_t pitch = c.slice_major ? (size_t)8 : (size_t)(c.row_stride >> 2);
         f32x4 s = {0.f, 0.f, 0.f, 0.f};
         int r = r0;
         for (; r + 8 <= r1; r += 8) {
             f32x4 v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = reinterpret_cast<const f32x4*>(c.m + (size_t)(r + u) * c.row_stride)[q];
+            for (int u = 0; u < 8; ++u) v[u] = base[(size_t)(r + u) * pitch];
             s += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
         }
-        for (; r < r1; ++r) s += reinterpret_cast<const f32x4*>(c.m + (size_t)r * c.row_stride)[q];
+        for (; r < r1; ++r) s += base[(size_t)r * pitch];
         reinterpret_cast<f32x4*>(c.partials + (size_t)bid * c.D)[q] = s;
     }
 }
@@ -1808,7 +1813,7 @@ hipError_t launch_decode_matry(const DecodeArgs& a, const MatryArgs& m, hipStrea
     });
 }
 hipError_t launch_csc_build(const CscArgs& a, hipStream_t stream, bool bitmap_clean, const float* colsum_m, int colsum_D,
-                            long colsum_row_stride, float* colsum_partials, float* colsum_out, bool prefilled) {
+                            long colsum_row_stride, float* colsum_partials, float* colsum_out, bool prefilled, bool colsum_slice_major) {
     if (a.n_rows <= 0) return hipSuccess;
     const long n = (long)a.n_rows * a.k;
     // (prefilled: the bits of exactly these codes are set already -- no clear, and the first launch is the column sums alone)
@@ -1817,7 +1822,7 @@ hipError_t launch_csc_build(const CscArgs& a, hipStream_t stream, bool bitmap_cl
     if (!bitmap_clean && !prefilled) hipLaunchKernelGGL(csc_clear_kernel, dim3(2048), dim3(256), 0, stream, a);
     const int n_scan = (a.S + 1023) / 1024;
     ColsumPlain c{colsum_m, a.n_rows, colsum_D, colsum_partials, colsum_row_stride > 0 ? colsum_row_stride : (long)colsum_D,
-                  colsum_out, (a.n_rows + 63) / 64};
+                  colsum_out, (a.n_rows + 63) / 64, colsum_slice_major ? 1 : 0};
     int colsum_in_scan = 0;
     if (colsum_m != nullptr && prefilled && a.epoch != 0) {
         // the bits are there already: count + first stage of the column sums, then scan + their second stage -- three launches in all

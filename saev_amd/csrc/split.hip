@@ -364,10 +364,28 @@ __global__ __launch_bounds__(256) void bias_finish_kernel(const double* __restri
     float out = 0.f, nrm = 0.f, dnrm = 0.f;
     if (sidx < S) {
         double acc = 0.0, sq = 0.0, dsq = 0.0;
-        for (int ks = 0; ks < nks; ++ks) {
-            acc += dot_part[(size_t)ks * S_pad + sidx];
-            sq += (double)sq_part[(size_t)ks * S_pad + sidx];
-            dsq += (double)sq_part[(size_t)(nks + ks) * S_pad + sidx];
+        // sixteen shares of each of the three sums are requested before the first add (48 loads in flight per thread: the kernel
+        // is one wave per SIMD on half the CUs, all latency); the adds keep their order, share by share
+        constexpr int CH = 16;
+#pragma unroll 1
+        for (int k0 = 0; k0 < nks; k0 += CH) {
+            double va[CH];
+            float vs[CH], vd[CH];
+#pragma unroll
+            for (int j = 0; j < CH; ++j) {
+                const int ks = min(k0 + j, nks - 1);  // (past the end: a share that is loaded again and not added)
+                va[j] = dot_part[(size_t)ks * S_pad + sidx];
+                vs[j] = sq_part[(size_t)ks * S_pad + sidx];
+                vd[j] = sq_part[(size_t)(nks + ks) * S_pad + sidx];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < CH; ++j)
+                if (k0 + j < nks) {
+                    acc += va[j];
+                    sq += (double)vs[j];
+                    dsq += (double)vd[j];
+                }
         }
         const double sc = (double)(*w_scale);
         const float be = b_enc[sidx];
