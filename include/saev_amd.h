@@ -923,6 +923,51 @@ int saev_probe_ap(const int64_t* row_ptr, const int32_t* indices, const float* d
                   double* ap, int64_t* pos, int64_t* tp, int64_t* pred_pos,   /* S x C, C, S x C, S x C */
                   int32_t top_k, int64_t* top_row,                            /* S x top_k, or top_k = 0 and NULL */
                   void* workspace, int64_t workspace_bytes, void* stream);
+/* LATENT AUROC (the reference's contrib/mimics mimics.scoring: every latent ranked by AUROC on every binary task; and the
+ * one-vs-rest companion of LATENT AP at token level), context-free; DESIGN.md 3.23.  AUROC[j, t] of latent j's activation as a
+ * detector of task t's positives against its negatives over the N rows, EXACT AND TIE-AWARE (the Mann-Whitney statistic with a tied
+ * pair counted half), for all S x T pairs in one call, with the per-role supports and sums of the activation.
+ * CARRIED OVER FROM LATENT AP UNCHANGED: x, the shapes and their limits, the two label forms, the event rule (a stored +-0.0 is no
+ * event; negative values and +-Inf are ordered events), pos, the sorted arrays left behind in the workspace, the argument checks
+ * before the device is touched, saev_last_error(NULL); nothing is allocated, nothing is read back, nothing synchronises; integer
+ * atomics only.
+ * TASKS: role is T x C uint8, row-major, on the device: role[t, c] = 0 leaves the rows of class c out of task t, 1 makes them its
+ * negatives, 2 its positives.  1 <= T <= 4096 (else SAEV_UNSUPPORTED, and -1 from the workspace-size function).  A row of class -1
+ * is left out of every task.  Tasks may overlap freely.  A role byte above 2 sets SAEV_LATENT_AUROC_ERR_ROLE in the error word.
+ * COUNTS: n_pos[t] / n_neg[t] = the rows whose class has role 2 / 1 in task t.
+ * STATISTIC: a TIE GROUP is a maximal set of rows of equal activation (fp32 ==; a row without an event has activation 0).  For task
+ * t, over its included rows only and the groups taken in descending order, with p_g / q_g the group's positives / negatives and P_g
+ * the positives in strictly higher groups:
+ *   U2[j, t] = sum_g (2 q_g P_g + p_g q_g)        = 2 x (pairs with the positive strictly above the negative) + (tied pairs).
+ * The rows without an event are ONE group between the positive and the negative values; one forward walk of the events in (value
+ * descending) order computes the sum as if that group were absent and keeps Ppos (positives among the events of value > 0), Qneg
+ * (negatives among the events of value < 0) and the event totals Pev, Qev; with p0 = n_pos - Pev and q0 = n_neg - Qev the walk ends
+ * with U2 += 2 q0 Ppos + p0 q0 + 2 p0 Qneg.  All of it is int64: U2 <= 2 n_pos n_neg < 2^62.
+ *   auroc[j, t] = (double)U2 / ((2.0 * (double)n_pos) * (double)n_neg), one fp64 division, no contraction; NaN (0x7ff8000000000000)
+ * when n_pos n_neg = 0 (U2 is 0 then).  A latent without events gets exactly 0.5.
+ * PER-ROLE STATISTICS: fire_pos / fire_neg[j, t] = the included rows of that role with value > 0; sum_pos / sum_neg[j, t] = the event
+ * values of that role, each converted exactly to fp64 and added one at a time in walk order (value descending, row ascending) to a
+ * sum that starts at +0; a non-finite sum is what IEEE gives.
+ * DETERMINISM: a pair's outputs depend on its own latent's events, the row classes and its own row of role only -- not on other
+ * latents or tasks, T, the launch or timing; two calls give the same bits, a task scored alone gives the bits it has among others,
+ * and so does a latent.
+ * OUTPUTS (device): auroc (S x T fp64), u2 (S x T int64), n_pos and n_neg (T int64), fire_pos and fire_neg (S x T int64), sum_pos and
+ * sum_neg (S x T fp64), pos (C int64); none may be NULL, nor may role (SAEV_INVALID_ARG).  err is int32[0] at off_err of the
+ * workspace: 0, or the largest of SAEV_LATENT_AP_ERR_CLASS, SAEV_LATENT_AP_ERR_LATENT and SAEV_LATENT_AUROC_ERR_ROLE met on the
+ * device; the outputs are void if it is not 0.
+ * WORKSPACE: saev_latent_auroc_workspace_bytes(N, S, C, T, nnz) bytes, 256-byte aligned.  It BEGINS with LATENT AP's layout for
+ * (N, S, C, nnz) -- saev_latent_ap_layout_of locates err, starts and the sorted arrays -- and at that layout's total_bytes follows
+ * the class-major role table: (C + 1) rows of Tp = 64 ceil(T / 64) bytes, row c + 1 = the roles of class c in tasks 0 .. Tp - 1
+ * (0 behind T, and for a byte above 2), row 0 = zeros for class -1.  Nothing else. */
+#define SAEV_LATENT_AUROC_ERR_ROLE 4
+int64_t saev_latent_auroc_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t T, int64_t nnz);
+int saev_latent_auroc(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+                      const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32,
+                      const uint8_t* role, int64_t T,                             /* T x C */
+                      double* auroc, int64_t* u2, int64_t* n_pos, int64_t* n_neg, /* S x T, S x T, T, T */
+                      int64_t* fire_pos, int64_t* fire_neg, double* sum_pos, double* sum_neg, /* S x T each */
+                      int64_t* pos,                                               /* C */
+                      void* workspace, int64_t workspace_bytes, void* stream);
 /* SPARSE LINEAR (the training half of the concept audit, the reference's contrib/trait_discovery tdiscovery.classification:
  * aggregate_to_images and the LogisticRegression(penalty="l1") of train_worker_fn), context-free; DESIGN.md 3.20.
  *

@@ -126,6 +126,34 @@ def latent_ap_matrix(token_acts_csr, labels_flat: np.ndarray, *, ignore_label_id
     return res.ap.cpu().numpy(), classes, res.n_pos.cpu().numpy()
 
 
+def latent_auroc_matrix(token_acts_csr, labels_flat: np.ndarray, *, ignore_label_ids=(0,), ignored_as_negative: bool = False, device=None):
+    """(auroc_sc (d_sae, n_seg_classes) float64, classes (n_seg_classes) int64, n_pos_c (n_seg_classes) int64): the exact tie-aware
+    AUROC of EVERY latent against every segmentation class, one-vs-rest, over the columns of ``latent_ap_matrix`` -- threshold-free
+    and, unlike AP, independent of the class's prevalence (``engine.latent_auroc``).  A row with an ignored label is
+    left out of every task; with ``ignored_as_negative`` those rows form a class of their own that is negative in every task."""
+    labels_flat = np.ascontiguousarray(labels_flat)
+    if labels_flat.dtype != np.uint8 or labels_flat.ndim != 1:
+        raise ValueError(f"labels_flat must be a uint8 vector, got {labels_flat.dtype} {labels_flat.shape}.")
+    csr = scipy.sparse.csr_matrix(token_acts_csr)
+    if csr.shape[0] != labels_flat.shape[0]:
+        raise ValueError(f"token_acts_csr has {csr.shape[0]} rows, labels_flat {labels_flat.shape[0]}.")
+    classes, remap = _columns(labels_flat, tuple(ignore_label_ids))
+    n_tasks = len(classes)
+    if n_tasks == 0:
+        raise ValueError("every label is ignored: there is no class to score.")
+    n_classes = n_tasks
+    if ignored_as_negative and n_tasks < len(np.unique(labels_flat)):
+        remap[np.setdiff1d(np.unique(labels_flat), classes)] = n_tasks
+        n_classes = n_tasks + 1
+    roles = np.ones((n_tasks, n_classes), dtype=np.uint8)
+    roles[np.arange(n_tasks), np.arange(n_tasks)] = 2
+    dev = _device(device)
+    n, s = csr.shape
+    res = engine.latent_auroc(*_csr_on(csr, dev), n, s, n_classes, labels=torch.from_numpy(labels_flat).to(dev), remap=torch.from_numpy(remap).to(dev),
+                              roles=torch.from_numpy(roles).to(dev))
+    return res.auroc.cpu().numpy(), classes, res.n_pos.cpu().numpy()
+
+
 def extract_feature_ranking(classifier: object, cls_type: str) -> tuple[np.ndarray, np.ndarray]:
     """(ranked_indices by descending importance with a stable sort, importance_scores) of a trained classifier: the sum of |coef_|
     over classes for "sparse-linear", feature_importances_ for "decision-tree" (duck-typed)."""

@@ -30,6 +30,9 @@
 //            with the neighbours whose rounded score equals b.
 //   top rows a gather from row and starts.
 //
+// LATENT AUROC (include/saev_amd.h: LATENT AUROC) shares the sort too and walks lane = task; its kernels (au_*) carry
+// their own description further down.
+//
 // Integer atomics only (digit counts in LDS, class counts, the error word); nothing is read back, nothing synchronises.
 #include "entry_util.h"
 
@@ -543,6 +546,153 @@ __global__ __launch_bounds__(256) void pa_top_rows_kernel(const int64_t* __restr
     }
 }
 
+// ---------------------------------------------------------------- auroc ------------------------------------------------------------------
+
+// LATENT AUROC (include/saev_amd.h: LATENT AUROC) shares the sort as well and walks lane = task:
+//   roles    the T x C role matrix turned class-major: row c + 1 of the table holds class c's role in every task (row 0, zeros, is
+//            class -1), Tp = 64 ceil(T / 64) bytes a row, so that the 64 lanes of a wave read 64 consecutive bytes per event.
+//   counts   n_pos / n_neg of a task = the class counts la_open enqueues, summed over the classes of role 2 / 1.
+//   walk     a wave per (latent, 64 tasks).  The key and the row's class are the same in every lane; a lane keeps its task's p, q of
+//            the open group, P, the event counters, U2 and the two fp64 sums in registers.  A group closes when the key changes
+//            (for every lane at once).  The rows without an event enter in closed form behind the walk.  The role bytes of eight
+//            events are fetched before the eight are worked through, from a copy of the task group's (C + 1) x 64 slice in LDS
+//            when that is at most AU_LDS_MAX_BYTES, from the table (L2) otherwise.
+#ifndef AU_LDS_MAX_BYTES
+#define AU_LDS_MAX_BYTES 16384
+#endif
+constexpr int AU_MAX_T = 4096;
+constexpr int AU_BATCH = 8;
+
+static inline int64_t au_tp(int64_t T) { return (T + 63) / 64 * 64; }
+
+// grid: (Tp / 64, C + 1), 64 threads
+__global__ __launch_bounds__(64) void au_roles_kernel(const uint8_t* __restrict__ role, int C, int T, int Tp, uint8_t* __restrict__ table,
+                                                      int32_t* __restrict__ err) {
+    const int t = blockIdx.x * 64 + threadIdx.x, r = blockIdx.y;  // (t < Tp, r <= C)
+    uint8_t v = 0;
+    if (r > 0 && t < T) {
+        v = role[(size_t)t * C + (r - 1)];
+        if (v > 2) { atomicMax(err, SAEV_LATENT_AUROC_ERR_ROLE); v = 0; }
+    }
+    table[(size_t)r * Tp + t] = v;
+}
+
+// a thread per task.  grid: ceil(T / 256)
+__global__ __launch_bounds__(256) void au_counts_kernel(const uint8_t* __restrict__ table, const unsigned long long* __restrict__ pos, int C, int T,
+                                                        int Tp, long long* __restrict__ n_pos, long long* __restrict__ n_neg) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    long long np = 0, nn = 0;
+    for (int c = 0; c < C; ++c) {
+        const int r = table[(size_t)(c + 1) * Tp + t];
+        const long long n = (long long)pos[c];
+        np += r == 2 ? n : 0;
+        nn += r == 1 ? n : 0;
+    }
+    n_pos[t] = np;
+    n_neg[t] = nn;
+}
+
+struct AuWalk {
+    const int64_t* starts;
+    const uint32_t* key;
+    const int32_t* row;
+    const uint8_t* u8;
+    const int32_t* remap;
+    const int32_t* i32;
+    const uint8_t* table;
+    const long long* n_pos;
+    const long long* n_neg;
+    double* auroc;
+    long long* u2;
+    long long* fire_pos;
+    long long* fire_neg;
+    double* sum_pos;
+    double* sum_neg;
+    int N, S, C, T, Tp;
+};
+
+// a wave per (latent, 64 tasks), lane = task.  grid: (ceil(S / 4), Tp / 64); LDS: (C + 1) x 64 bytes of dynamic LDS
+template <bool LDS>
+__global__ __launch_bounds__(256) void au_walk_kernel(AuWalk a) {
+#pragma clang fp contract(off)
+    extern __shared__ uint8_t au_slice[];
+    const int lane = threadIdx.x & 63;
+    const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int t = blockIdx.y * 64 + lane;  // (< Tp)
+    if (LDS) {  // the four waves share the task group: its slice of the table, a 64-byte row as 16 words
+        const int words = (a.C + 1) * 16;
+        for (int w = threadIdx.x; w < words; w += 256)
+            reinterpret_cast<uint32_t*>(au_slice)[w] =
+                *reinterpret_cast<const uint32_t*>(a.table + (size_t)(w >> 4) * a.Tp + (size_t)blockIdx.y * 64 + (size_t)(w & 15) * 4);
+        __syncthreads();
+    }
+    if (j >= a.S) return;
+    const bool active = t < a.T;
+    const uint8_t* mine = LDS ? au_slice + lane : a.table + t;  // + (class + 1) * stride: this lane's role of a class
+    const size_t stride = LDS ? 64 : (size_t)a.Tp;
+    const int64_t s0 = a.starts[j], s1 = a.starts[j + 1];
+
+    long long p = 0, q = 0, P = 0, Qev = 0, Ppos = 0, Qneg = 0, U2 = 0;
+    double sp = 0.0, sn = 0.0;
+    uint32_t curk = 0;
+    bool open = false;
+    for (int64_t base = s0; base < s1; base += 64) {
+        const int64_t e = base + lane;
+        uint32_t myk = 0;
+        int mycl = -1;
+        if (e < s1) { myk = a.key[e]; mycl = la_class(a.u8, a.remap, a.i32, a.row[e], a.C); }
+        const int cnt = (int)min((int64_t)64, s1 - base);
+        for (int i0 = 0; i0 < cnt; i0 += AU_BATCH) {
+            uint32_t ks[AU_BATCH];
+            int rs[AU_BATCH];
+#pragma unroll
+            for (int u = 0; u < AU_BATCH; ++u) {  // (behind cnt: class -1, the table's row of zeros)
+                ks[u] = __shfl(myk, i0 + u, 64);
+                rs[u] = mine[(size_t)(__shfl(mycl, i0 + u, 64) + 1) * stride];
+            }
+#pragma unroll
+            for (int u = 0; u < AU_BATCH; ++u) {
+                if (i0 + u < cnt) {
+                    const uint32_t k = ks[u];
+                    if (open && k != curk) {  // the group is closed, for every lane
+                        U2 += q * (2 * P + p);
+                        P += p;
+                        p = 0;
+                        q = 0;
+                    }
+                    curk = k;
+                    open = true;
+                    const float v = ukey2f(~k);
+                    const double dv = (double)v;
+                    const long long isp = rs[u] == 2 ? 1 : 0, isn = rs[u] == 1 ? 1 : 0;
+                    p += isp;
+                    q += isn;
+                    Qev += isn;
+                    if (v > 0.f) Ppos += isp; else Qneg += isn;
+                    if (isp) sp = sp + dv;
+                    if (isn) sn = sn + dv;
+                }
+            }
+        }
+    }
+    if (open) {
+        U2 += q * (2 * P + p);
+        P += p;
+    }
+    if (!active) return;
+    const long long np = a.n_pos[t], nn = a.n_neg[t];
+    const long long p0 = np - P, q0 = nn - Qev;  // the rows without an event: one group between the positive and the negative values
+    U2 += 2 * q0 * Ppos + p0 * q0 + 2 * p0 * Qneg;
+    const size_t at = (size_t)j * a.T + t;
+    a.u2[at] = U2;
+    a.auroc[at] = (np > 0 && nn > 0) ? (double)U2 / ((2.0 * (double)np) * (double)nn) : __longlong_as_double(0x7ff8000000000000LL);
+    a.fire_pos[at] = Ppos;
+    a.fire_neg[at] = Qev - Qneg;
+    a.sum_pos[at] = sp;
+    a.sum_neg[at] = sn;
+}
+
 // ---------------------------------------------------------------- host -------------------------------------------------------------------
 
 // what la_open leaves for the rest of an entry
@@ -641,6 +791,48 @@ int saev_probe_ap(const int64_t* row_ptr, const int32_t* indices, const float* d
     if (top_k > 0)
         hipLaunchKernelGGL(pa_top_rows_kernel, dim3((unsigned)std::min<int64_t>((S * (int64_t)top_k + 255) / 256, 8192)), dim3(256), 0, s, e.starts,
                            e.row, (long)S, (int)top_k, reinterpret_cast<long long*>(top_row));
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");
+    return SAEV_OK;
+}
+
+int64_t saev_latent_auroc_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t T, int64_t nnz) {
+    if (!entry_shape_ok(N, S, C, nnz) || T < 1 || T > AU_MAX_T) return -1;
+    saev_latent_ap_layout L;
+    la_layout(S, C, nnz, &L);
+    return L.total_bytes + round256((C + 1) * au_tp(T));
+}
+
+int saev_latent_auroc(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+                      const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, const uint8_t* role, int64_t T, double* auroc,
+                      int64_t* u2, int64_t* n_pos, int64_t* n_neg, int64_t* fire_pos, int64_t* fire_neg, double* sum_pos, double* sum_neg,
+                      int64_t* pos, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* who = "saev_latent_auroc";
+    if (const int rc = entry_check_shape(who, N, S, C, nnz)) return rc;
+    if (T < 1 || T > AU_MAX_T) return entry_refuse(SAEV_UNSUPPORTED, who, "the number of tasks must lie in [1, 4096]");
+    // this entry's workspace is longer than la_open's: its size is checked where la_open checks its own, behind the entry's arguments
+    const int64_t need = saev_latent_auroc_workspace_bytes(N, S, C, T, nnz);
+    const char* own = !role ? "role must not be NULL"
+        : (!auroc || !u2 || !n_pos || !n_neg || !fire_pos || !fire_neg || !sum_pos || !sum_neg || !pos)
+            ? "auroc, u2, n_pos, n_neg, fire_pos, fire_neg, sum_pos, sum_neg and pos must not be NULL"
+        : (!workspace || workspace_bytes < need) ? "workspace smaller than saev_latent_auroc_workspace_bytes(N, S, C, T, nnz)"
+        : nullptr;
+    LaOpen o;
+    if (const int rc = la_open(who, row_ptr, indices, data, nnz, N, S, C, class_u8, remap, class_i32, pos, own, workspace, workspace_bytes, stream, &o))
+        return rc;
+    hipStream_t s = o.s;
+    const int Tp = (int)au_tp(T);
+    uint8_t* table = o.ws + o.L.total_bytes;
+    long long* np = reinterpret_cast<long long*>(n_pos);
+    long long* nn = reinterpret_cast<long long*>(n_neg);
+    hipLaunchKernelGGL(au_roles_kernel, dim3((unsigned)(Tp / 64), (unsigned)(C + 1)), dim3(64), 0, s, role, (int)C, (int)T, Tp, table, o.err);
+    hipLaunchKernelGGL(au_counts_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, table, o.pos, (int)C, (int)T, Tp, np, nn);
+    const LaSorted e = la_sort(o.L, o.ws, row_ptr, indices, data, nnz, N, S, s);
+    AuWalk a{e.starts, e.key, e.row, class_u8, remap, class_i32, table, np, nn, auroc, reinterpret_cast<long long*>(u2),
+             reinterpret_cast<long long*>(fire_pos), reinterpret_cast<long long*>(fire_neg), sum_pos, sum_neg, (int)N, (int)S, (int)C, (int)T, Tp};
+    const dim3 grid((unsigned)((S + 3) / 4), (unsigned)(Tp / 64));
+    const size_t slice = (size_t)(C + 1) * 64;
+    if (slice <= (size_t)AU_LDS_MAX_BYTES) hipLaunchKernelGGL(au_walk_kernel<true>, grid, dim3(256), slice, s, a);
+    else hipLaunchKernelGGL(au_walk_kernel<false>, grid, dim3(256), 0, s, a);
     if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");
     return SAEV_OK;
 }

@@ -899,9 +899,10 @@ class LatentAPResult(_APResult):
     best_class = property(lambda self: self._read("best_class"))
 
 
-def _ap_open(who: str, indptr, indices, data, n_rows: int, n_latents: int, n_classes: int, labels, remap, nnz, top_k: int = 0):
-    """What ``latent_ap`` and ``probe_ap`` do before their C entry: the size checks, the nnz rule, the CSR triple and the labels on the
-    device, the layout and a workspace of its size.  Returns (lib, device, nnz, the ten leading arguments of either entry, ws, layout)."""
+def _ap_open(who: str, indptr, indices, data, n_rows: int, n_latents: int, n_classes: int, labels, remap, nnz, top_k: int = 0, n_tasks: int | None = None):
+    """What ``latent_ap``, ``probe_ap`` and ``latent_auroc`` do before their C entry: the size checks, the nnz rule, the CSR triple and
+    the labels on the device, the layout and a workspace of its size (with ``n_tasks``: of ``latent_auroc``'s size, which begins with
+    that layout).  Returns (lib, device, nnz, the ten leading arguments of either entry, ws, layout)."""
     for name, v, hi in (("n_rows", n_rows, 2**31), ("n_latents", n_latents, 2**31), ("n_classes", n_classes, 4097)):
         if not 1 <= v < hi:
             raise ValueError(f"{who}: unsupported {name} {v} (1 <= {name} < {hi})")
@@ -917,7 +918,8 @@ def _ap_open(who: str, indptr, indices, data, n_rows: int, n_latents: int, n_cla
     lib = _lib.load()
     layout = _lib.SaevLatentAPLayout()
     _lib.check(lib, None, lib.saev_latent_ap_layout_of(n_rows, n_latents, n_classes, nnz, C.byref(layout)), "saev_latent_ap_layout_of")
-    ws = torch.empty(layout.total_bytes, device=device, dtype=torch.uint8)
+    total = layout.total_bytes if n_tasks is None else lib.saev_latent_auroc_workspace_bytes(n_rows, n_latents, n_classes, n_tasks, nnz)
+    ws = torch.empty(total, device=device, dtype=torch.uint8)
     return lib, device, nnz, csr, classes, ws, layout
 
 
@@ -983,6 +985,54 @@ def probe_ap(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_
                                _ptr(out["n_pred_pos"]), top_k, _ptr(out["top_rows"]), _ptr(ws), ws.numel(), _stream())
     _lib.check(lib, None, rc, "saev_probe_ap")
     return ProbeAPResult(out, ws, layout, (n_rows, n_latents, n_classes, nnz))
+
+
+class LatentAUROCResult(_APResult):
+    """What ``latent_auroc`` leaves on the device: ``auroc`` (S, T) float64 (NaN for a task without positives or without negatives),
+    ``u2`` (S, T) int64 (twice the Mann-Whitney U: 2 x pairs ranked right + tied pairs), ``n_pos`` and ``n_neg`` (T) int64,
+    ``fire_pos`` and ``fire_neg`` (S, T) int64 (included rows of the role with activation > 0), ``sum_pos`` and ``sum_neg`` (S, T)
+    float64 (the role's activations summed) and ``class_counts`` (C) int64.  The call itself does not synchronise; the first read of
+    a result -- or ``check()`` -- reads the device's error word (one synchronisation) and raises ValueError if it is not 0.
+    ``layout`` is the leading part of the workspace, as of ``latent_ap`` (include/saev_amd.h: LATENT AUROC)."""
+
+    _WHO = "latent_auroc"
+    _ERRORS = {**LatentAPResult._ERRORS, 4: "a role byte is above 2"}
+
+    auroc = property(lambda self: self._read("auroc"))
+    u2 = property(lambda self: self._read("u2"))
+    n_pos = property(lambda self: self._read("n_pos"))
+    n_neg = property(lambda self: self._read("n_neg"))
+    fire_pos = property(lambda self: self._read("fire_pos"))
+    fire_neg = property(lambda self: self._read("fire_neg"))
+    sum_pos = property(lambda self: self._read("sum_pos"))
+    sum_neg = property(lambda self: self._read("sum_neg"))
+    class_counts = property(lambda self: self._read("class_counts"))
+
+
+def latent_auroc(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_rows: int, n_latents: int, n_classes: int, *,
+                 labels: torch.Tensor, remap: torch.Tensor | None = None, roles: torch.Tensor, nnz: int | None = None) -> LatentAUROCResult:
+    """Exact tie-aware AUROC of every latent on every binary task, with the per-role supports and activation sums
+    (include/saev_amd.h: LATENT AUROC).  x, ``labels``, ``remap`` and ``nnz`` as for ``latent_ap``; ``roles`` (T, C)
+    uint8 on the device: 0 leaves the rows of class c out of task t, 1 makes them its negatives, 2 its positives; 1 <= T <= 4096.
+    One call, one workspace, no synchronisation; there is no CPU path."""
+    if roles.dim() != 2 or roles.dtype != torch.uint8:
+        raise ValueError(f"latent_auroc: roles must be a (n_tasks, n_classes) uint8 matrix, got {roles.dtype} {tuple(roles.shape)}")
+    n_tasks = roles.shape[0]
+    if not 1 <= n_tasks <= 4096:
+        raise ValueError(f"latent_auroc: unsupported n_tasks {n_tasks} (1 <= n_tasks <= 4096)")
+    lib, device, nnz, csr, classes, ws, layout = _ap_open("latent_auroc", indptr, indices, data, n_rows, n_latents, n_classes, labels, remap, nnz,
+                                                          n_tasks=n_tasks)
+    roles = _on(roles, torch.uint8, (n_tasks, n_classes), "roles", device)
+    pairs, tasks = (n_latents, n_tasks), (n_tasks,)
+    i64, f64 = dict(device=device, dtype=torch.int64), dict(device=device, dtype=torch.float64)
+    out = dict(auroc=torch.empty(pairs, **f64), u2=torch.empty(pairs, **i64), n_pos=torch.empty(tasks, **i64), n_neg=torch.empty(tasks, **i64),
+               fire_pos=torch.empty(pairs, **i64), fire_neg=torch.empty(pairs, **i64), sum_pos=torch.empty(pairs, **f64),
+               sum_neg=torch.empty(pairs, **f64), class_counts=torch.empty(n_classes, **i64))
+    with torch.cuda.device(device):
+        rc = lib.saev_latent_auroc(*map(_ptr, csr), nnz, n_rows, n_latents, n_classes, *map(_ptr, classes), _ptr(roles), n_tasks,
+                                   *map(_ptr, out.values()), _ptr(ws), ws.numel(), _stream())
+    _lib.check(lib, None, rc, "saev_latent_auroc")
+    return LatentAUROCResult(out, ws, layout, (n_rows, n_latents, n_classes, nnz))
 
 
 class PoolResult(_Checked):
