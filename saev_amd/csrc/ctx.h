@@ -255,7 +255,7 @@ struct saev_ctx {
     double rt_l1 = 0.0;               // the L1 coefficient (objectives.py: sparsity = coeff * l1)
     float* rt_dA = nullptr;           // (max_batch x d_sae) g W_dec^T, then dH in place
     float *rt_parts = nullptr, *rt_colpart = nullptr;  // per-workgroup maxima; column sums of dH per block of rows
-    float* rt_scales = nullptr;       // operand scales {2^e, 1}: [0] f, [2] g, [4] dH, [6] x
+    float* rt_scales = nullptr;       // operand scales {2^e, 1}: [0] f, [2] g, [4] dH, [6] x; saev_encode_dense (f16x3): [8] max |x|, [10] its pair
     int rt_Sp = 0, rt_kpad = 0;       // d_sae rounded up to 32; the batch axis padded for the split-K weight gradients
     _Float16 *rt_xsF = nullptr, *rt_xsG = nullptr;    // row-operand images of f (k = d_sae) and of g (k = d_model)
     _Float16 *rt_wsR = nullptr, *rt_wsK = nullptr;    // W_dec as "encoder" of dA (rows = latents) and of x_hat (rows = d_model columns)

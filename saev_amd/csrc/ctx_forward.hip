@@ -113,8 +113,20 @@ static int prepare_encoder(saev_ctx* c, const float* x, int n, int32_t* pre_flag
     return SAEV_OK;
 }
 
+// The f16x3 images of a ReLU TRAINING context's dense h: x times the power of two that puts max |x| (absmax_dev, on the device)
+// into [2^13, 2^14), written to pair = {2^e, 1} for the encoder to undo.  The other contexts' f16x3 images carry no
+// data-dependent scale (|x| < 65 504, and small x loses the low half to fp16's subnormals); the dense step's mask is
+// a comparison of h with zero and must hold at any activation scale, as its other four contractions do (rt_scales).
+static int prepare_dense_scaled(saev_ctx* c, const float* x, int n, const float* absmax_dev, float* pair, hipStream_t s) {
+    HIPCHK(c, launch_pow2_scale(absmax_dev, pair, s));
+    HIPCHK(c, launch_split_rows(x, n, c->cfg.d_model, c->Dp, c->xs, 0, s, 1.0f, pair));
+    { int rcw = wait_wenc(c, s); if (rcw != SAEV_OK) return rcw; }
+    HIPCHK(c, launch_split_wT(c->params + c->off_W_enc, c->cfg.d_model, c->cfg.d_sae, c->S_pad, c->Dp, 256.0f, c->ws, 0, s));
+    return SAEV_OK;
+}
+
 static int run_encoder(saev_ctx* c, const float* x, int n, int epi, float* h_out, const int32_t* flag, int when,
-                       hipStream_t s, bool predicted = false) {
+                       hipStream_t s, bool predicted = false, const float* x_scale = nullptr) {
     // F16R: only the TopK pass is approximate-then-refined; a dense h must be exact, so it comes from the fp32 kernel
     const bool f16r = c->cfg.encoder_mode == SAEV_ENCODER_F16R;
     if (c->cfg.encoder_mode != SAEV_ENCODER_F32 && !(f16r && epi == EPI_DENSE)) {
@@ -123,7 +135,7 @@ static int run_encoder(saev_ctx* c, const float* x, int n, int epi, float* h_out
         a.xs = c->xs_c; a.ws = c->ws;
         a.b_enc = f16r ? c->b_shift : c->params + c->off_b_enc;  // f16r: images are centred, the bias carries mu W
         a.n_rows = n; a.Dp = c->Dp; a.S = c->cfg.d_sae; a.w_scale = (bf || f16r) ? 1.0f : 256.0f;
-        a.scale_dev = f16r ? scl(c) : nullptr;
+        a.scale_dev = f16r ? scl(c) : x_scale;  // (x_scale: prepare_dense_scaled's pair, f16x3 only)
         a.arith = bf ? 1 : (f16r ? 2 : 0);
         a.row_margin = f16r ? c->row_margin : nullptr;
         a.s_splits = encoder_splits(n, a.S, encode_f16x3_tile_rows(), encode_f16x3_tile_latents(), 256);  // (one workgroup per CU)
@@ -170,6 +182,16 @@ int saev_encode_dense(saev_ctx* c, const float* x, int32_t n, float* h_out, void
             "saev_encode_dense: n_rows > max_batch");
     bind_x_sources(c, x, n, false);
     c->xprep_x = nullptr;  // the images below are rebuilt for this call: nothing to lend
+    if (c->relu_train && c->cfg.encoder_mode == SAEV_ENCODER_F16X3) {
+        // the step's own h, bit for bit: the same scaled images from this x's own maximum (in words of rt_scales the step does not
+        // use: a step between its forward and its backward keeps its `upper` and its scales)
+        hipStream_t s = (hipStream_t)stream;
+        HIPCHK(c, hipMemsetAsync(c->rt_scales + 8, 0, sizeof(float), s));
+        HIPCHK(c, launch_absmax(x, (long)n * c->cfg.d_model, c->rt_scales + 8, s));
+        int rc = prepare_dense_scaled(c, x, n, c->rt_scales + 8, c->rt_scales + 10, s);
+        if (rc != SAEV_OK) return rc;
+        return run_encoder(c, x, n, EPI_DENSE, h_out, nullptr, 0, s, false, c->rt_scales + 10);
+    }
     if (c->cfg.encoder_mode != SAEV_ENCODER_F16R) {  // (f16r: a dense h comes from the fp32 kernel, no images needed)
         int rc = prepare_encoder(c, x, n, nullptr, (hipStream_t)stream);
         if (rc != SAEV_OK) return rc;
@@ -415,6 +437,12 @@ int btk_codes(saev_ctx* c, const float* h, int n, int training, int32_t* row_nnz
 
 // h = x W_enc + b_enc into the context's dense buffer: the exact fp32 kernel in the f32 and f16r modes, the split-fp16 one in f16x3
 int encode_dense_h(saev_ctx* c, const float* x, int n, hipStream_t s) {
+    if (c->relu_train && c->cfg.encoder_mode == SAEV_ENCODER_F16X3) {
+        // (relu_train_forward has left max |x| in `upper`; the pair is the one its backward forms again for x's k-major images)
+        int rc = prepare_dense_scaled(c, x, n, c->upper, c->rt_scales + 6, s);
+        if (rc != SAEV_OK) return rc;
+        return run_encoder(c, x, n, EPI_DENSE, c->h_dense, nullptr, 0, s, false, c->rt_scales + 6);
+    }
     if (c->cfg.encoder_mode != SAEV_ENCODER_F16R) {
         int rc = prepare_encoder(c, x, n, nullptr, s);
         if (rc != SAEV_OK) return rc;

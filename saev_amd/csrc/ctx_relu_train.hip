@@ -15,7 +15,7 @@ int relu_train_alloc(saev_ctx* c) {
     A(rt_dA, MB * S);
     A(rt_parts, std::max(relu_act_parts((int)MB), relu_dact_parts((int)MB, (int)S)));
     A(rt_colpart, (size_t)relu_dact_row_blocks((int)MB) * S);
-    A(rt_scales, 8);
+    A(rt_scales, 12);
     A(rt_xsF, (size_t)c->MB_pad * 2 * c->rt_Sp); A(rt_xsG, (size_t)c->MB_pad * 2 * c->Dp);
     A(rt_wsR, S256 * 2 * c->Dp); A(rt_wsK, D256 * 2 * c->rt_Sp);
     A(rt_kF, S256 * 2 * Kp); A(rt_kG, D256 * 2 * Kp); A(rt_kX, D256 * 2 * Kp);

@@ -64,7 +64,9 @@ class ReluRow:
 # padding of the batch axis in the split-K weight gradients (ksplit_shape: R x C tiles x n_split >= 256 or n_split = 16), the 64-row
 # blocks of relu_dact_kernel's column sums, its 1024-column workgroups, one wave per row in relu_act_kernel / relu_mse_kernel.
 # Sizes are the smallest that reach the class.  n_split is 16 in every row (tiles <= 15 at these sizes; it is 1 from 256 tiles on:
-# tests/test_gpu_relu_train.py::test_one_split_of_the_weight_gradients reaches that); Kp is PADDED wherever n % 256 != 0: all rows.
+# tests/test_gpu_relu_train.py::test_one_split_of_the_weight_gradients reaches that); Kp is PADDED wherever n % 256 != 0: all rows but
+# the last two.  (A batch SMALLER than the context's max_batch, whose k-major images are laid out for Kp(max_batch):
+# tests/test_gpu_relu_train.py::test_a_smaller_batch_after_a_full_one_on_the_same_context.)
 RELU_SHAPES = (
     # one row, K = n = 1 in the split-K batches (Kp = 256: 255 rows of padding), a single partial tile of everything
     ReluRow(1, 20, 36, seed=0),
@@ -80,6 +82,10 @@ RELU_SHAPES = (
     ReluRow(70, 1280, 516, seed=3),
     # the largest ragged width (Dp = 4096)
     ReluRow(34, 4092, 260, seed=0),
+    # Kp = n = 256: no padding of the batch axis, one whole row tile, four whole column-sum blocks
+    ReluRow(256, 36, 260, seed=3),
+    # two whole row tiles, Kp = n = 512; everything else a single partial tile
+    ReluRow(512, 20, 36, seed=0),
 )
 
 

@@ -203,6 +203,22 @@ def test_one_split_of_the_weight_gradients(encoder_mode):
     _step_and_check(eng, f"{n}x{d}x{s}", x.cuda(), BOUND, strict_mask=False)
 
 
+def test_a_smaller_batch_after_a_full_one_on_the_same_context(encoder_mode):
+    """The ragged last batch of train() / evaluate(): the context lays its k-major operand images out for Kp(max_batch) = 512 and
+    a step of n rows uses Kp(n) = 256 of it (n = 65, n = 1), over whatever the full batch before left there; then a full batch
+    again.  Every step against the restatement, a tail between them."""
+    from test_gpu_parity import rand_params
+
+    d, s, mb = 100, 1004, 300
+    eng = rt_engine(d, s, mb, l1=L1_COEFF)
+    eng.load_params(rand_params(d, s, seed=12))
+    for i, n in enumerate((300, 65, 1, 300)):
+        if i:
+            eng.step_tail(1e-3, 1.0)
+        x = torch.randn(n, d, generator=torch.Generator().manual_seed(40 + i))
+        _step_and_check(eng, f"max_batch {mb}, step {i} of {n} rows", x.cuda(), BOUND, strict_mask=False)
+
+
 def test_the_same_step_twice_gives_the_same_bits(encoder_mode):
     row = RELU_SHAPES[2]
     p, x = relu_row_inputs(row)
