@@ -153,11 +153,12 @@ def row_inputs(row: Row):
     return p, x, toks
 
 
-def input_conditions(row: Row, W_enc, b_enc, x, toks):
+def input_conditions(row: Row, W_enc, b_enc, x, toks, thr=DEAD_THR):
     """Asserts what makes the fp32 and the fp64 selections of a row's inputs the same sets: on every batch row the fp64 k-th and
     (k+1)-th pre-activation lie more than 2 tol_b apart (tol_b of tests/topk_exactness.py: two fp32 evaluations differ by at most
     that), no dead latent is among the k, and for n_dead > k_aux the same gap separates the k_aux-th and (k_aux+1)-th DEAD
-    pre-activation.  Returns (mask of the fp64 top-k as bool, dead mask, smallest gap / tol_b of either kind)."""
+    pre-activation.  `thr`: the dead threshold the tracker `toks` is read against (tests/auxk_bound_cases.py has its own).
+    Returns (mask of the fp64 top-k as bool, dead mask, smallest gap / tol_b of either kind)."""
     h = x.double() @ W_enc.double() + b_enc.double()
     tol = 8.0 * 2.0 ** -24 * x.double().norm(dim=1) * W_enc.double().norm(dim=0).max()
     k = min(row.k, row.s)
@@ -168,7 +169,7 @@ def input_conditions(row: Row, W_enc, b_enc, x, toks):
         worst[0] = gap.min().item()
         assert worst[0] > 2.0, f"{row.id}: batch row {int(gap.argmin())}: the k-th and (k+1)-th pre-activation are {worst[0]:.2f} tol_b apart"
     mask = torch.zeros(row.n, row.s, dtype=torch.bool).scatter_(1, h.topk(k, dim=1).indices, True)
-    dead = toks >= DEAD_THR
+    dead = toks >= thr
     assert int(dead.sum()) == row.n_dead
     assert not mask[:, dead].any(), f"{row.id}: a dead latent is among the top-k"
     if row.n_dead > row.k_aux:
