@@ -4,7 +4,8 @@ shapes -- one row per dispatch class of d_model, d_sae and top_k ("Pa
 
 The restatement is teacher-forced: f = h * mask with the mask taken from the codes the step itself selected, so a pre-activation
 pair closer than fp32 can tell apart never decides the comparison.  The AuxK selection inside it is the reference's own top-k over
-the dead pre-activations; `input_conditions` asserts that fp32 and fp64 cannot disagree on either selection for a row's inputs."""
+the dead pre-activations; `input_conditions` asserts that fp32 and fp64 cannot disagree on either selection for a row's inputs.
+The bf16 encoder's step is the same restatement with `bf16_codes=True` (tests/test_gpu_bf16_geometry.py, tests/bf16_cases.py)."""
 
 import dataclasses
 
@@ -19,9 +20,13 @@ BOUND = 2e-5        # of each tensor's largest element (tests/test_gpu_dw_slices
 MAX_PREFIXES = 16
 
 
-def restated_gradients(params, x, mask, dead_mask, prefixes, k_aux, alpha, dtype=torch.float64):
+def restated_gradients(params, x, mask, dead_mask, prefixes, k_aux, alpha, dtype=torch.float64, *, bf16_codes=False):
     """loss = mean over prefixes of the rescaled MSE + AuxK, with f = h * mask (df/dh = the mask; a threshold has no gradient), in
-    ``dtype``.  Returns (mse, aux, {name: gradient})."""
+    ``dtype``.  Returns (mse, aux, {name: gradient}).
+
+    ``bf16_codes``: the bf16 encoder (oracle/sae_ref.py: encode_pre_bf16).  The VALUE of the h that enters f is the product of the
+    bf16-rounded x and W_enc (round to nearest even) plus b_enc, evaluated in ``dtype``; its gradient stays that of the unrounded
+    formula, and the AuxK term keeps the unrounded h."""
     leaves = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in params.items()}
     x = x.to(dtype)
     if dead_mask is None:
@@ -29,7 +34,13 @@ def restated_gradients(params, x, mask, dead_mask, prefixes, k_aux, alpha, dtype
     if prefixes is not None and not torch.is_tensor(prefixes):
         prefixes = torch.tensor([int(p) for p in prefixes], dtype=torch.int64)
     h = x @ leaves["W_enc"] + leaves["b_enc"]
-    f = h * mask.to(dtype)
+    h_codes = h
+    if bf16_codes:
+        with torch.no_grad():
+            h_bf = params["W_enc"].detach().to(torch.bfloat16).to(dtype)
+            h_bf = x.to(torch.bfloat16).to(dtype) @ h_bf + leaves["b_enc"]
+        h_codes = h + (h_bf - h).detach()
+    f = h_codes * mask.to(dtype)
     x_hats = R.decode(f, leaves["W_dec"], leaves["b_dec"], prefixes)
     P = x_hats.shape[1]
     mse = R.mean_squared_err(x_hats, x[:, None, :].expand(-1, P, -1)).mean()

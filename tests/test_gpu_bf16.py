@@ -2,7 +2,12 @@
 
 Tolerances: against the oracle evaluated with the same bf16-rounded encoder operands the
 HIP path is held to the fp32 bands of test_gpu_parity.py; against the fp32 oracle the reconstruction MSE must
-agree to 1e-2 relative."""
+agree to 1e-2 relative.
+
+The shapes here are few and friendly (top_k in {8 .. 64}, d_sae a multiple of 512 on the fused route).  Every dispatch class of
+d_model, d_sae and top_k, the dense route (top_k > 64, list overflow), predicted bounds, the hand-over of the images the fused
+Adam leaves and the late tile checksums are in tests/test_gpu_bf16_geometry.py, held to tol_b of tests/topk_exactness.py against
+the product of the rounded operands, and the gradients to the bound of tests/step_restatement.py."""
 
 import math
 
