@@ -723,6 +723,75 @@ int saev_latent_topk_update(const int32_t* idx, const float* val, const int32_t*
                             const int32_t* indices, const float* data, int64_t nnz, const uint8_t* keep, int64_t n, int64_t S,
                             int64_t row_base, const saev_latent_topk_state* state, void* workspace, int64_t workspace_bytes,
                             void* stream);
+/* LATENT EDITS (the intervention of the reference's contrib/interactive_interp/semseg: set a latent, decode, add the SAE's error
+ * back), context-free.  For an SAE x_hat = b_dec + sum_j f_j W_dec[j, :] and edits e = (latent l_e, target t_e(f)),
+ *   x' = (x - x_hat) + x_hat_mod = x + sum_e c_e W_dec[l_e, :],   c_e = t_e(f_l) - f_l
+ * b_dec and every unedited latent cancel: one pass over x, a few W_dec rows, no n x S matrix and no decode.
+ * AN EDIT is 16 bytes.  op is SAEV_EDIT_SET (t = value), SAEV_EDIT_SCALE (t = value f) or SAEV_EDIT_ADD (t = f + value), optionally
+ * | SAEV_EDIT_IF_ACTIVE (the edit applies only where f != 0).  group is -1 (the GLOBAL list: every row) or g in [0, n_groups) (the
+ * list of group g: rows with row_group[b] == g).  Edits do not compose: each reads the ORIGINAL f.
+ * saev_edit_plan_build validates on the host, in this order, before the device is touched: (1) sizes -- negative sizes and S outside
+ * [1, 2^31) are SAEV_INVALID_ARG, n_edits or n_groups above 65 536 SAEV_UNSUPPORTED, edits NULL with n_edits > 0 SAEV_INVALID_ARG;
+ * (2) every latent in [0, S); (3) every op known; (4) every group in [-1, n_groups) (SAEV_INVALID_ARG each); (5) at most 256 edits
+ * in the global list and in each group's list (SAEV_UNSUPPORTED); (6) no latent twice in one list, none in both the global list and
+ * a group's list (SAEV_INVALID_ARG); then (7) plan NULL with plan_bytes == 0 VALIDATES ONLY (SAEV_OK, no device needed), any other plan NULL, smaller than saev_edit_plan_bytes(n_edits, n_groups) (-1: unsupported
+ * sizes) or not 256-byte aligned (SAEV_INVALID_ARG).  It writes the edits grouped into the device plan -- the global list, then each
+ * group's list, a CSR over the lists; inside a list the caller's order is kept -- and WAITS for `stream` (the host images are its
+ * own).  A plan serves any number of saev_intervene_rows calls with the same n_edits and n_groups and an S no smaller.
+ * saev_intervene_rows takes x (n_rows x D fp32), W_dec (S x D fp32 row-major) and the codes as padded rows (as saev_decode_rows):
+ * row b's entries in its first min(row_nnz[b], row_cap) slots of idx / val (n_rows x row_cap); row_nnz NULL = every row has
+ * row_cap entries (the TopK form); a negative count reads as 0.  For each row b:
+ *   1. f_l is the value of the FIRST slot whose idx equals l, or 0 when there is none.
+ *   2. the applicable edits are the global list, then the list of group row_group[b] (row_group NULL, or a value outside
+ *      [0, n_groups): no group list).  A row with row_keep[b] == 0 (row_keep may be NULL) has none at all.
+ *   3. c_e in fp32 from the original f: value - f (SET), fmaf(value, f, -f) (SCALE), value (ADD).  An edit with c_e == 0, or
+ *      IF_ACTIVE with f == 0, is SKIPPED: it loads no W_dec row (an Inf or NaN there does not reach the output).
+ *   4. out[b, d] = x[b, d], then one fmaf(c_e, W_dec[l_e, d], .) per remaining edit in list order.  Columns are independent.
+ *   5. a row without a remaining edit gets out[b, :] = x[b, :] BIT FOR BIT.
+ * out == x (in place) is allowed; out overlapping x in any other way, or W_dec, idx or val, is SAEV_INVALID_ARG.  rows_changed (int64
+ * per edit in the CALLER's index, may be NULL) is ADDED the number of rows where the edit's c_e was applied: integer atomics,
+ * summed per workgroup first.  No floating-point atomic: two calls give the same bits, and in place gives the bits of out of place.
+ * Any D >= 1: 16-byte vector accesses when D % 4 == 0 and x, out and W_dec are 16-byte aligned, scalar ones otherwise (the same
+ * values).  n_rows, D, S, row_cap < 2^31 (SAEV_UNSUPPORTED); n_rows = 0 returns SAEV_OK; n_edits = 0 copies x (plan may be NULL).
+ * Nothing is allocated, nothing read back, nothing synchronises. */
+#define SAEV_EDIT_SET 0
+#define SAEV_EDIT_SCALE 1
+#define SAEV_EDIT_ADD 2
+#define SAEV_EDIT_IF_ACTIVE 4
+typedef struct {
+    int32_t latent;
+    int32_t op;
+    float value;
+    int32_t group;
+} saev_edit;
+int64_t saev_edit_plan_bytes(int64_t n_edits, int64_t n_groups);
+int saev_edit_plan_build(const saev_edit* edits_host, int64_t n_edits, int64_t n_groups, int64_t S, void* plan_dev, int64_t plan_bytes,
+                         void* stream);
+int saev_intervene_rows(const float* x, int64_t n_rows, int64_t D, const float* W_dec, int64_t S, const int32_t* idx, const float* val,
+                        const int32_t* row_nnz, int64_t row_cap, const void* plan_dev, int64_t n_edits, int64_t n_groups,
+                        const int32_t* row_group, const uint8_t* row_keep, float* out, int64_t* rows_changed, void* stream);
+/* CLASS FIRING COUNTS (the reference's semseg quantitative.get_latent_lookup: for every class the latent whose firing best
+ * predicts it, by F1 over a few thresholds), context-free, from the sparse codes alone.  State is the caller's device memory,
+ * ZERO-INITIALISED before the first call: hist (C x T x S uint32), pos (T x S uint32), n_rows_c (C int64); calls accumulate.
+ * thr (T floats on the HOST): >= 0, strictly ascending, 1 <= T <= 8.  A row (padded codes as above) is KEPT when 0 <= label[b] < C
+ * and row_keep (may be NULL) allows it; a kept row adds 1 to n_rows_c[label[b]].  Each stored entry (s, v) of a kept row with s in
+ * [0, S) has m = #{t : v > thr_t} (strict; a NaN gives 0); m >= 1 adds 1 to hist[label][m - 1][s] and to pos[m - 1][s] -- one pair
+ * of integer atomics per code, not one per threshold.  Exact, order-independent.
+ * saev_class_fire_f1: TP[c, t, s] = sum over u >= t of hist[c][u][s], POS likewise from pos, FP = POS - TP, FN = n_rows_c[c] - TP,
+ *   f1[c, t, s] = float32(2 TP) / (float32(2 TP + FP + FN) + 1e-10f)   (integers exact, each converted once; fp32 division)
+ * f1[c, s] = max over t, a tie going to the LOWEST t, which best_t[c, s] records; latent_mask (S bytes, may be NULL): a latent with
+ * mask 0 gets f1 = -1, best_t = 0.  A zero denominator gives 0.
+ * ONE DIFFERENCE from the reference: a batch without a row of class c still adds its firing rows to c's false positives (POS is
+ * global); the reference's loop over the batch's unique classes skips such batches, so its FP depends on the batching.
+ * Refusals, in this order: negative sizes (SAEV_INVALID_ARG); S >= 2^31 (SAEV_UNSUPPORTED); S < 1 (SAEV_INVALID_ARG); C outside
+ * [1, 4096], T outside [1, 8] (SAEV_UNSUPPORTED); counts only: n_rows, row_cap or n_rows * row_cap >= 2^31 (SAEV_UNSUPPORTED), thr
+ * NULL, negative, NaN or not ascending (SAEV_INVALID_ARG); C * T * S >= 2^31 (SAEV_UNSUPPORTED); a NULL state or output pointer
+ * (SAEV_INVALID_ARG).  n_rows = 0 returns SAEV_OK. */
+int saev_class_fire_counts(const int32_t* idx, const float* val, const int32_t* row_nnz, int64_t row_cap, int64_t n_rows,
+                           const int32_t* label, const uint8_t* row_keep, int64_t S, int64_t C, const float* thr_host, int32_t T,
+                           uint32_t* hist, uint32_t* pos, int64_t* n_rows_c, void* stream);
+int saev_class_fire_f1(const uint32_t* hist, const uint32_t* pos, const int64_t* n_rows_c, int64_t S, int64_t C, int32_t T,
+                       const uint8_t* latent_mask, float* f1, uint8_t* best_t, void* stream);
 /* PROBE1D (the reference's contrib/trait_discovery tdiscovery.probe1d.Sparse1DProbe: what writes probe1d_metrics.npz next to
  * token_acts.npz), context-free: for each of the S x C (latent j, class c) pairs the two-parameter logistic regression
  * y_c ~ sigma(b + w x_j) over N rows, fitted by damped Newton (Levenberg-Marquardt) steps, and its loss and confusion counts.

@@ -113,6 +113,13 @@ class SaevL1LogisticLayout(C.Structure):
                                          "off_g", "off_part", "off_r", "off_loss", "off_bp")]
 
 
+class SaevEdit(C.Structure):
+    """include/saev_amd.h: saev_edit (one edit of a latent; 16 bytes)."""
+
+    _fields_ = [("latent", C.c_int32), ("op", C.c_int32), ("value", C.c_float), ("group", C.c_int32)]
+
+
+EDIT_SET, EDIT_SCALE, EDIT_ADD, EDIT_IF_ACTIVE = 0, 1, 2, 4
 ACT_TOPK, ACT_RELU, ACT_BATCHTOPK = 0, 1, 2
 ROW_OVERFLOW = -7  # saev_status SAEV_ROW_OVERFLOW
 BATCH_OVERWRITE = 1
@@ -230,6 +237,11 @@ _SIGNATURES = {
     "saev_l1_logistic_init": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, P, C.c_int64, P]),
     "saev_l1_logistic_iterate": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, P, C.c_int64, P]),
     "saev_l1_logistic_result": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, P, P, P, P, C.c_int64, P]),
+    "saev_edit_plan_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "saev_edit_plan_build": (C.c_int, [C.POINTER(SaevEdit), C.c_int64, C.c_int64, C.c_int64, P, C.c_int64, P]),
+    "saev_intervene_rows": (C.c_int, [P, C.c_int64, C.c_int64, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int64, P, P, P, P, P]),
+    "saev_class_fire_counts": (C.c_int, [P, P, P, C.c_int64, C.c_int64, P, P, C.c_int64, C.c_int64, C.POINTER(C.c_float), C.c_int32, P, P, P, P]),
+    "saev_class_fire_f1": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int32, P, P, P, P]),
     "saev_comm_unique_id": (C.c_int, [P]),
     "saev_comm_init": (C.c_int, [P, P, C.c_int32, C.c_int32]),
     "saev_comm_world": (C.c_int, [P]),

@@ -1162,6 +1162,147 @@ def l1_logistic(X: torch.Tensor, y: torch.Tensor, C: float, *, kkt_tol: float = 
     return res
 
 
+def _row_bytes(who: str, name: str, t, n: int, device):
+    """A per-row bool / uint8 vector as the C entries take it (None passes through)."""
+    if t is None:
+        return None
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dtype != torch.uint8 or tuple(t.shape) != (n,) or t.device != device:
+        raise ValueError(f"{who}: {name} must be a bool / uint8 vector of {n} rows on {device}")
+    return t.contiguous()
+
+
+def _padded_codes(who: str, idx, val, row_nnz, n: int, device):
+    if idx.ndim != 2 or idx.shape[0] != n:
+        raise ValueError(f"{who}: idx must be ({n}, cap), got {tuple(idx.shape)}")
+    cap = idx.shape[1]
+    return (_on(idx, torch.int32, (n, cap), "idx", device), _on(val, torch.float32, (n, cap), "val", device),
+            _on(row_nnz, torch.int32, (n,), "row_nnz", device), cap)
+
+
+def edit_records(edits) -> "C.Array":
+    """``(latent, op, value, group)`` tuples as the saev_edit array of include/saev_amd.h (no device needed)."""
+    arr = (_lib.SaevEdit * max(len(edits), 1))()
+    for i, (latent, op, value, group) in enumerate(edits):
+        arr[i] = _lib.SaevEdit(int(latent), int(op), float(value), int(group))
+    return arr
+
+
+def build_edit_plan(edits, d_sae: int, n_groups: int, device) -> torch.Tensor:
+    """The device plan of ``saev_edit_plan_build`` for ``(latent, op, value, group)`` tuples (include/saev_amd.h: LATENT EDITS): the
+    edits validated on the host -- ValueError with the library's message for an edit it refuses -- and regrouped on the device.
+    One synchronisation; the plan serves every later ``intervene_rows`` call."""
+    device = _hip_device("build_edit_plan", device)
+    lib = _lib.load()
+    need = int(lib.saev_edit_plan_bytes(len(edits), n_groups))
+    if need < 0:
+        raise ValueError(f"build_edit_plan: at most 65536 edits and 65536 groups, got {len(edits)} and {n_groups}")
+    plan = torch.empty(need, device=device, dtype=torch.uint8)
+    with torch.cuda.device(device):
+        rc = lib.saev_edit_plan_build(edit_records(edits), len(edits), n_groups, d_sae, _ptr(plan), need, _stream())
+    if rc in (-1, -3):
+        raise ValueError((lib.saev_last_error(None) or b"saev_edit_plan_build refused the edits").decode())
+    _lib.check(lib, None, rc, "saev_edit_plan_build")
+    return plan
+
+
+def intervene_rows(x: torch.Tensor, W_dec: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, row_nnz: torch.Tensor | None,
+                   plan: torch.Tensor, n_edits: int, n_groups: int, *, row_group: torch.Tensor | None = None,
+                   row_keep: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                   rows_changed: torch.Tensor | None = None) -> torch.Tensor:
+    """x' = x + sum_e (t_e(f_l) - f_l) W_dec[l_e, :] for the edits of ``plan`` (``build_edit_plan``) on padded code rows
+    (include/saev_amd.h: LATENT EDITS).  x (n, D) float32, W_dec (S, D) float32, idx / val (n, cap), row_nnz (n)
+    int32 or None (full rows), row_group (n) int32, row_keep (n) bool, rows_changed (n_edits) int64 (added to).  ``out`` may be
+    ``x`` (in place); it is allocated when None.  Rows no edit touches come back bit for bit.  There is no CPU path."""
+    who = "intervene_rows"
+    device = _hip_device(who, x.device)
+    if x.ndim != 2 or W_dec.ndim != 2 or x.shape[1] != W_dec.shape[1]:
+        raise ValueError(f"{who}: x must be (n, D) and W_dec (S, D), got {tuple(x.shape)} and {tuple(W_dec.shape)}")
+    n, D = x.shape
+    S = W_dec.shape[0]
+    if out is None:
+        x = _on(x, torch.float32, (n, D), "x", device)
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, D) or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous float32 ({n}, {D}) tensor on {device}")
+    elif not (x.dtype == torch.float32 and x.device == device and x.is_contiguous()):
+        raise ValueError(f"{who}: with out given, x must be a contiguous float32 tensor on {device}")
+    W_dec = _on(W_dec.detach(), torch.float32, (S, D), "W_dec", device)
+    idx, val, row_nnz, cap = _padded_codes(who, idx, val, row_nnz, n, device)
+    row_group = _on(row_group, torch.int32, (n,), "row_group", device)
+    row_keep = _row_bytes(who, "row_keep", row_keep, n, device)
+    if rows_changed is not None and (rows_changed.dtype != torch.int64 or tuple(rows_changed.shape) != (n_edits,) or rows_changed.device != device
+                                     or not rows_changed.is_contiguous()):
+        raise ValueError(f"{who}: rows_changed must be a contiguous int64 vector of {n_edits} edits on {device}")
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        rc = lib.saev_intervene_rows(_ptr(x), n, D, _ptr(W_dec), S, _ptr(idx), _ptr(val), _ptr(row_nnz), cap, _ptr(plan), n_edits, n_groups,
+                                     _ptr(row_group), _ptr(row_keep), _ptr(out), _ptr(rows_changed), _stream())
+    _lib.check(lib, None, rc, "saev_intervene_rows")
+    return out
+
+
+class ClassFireCounts:
+    """Class-conditional firing counts of every latent over a stream of batches (include/saev_amd.h: CLASS FIRING COUNTS; the
+    reference's semseg ``get_latent_lookup``): ``hist`` (C, T, S) / ``pos`` (T, S) uint32 as int32 tensors, ``n_rows_c`` (C) int64.
+    ``add`` takes padded code rows and their labels, ``f1`` forms the best F1 over the thresholds, ``lookup`` the top latents of
+    every class.  Nothing is read back before ``lookup``."""
+
+    def __init__(self, d_sae: int, n_classes: int, device, thresholds=(0.0, 0.1, 0.3, 1.0)):
+        self.device = _hip_device("ClassFireCounts", device)
+        self.lib = _lib.load()
+        self.d_sae, self.n_classes, self.thresholds = d_sae, n_classes, tuple(float(t) for t in thresholds)
+        T = len(self.thresholds)
+        if not 1 <= T <= 8:
+            raise ValueError(f"ClassFireCounts: 1 to 8 thresholds, got {T}")
+        if d_sae < 1 or n_classes < 1 or n_classes * T * d_sae >= 2**31:
+            raise ValueError(f"ClassFireCounts: unsupported shape (n_classes * thresholds * d_sae = {n_classes * T * d_sae} must stay below 2^31)")
+        self._thr = (C.c_float * T)(*self.thresholds)
+        self.hist = torch.zeros(n_classes, T, d_sae, device=self.device, dtype=torch.int32)
+        self.pos = torch.zeros(T, d_sae, device=self.device, dtype=torch.int32)
+        self.n_rows_c = torch.zeros(n_classes, device=self.device, dtype=torch.int64)
+
+    def zero_(self) -> "ClassFireCounts":
+        for t in (self.hist, self.pos, self.n_rows_c):
+            t.zero_()
+        return self
+
+    def add(self, idx: torch.Tensor, val: torch.Tensor, row_nnz: torch.Tensor | None, labels: torch.Tensor,
+            keep: torch.Tensor | None = None) -> None:
+        """One batch: idx (n, cap) int32, val (n, cap) float32, row_nnz (n) int32 or None (full rows), labels (n) integer class ids
+        (a label outside [0, n_classes) drops the row), keep (n) bool."""
+        n = idx.shape[0]
+        idx, val, row_nnz, cap = _padded_codes("ClassFireCounts.add", idx, val, row_nnz, n, self.device)
+        labels = _on(labels.to(torch.int32), torch.int32, (n,), "labels", self.device)
+        keep = _row_bytes("ClassFireCounts.add", "keep", keep, n, self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.saev_class_fire_counts(_ptr(idx), _ptr(val), _ptr(row_nnz), cap, n, _ptr(labels), _ptr(keep), self.d_sae,
+                                                 self.n_classes, self._thr, len(self.thresholds), _ptr(self.hist), _ptr(self.pos),
+                                                 _ptr(self.n_rows_c), _stream())
+        _lib.check(self.lib, None, rc, "saev_class_fire_counts")
+
+    def f1(self, latent_mask: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(f1, best_t)``, (C, S) float32 / uint8 on the device: the best F1 over the thresholds and the index of the (lowest)
+        threshold that gives it; a latent whose ``latent_mask`` (S bool) is False gets -1."""
+        latent_mask = _row_bytes("ClassFireCounts.f1", "latent_mask", latent_mask, self.d_sae, self.device)
+        f1 = torch.empty(self.n_classes, self.d_sae, device=self.device, dtype=torch.float32)
+        best_t = torch.empty(self.n_classes, self.d_sae, device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            rc = self.lib.saev_class_fire_f1(_ptr(self.hist), _ptr(self.pos), _ptr(self.n_rows_c), self.d_sae, self.n_classes,
+                                             len(self.thresholds), _ptr(latent_mask), _ptr(f1), _ptr(best_t), _stream())
+        _lib.check(self.lib, None, rc, "saev_class_fire_f1")
+        return f1, best_t
+
+    def lookup(self, top_k: int = 3, latent_mask: torch.Tensor | None = None):
+        """``(latents, scores, thresholds)``, CPU tensors of shape (C, top_k): every class's best latents by F1, best first, and
+        the threshold each score was reached at."""
+        f1, best_t = self.f1(latent_mask)
+        scores, latents = torch.topk(f1, k=min(top_k, self.d_sae), dim=1)
+        thr = torch.tensor(self.thresholds, dtype=torch.float32)[best_t.gather(1, latents).long().cpu()]
+        return latents.cpu(), scores.cpu(), thr
+
+
 @dataclasses.dataclass
 class StepStats:
     mse: float

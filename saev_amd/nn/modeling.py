@@ -405,6 +405,13 @@ class SparseAutoencoder(torch.nn.Module):
             return self._eng(x.shape[0]).encode_batch_topk(x, training=self.training)
         return self._eng(x.shape[0]).encode_topk(x)
 
+    def intervene(self, x: Tensor, edits, **kwargs):
+        """``x`` (..., d_model) with ``edits`` applied to this SAE's latents and its error term kept:
+        ``saev_amd.interventions.intervene(self, x, edits, **kwargs)``."""
+        from .. import interventions
+
+        return interventions.intervene(self, x, edits, **kwargs)
+
     def decode(self, f_x: Tensor, *, prefixes: Tensor | None = None) -> Tensor:
         """(batch, n_prefixes, d_model) Matryoshka reconstructions of dense latents (modeling.py:351-409)."""
         b, d_sae = f_x.shape
