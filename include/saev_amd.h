@@ -304,8 +304,12 @@ int saev_read_stats(saev_ctx* ctx, saev_step_stats* out_host, void* stream);
 int saev_normalize_w_dec(saev_ctx* ctx, void* stream);
 /* modeling.py:343-347  h = x @ W_enc + b_enc, dense (n_rows x d_sae) output. */
 int saev_encode_dense(saev_ctx* ctx, const float* x, int32_t n_rows, float* h_out, void* stream);
-/* modeling.py:169-179  per-row top-k of a dense (n_rows x d_sae) matrix -> idx/val (n_rows x k),
- * unsorted.  `mask` (d_sae int32, may be NULL) restricts candidates to latents with mask != 0. */
+/* modeling.py:169-179  per-row top-k of a dense (n_rows x d_sae) matrix -> idx/val (n_rows x k), each row in ascending latent
+ * order.  `mask` (d_sae int32, may be NULL) restricts candidates to latents with mask != 0 (any non-zero word).  A mask that
+ * leaves e < k eligible latents gives those e codes followed by k - e slots of idx = -1, val = 0.
+ * The order is a total order on the bit patterns: key = bits ^ 0xFFFFFFFF if the sign bit is set, else bits | 0x80000000; the
+ * larger key wins and equal keys go to the lower latent index.  So +NaN is above +inf, a NaN with the sign bit set is below
+ * -inf, and -0.0 < +0.0.  Values are emitted with their bits unchanged.  1 <= k <= d_sae. */
 int saev_topk_dense(saev_ctx* ctx, const float* h, int32_t n_rows, int32_t k, const int32_t* mask,
                     int32_t* idx_out, float* val_out, void* stream);
 /* encode + TopK without materialising h (the fast path): idx/val (n_rows x top_k). */

@@ -9,7 +9,8 @@
 //                         smaller latent index, output ordered by latent index.
 //
 // Both emit exactly k (idx, val) pairs per row in ascending idx order (deterministic, and what the
-// sparse backward's binary search relies on).  Ties on the k-th value: lowest indices win ("any k"
+// sparse backward's binary search relies on); a row with e < k eligible elements -- a mask, a short candidate list -- emits its e
+// pairs followed by k - e slots of (-1, 0).  Ties on the k-th value: lowest indices win ("any k"
 // is acceptable to the reference: tests/test_nn_activations.py:41-52).
 #include "common.h"
 #include "kernels.h"
@@ -56,8 +57,8 @@ __global__ __launch_bounds__(SD_THREADS) void select_dense_kernel(SelectDenseArg
     for (int row = blockIdx.x; row < a.n_rows; row += gridDim.x) {
     const float* h = a.h + (size_t)row * S;
 
-    // number of eligible elements (mask) bounds k
-    // (without a mask, k <= S is enforced by the host)
+    // (without a mask, k <= S is enforced by the host; a mask may leave fewer than k eligible elements: see the fill after the
+    // compaction)
     uint32_t prefix = 0, pmask = 0;
     int need = k;
 
@@ -152,6 +153,13 @@ __global__ __launch_bounds__(SD_THREADS) void select_dense_kernel(SelectDenseArg
         }
         base_gt += tot & 0xFFFF;
         base_eq += tot >> 16;
+    }
+    // a mask that leaves fewer than k eligible latents: no digit reaches `need`, T stays 0 and every eligible element was written
+    // above; the slots past them read "no code" (-1 / 0), as sort_by_idx_and_store pads a short candidate list.  (With k or more
+    // eligible latents base_gt + min(base_eq, need) == k: nothing to fill.)
+    for (int p = base_gt + min(base_eq, need) + tid; p < k; p += SD_THREADS) {
+        oi[p] = -1;
+        ov[p] = 0.f;
     }
     __syncthreads();  // (the next row's histogram)
     }

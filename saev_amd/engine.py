@@ -1600,13 +1600,46 @@ class SaeEngine:
         self._chk(self.lib.saev_encode_dense(self.ctx, _ptr(x), x.shape[0], _ptr(h), _stream()), "saev_encode_dense")
         return h
 
+    def _check_dev(self, what: str, t: torch.Tensor, dtype: torch.dtype) -> None:
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != dtype:
+            got = f"{t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise _lib.SaevError(f"{what} must be {dtype} on {self.device}, got {got}")
+
+    def _check_codes(self, idx: torch.Tensor, val: torch.Tensor):
+        """(idx, val) of a fixed-length code matrix: int32 / float32 on the engine's device, both (n, k), contiguous."""
+        self._check_dev("idx", idx, torch.int32)
+        self._check_dev("val", val, torch.float32)
+        if idx.ndim != 2 or idx.shape != val.shape or idx.shape[0] < 1 or idx.shape[1] < 1:
+            raise _lib.SaevError(f"idx and val must both be (n, k), got {tuple(idx.shape)} and {tuple(val.shape)}")
+        return idx.contiguous(), val.contiguous()
+
     def topk_dense(self, h: torch.Tensor, k: int, mask: torch.Tensor | None = None):
+        """``(idx, val)``, (n, k) each, of the per-row top-k of ``h`` (n, d_sae), in ascending latent order (include/saev_amd.h,
+        saev_topk_dense: the order of NaN and of the zeros, and the -1 / 0 slots of a mask with fewer than k eligible latents).
+        ``h`` must be float32 on the engine's device.  ``mask`` is a (d_sae,) bool or integer tensor, non-zero = eligible; it is the
+        one argument that may live on another device (the host, usually): it is a small vector that is converted to int32 words and
+        copied here anyway."""
+        S = self.cfg.d_sae
+        self._check_dev("h", h, torch.float32)
+        if h.ndim != 2 or h.shape[1] != S or h.shape[0] < 1:
+            raise _lib.SaevError(f"h must be (n, {S}), got {tuple(h.shape)}")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= S:
+            raise _lib.SaevError(f"k must be an int in 1..{S}, got {k!r}")
         h = h.contiguous()
+        if h.data_ptr() % 16:
+            h = h.clone()
         n = h.shape[0]
         idx = torch.empty(n, k, device=self.device, dtype=torch.int32)
         val = torch.empty(n, k, device=self.device, dtype=torch.float32)
         if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.shape != (S,) or mask.is_floating_point() or mask.is_complex():
+                raise _lib.SaevError(f"mask must be an integer or bool tensor of shape ({S},), got "
+                                     f"{tuple(mask.shape) if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+            if mask.dtype != torch.int32:  # (an int64 word whose low half is zero must stay "eligible")
+                mask = mask != 0
             mask = mask.to(self.device, torch.int32).contiguous()
+            if mask.data_ptr() % 16:
+                mask = mask.clone()
         self._chk(self.lib.saev_topk_dense(self.ctx, _ptr(h), n, k, _ptr(mask), _ptr(idx), _ptr(val), _stream()), "saev_topk_dense")
         return idx, val
 
@@ -1621,20 +1654,24 @@ class SaeEngine:
         return idx, val
 
     def scatter_dense(self, idx: torch.Tensor, val: torch.Tensor) -> torch.Tensor:
+        idx, val = self._check_codes(idx, val)
         n, k = idx.shape
         f = torch.zeros(n, self.cfg.d_sae, device=self.device, dtype=torch.float32)
-        self._chk(self.lib.saev_scatter_dense(self.ctx, _ptr(idx.contiguous()), _ptr(val.contiguous()), n, k, _ptr(f), _stream()), "saev_scatter_dense")
+        self._chk(self.lib.saev_scatter_dense(self.ctx, _ptr(idx), _ptr(val), n, k, _ptr(f), _stream()), "saev_scatter_dense")
         return f
 
     def decode_sparse(self, idx: torch.Tensor, val: torch.Tensor, prefixes=None) -> torch.Tensor:
+        idx, val = self._check_codes(idx, val)
         n, k = idx.shape
         if prefixes is None:
             pre = [self.cfg.d_sae]
         else:
             pre = [int(p) for p in prefixes]
+        if not pre:
+            raise _lib.SaevError("prefixes must hold at least one cut")
         arr = (C.c_int64 * len(pre))(*pre)
         out = torch.empty(n, len(pre), self.cfg.d_model, device=self.device, dtype=torch.float32)
-        self._chk(self.lib.saev_decode_sparse(self.ctx, _ptr(idx.contiguous()), _ptr(val.contiguous()), n, k, arr, len(pre), _ptr(out), _stream()), "saev_decode_sparse")
+        self._chk(self.lib.saev_decode_sparse(self.ctx, _ptr(idx), _ptr(val), n, k, arr, len(pre), _ptr(out), _stream()), "saev_decode_sparse")
         return out
 
     # ---- ReLU SAE forward: padded variable-length rows (include/saev_amd.h, saev_encode_relu) ---------------------------
@@ -1734,9 +1771,23 @@ class SaeEngine:
         self._chk(self.lib.saev_remove_parallel_grads(self.ctx, _stream()), "saev_remove_parallel_grads")
 
     def gather_rows(self, pool: torch.Tensor, rows: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """``out[r] = pool[rows[r]]``: pool (rows, d_model) float32, contiguous; rows (n,) int64, every entry a row of the pool
+        (the kernel does not check: the caller draws them); ``out`` (n, d_model) float32, contiguous, written in place."""
+        D = self.cfg.d_model
+        self._check_dev("pool", pool, torch.float32)
+        self._check_dev("rows", rows, torch.int64)
+        if pool.ndim != 2 or pool.shape[1] != D or not pool.is_contiguous() or pool.data_ptr() % 16:
+            raise _lib.SaevError(f"pool must be a contiguous, 16-byte aligned (rows, {D}) matrix, got {tuple(pool.shape)} with strides {pool.stride()}")
+        if rows.ndim != 1 or rows.shape[0] < 1:
+            raise _lib.SaevError(f"rows must be (n,) with n >= 1, got {tuple(rows.shape)}")
+        rows = rows.contiguous()
         n = rows.shape[0]
         if out is None:
-            out = torch.empty(n, self.cfg.d_model, device=self.device, dtype=torch.float32)
+            out = torch.empty(n, D, device=self.device, dtype=torch.float32)
+        else:
+            self._check_dev("out", out, torch.float32)
+            if out.shape != (n, D) or not out.is_contiguous() or out.data_ptr() % 16:
+                raise _lib.SaevError(f"out must be a contiguous, 16-byte aligned ({n}, {D}) matrix, got {tuple(out.shape)} with strides {out.stride()}")
         self._chk(self.lib.saev_gather_rows(self.ctx, _ptr(pool), _ptr(rows), n, _ptr(out), _stream()), "saev_gather_rows")
         return out
 

@@ -193,8 +193,9 @@ class TopKActivation(torch.nn.Module):
             raise RuntimeError("TopKActivation needs its owning SparseAutoencoder to reach the HIP engine")
         eng = sae._eng()
         k = min(self.cfg.top_k, x.shape[-1])
-        idx, val = eng.topk_dense(x, k)
-        return eng.scatter_dense(idx, val)
+        # top-k along the last dimension, as torch.topk(dim=-1): leading dimensions are rows
+        idx, val = eng.topk_dense(x.reshape(-1, x.shape[-1]), k)
+        return eng.scatter_dense(idx, val).reshape(x.shape)
 
 
 class ReluActivation(torch.nn.Module):
