@@ -1127,6 +1127,50 @@ int saev_l1_logistic_iterate(const float* X, const int32_t* y, int64_t n, int64_
                              void* workspace, int64_t workspace_bytes, void* stream);
 int saev_l1_logistic_result(const float* X, const int32_t* y, int64_t n, int64_t S, int64_t K, double C, double kkt_tol, double* coef,
                             double* intercept, double* scalars, void* workspace, int64_t workspace_bytes, void* stream);
+/* COACTIVATION (latents matched by what they fire on: idea 8, "cross-run feature alignment", of the reference's
+ * contrib/mimics/README.md, which the reference never built), context-free; DESIGN.md 3.25.
+ *
+ * A (N x Sa) and B (N x Sb) are CSR matrices over the SAME N rows, each as every analysis entry takes it (indptr: N + 1 int64
+ * absolute positions with indptr[last] <= nnz, indices int32 in [0, S), data fp32); rows must be CANONICAL (no column twice in a
+ * row; the result for such a row is unspecified, nothing is read or written out of bounds).  A stored entry FIRES when value > thr
+ * (value == thr does not).  The firing set of a latent is the set of rows in which it fires; n_a (Sa int32) and n_b (Sb int32) are
+ * the set sizes, I(a, b) the number of rows in which a of A and b of B both fire.  For every latent a the call writes its top_m
+ * partners b with I(a, b) >= 1 to out_index (Sa x top_m int32) and their I to out_inter (Sa x top_m int32), best first; a latent
+ * with fewer partners is padded with index -1 and intersection 0.  b_indptr == NULL matches A against itself: the pair b == a is no
+ * partner, Sb, nnz_b, thr_b, b_indices, b_data and n_b are ignored (n_b may be NULL; the supports are n_a).
+ * THE ORDER is defined on integers, so that every correct implementation gives the same answer:
+ *   SAEV_COACT_JACCARD      I / (n_a + n_b - I).  With U = n_a + n_b - I, b1 ranks before b2 iff I1 * U2 > I2 * U1 in unsigned 64-bit
+ *                           (I < 2^31, U < 2^32); on equality iff b1 < b2.
+ *   SAEV_COACT_CONTAINMENT  I / n_a ("which latent covers a's rows").  b1 ranks before b2 iff I1 > I2; then n_b1 < n_b2; then b1 < b2.
+ * Floating-point similarities are the caller's to form from the integers; none is formed inside.
+ * err (one int32 on the device, zeroed by the call): 0, or the largest SAEV_COACT_ERR_* met in A or B -- the outputs are void then,
+ * nothing is read or written out of bounds, and the caller reads the word when it next synchronises.
+ * METHOD.  The firing entries of A are counted per latent and their rows placed under their latent (integer global atomics; the
+ * order inside a latent is free, everything downstream is a count).  A workgroup owns one latent a and a window of
+ * saev_coactivation_window() latents of B (fewer, with more workgroups a CU, where Sb is smaller) as uint32 counters in LDS: for every row of a's list a lane group reads B's row and adds 1
+ * to the counter of each firing entry inside the window, then the non-zero counters become keys and the best 8 are kept; Sb past
+ * the window takes further windows.  A latent with more than saev_coactivation_chunk_rows() rows is cut into chunks of that many,
+ * each walked by its own workgroup and added into a global int32 row of Sb counters, which a second kernel ranks;
+ * saev_coactivation_slots() such rows exist and the heavy latents are taken that many at a time.  No float atomics: two calls
+ * give the same bits, and so does any order of the rows.
+ * 1 <= N, Sa, Sb < 2^31, 0 <= nnz_a, nnz_b < 2^31 (else SAEV_UNSUPPORTED, -1 from the size function), 1 <= top_m <= 8.  workspace:
+ * saev_coactivation_workspace_bytes(N, Sa, Sb, nnz_a, nnz_b) bytes of device memory, 256-byte aligned (for B == NULL: Sb = Sa, nnz_b =
+ * nnz_a): the offsets and cursors (Sa), the event list (nnz_a), the heavy list, and min(heavy bound, slots) x Sb counters, where
+ * the heavy bound is min(Sa, nnz_a / (chunk_rows + 1)).  Arguments are checked before the device is touched; a refused call leaves
+ * its message with saev_last_error(NULL).  Nothing is allocated, read back or synchronised. */
+#define SAEV_COACT_JACCARD 0
+#define SAEV_COACT_CONTAINMENT 1
+#define SAEV_COACT_ERR_COLUMN 1
+#define SAEV_COACT_ERR_VALUE 2
+#define SAEV_COACT_ERR_INDPTR 3
+int64_t saev_coactivation_chunk_rows(void);
+int64_t saev_coactivation_window(void);
+int64_t saev_coactivation_slots(void);
+int64_t saev_coactivation_workspace_bytes(int64_t N, int64_t Sa, int64_t Sb, int64_t nnz_a, int64_t nnz_b);
+int saev_coactivation(const int64_t* a_indptr, const int32_t* a_indices, const float* a_data, int64_t nnz_a, int64_t Sa,
+                      const int64_t* b_indptr, const int32_t* b_indices, const float* b_data, int64_t nnz_b, int64_t Sb, int64_t N,
+                      float thr_a, float thr_b, int32_t measure, int32_t top_m, int32_t* n_a, int32_t* n_b, int32_t* out_index,
+                      int32_t* out_inter, int32_t* err, void* workspace, int64_t workspace_bytes, void* stream);
 /* PARAMETER OWNERSHIP.  With the f16r encoder the context keeps, from one call to the next, what its forward needs of W_enc
  * (fp16 operand images, a slice-major fp32 transpose, bias and norm shares: written by the Adam launch of saev_train_step, or by
  * the last forward that prepared them itself) and uses it for as long as only the library has written the parameter buffer.  A

@@ -237,6 +237,12 @@ _SIGNATURES = {
     "saev_l1_logistic_init": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, P, C.c_int64, P]),
     "saev_l1_logistic_iterate": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, P, C.c_int64, P]),
     "saev_l1_logistic_result": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, P, P, P, P, C.c_int64, P]),
+    "saev_coactivation_chunk_rows": (C.c_int64, []),
+    "saev_coactivation_window": (C.c_int64, []),
+    "saev_coactivation_slots": (C.c_int64, []),
+    "saev_coactivation_workspace_bytes": (C.c_int64, [C.c_int64] * 5),
+    "saev_coactivation": (C.c_int, [P, P, P, C.c_int64, C.c_int64, P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_int32,
+                                    C.c_int32, P, P, P, P, P, P, C.c_int64, P]),
     "saev_edit_plan_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "saev_edit_plan_build": (C.c_int, [C.POINTER(SaevEdit), C.c_int64, C.c_int64, C.c_int64, P, C.c_int64, P]),
     "saev_intervene_rows": (C.c_int, [P, C.c_int64, C.c_int64, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int64, P, P, P, P, P]),

@@ -1080,6 +1080,109 @@ def pool_images(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor,
     return PoolResult(out, err, -(-n_latents // range_len), range_len)
 
 
+class CoactResult(_Checked):
+    """What ``coactivation_match`` leaves on the device: ``index`` (Sa, top_m) int32, per latent of A its best partners in B, best
+    first, -1 where it has fewer; ``intersection`` (Sa, top_m) int32, the rows in which both fire; ``support_a`` (Sa) and
+    ``support_b`` (Sb) int32, the sizes of the firing sets.  ``jaccard`` and ``containment`` (Sa, top_m) float64 are formed from those
+    integers, NaN where the index is -1.  ``mutual`` (Sa) bool: a's best partner's best partner is a (for two matrices a second call
+    with the roles swapped, made on first use; ``reverse`` is its result).  The call itself does not synchronise; the first read of
+    a result -- or ``check()`` -- reads the device's error word (one synchronisation) and raises ValueError if it is not 0."""
+
+    _ERRORS = {1: "a column index lies outside [0, n_latents)", 2: "a stored value is not finite", 3: "indptr is not a non-decreasing sequence of positions into indices"}
+
+    def __init__(self, out, err, ws, measure, top_m, swapped):
+        super().__init__(out, err, self._ERRORS, "coactivation_match")
+        self.measure, self.top_m, self._ws, self._swapped, self._reverse = measure, top_m, ws, swapped, None
+
+    index = property(lambda self: self._read("index"))
+    intersection = property(lambda self: self._read("intersection"))
+    support_a = property(lambda self: self._read("support_a"))
+    support_b = property(lambda self: self._read("support_b"))
+
+    def _partner_support(self):
+        return self.support_b.to(torch.int64)[self.index.clamp_min(0).to(torch.int64)]
+
+    @property
+    def jaccard(self) -> torch.Tensor:
+        inter = self.intersection.to(torch.int64)
+        union = self.support_a.to(torch.int64)[:, None] + self._partner_support() - inter
+        return torch.where(self.index >= 0, inter.double() / union.double(), torch.nan)
+
+    @property
+    def containment(self) -> torch.Tensor:
+        inter = self.intersection.to(torch.int64)
+        return torch.where(self.index >= 0, inter.double() / self.support_a.to(torch.int64)[:, None].double(), torch.nan)
+
+    @property
+    def reverse(self) -> "CoactResult":
+        """B's latents matched against A's (the same measure, top_m = 1); of a self match the result itself."""
+        if self._reverse is None:
+            self._reverse = self if self._swapped is None else self._swapped()
+        return self._reverse
+
+    @property
+    def mutual(self) -> torch.Tensor:
+        best = self.index[:, 0].to(torch.int64)
+        back = self.reverse.index[:, 0].to(torch.int64)
+        own = torch.arange(best.numel(), device=best.device)
+        return (best >= 0) & (back[best.clamp_min(0)] == own)
+
+
+_COACT_MEASURES = {"jaccard": 0, "containment": 1}
+
+
+def coactivation_match(A, B=None, *, n_rows: int, n_latents_a: int, n_latents_b: int | None = None, thr_a: float = 0.0, thr_b: float = 0.0,
+                       measure: str = "jaccard", top_m: int = 1) -> CoactResult:
+    """For every latent of A the ``top_m`` latents of B whose firing sets overlap its own most, on the HIP kernels of
+    saev_coactivation (include/saev_amd.h: COACTIVATION): no Sa x Sb matrix, nothing read back.  A and B are CSR
+    triples (indptr, indices, data) on one HIP device over the same ``n_rows`` rows (indptr int64, indices int32, data float32, rows
+    canonical); an entry fires when its value is > the threshold.  ``B=None`` matches A against itself with the pair b == a
+    excluded.  ``measure``: "jaccard" (I / (n_a + n_b - I)) or "containment" (I / n_a); the ranking is on integers (ties: the
+    lower index for Jaccard; the smaller support, then the lower index for containment).  There is no CPU path."""
+    if measure not in _COACT_MEASURES:
+        raise ValueError(f"coactivation_match: measure must be one of {sorted(_COACT_MEASURES)}, got {measure!r}")
+    if not 1 <= top_m <= 8:
+        raise ValueError(f"coactivation_match: unsupported top_m {top_m} (1 <= top_m <= 8)")
+    if B is None:
+        if n_latents_b not in (None, n_latents_a):
+            raise ValueError(f"coactivation_match: n_latents_b {n_latents_b} without B (a self match has n_latents_a = {n_latents_a} partners)")
+        n_latents_b = n_latents_a
+    elif n_latents_b is None:
+        raise ValueError("coactivation_match: n_latents_b comes with B")
+    for name, v in (("n_rows", n_rows), ("n_latents_a", n_latents_a), ("n_latents_b", n_latents_b)):
+        if not 1 <= v < 2**31:
+            raise ValueError(f"coactivation_match: unsupported {name} {v} (1 <= {name} < 2^31)")
+    if not (math.isfinite(thr_a) and math.isfinite(thr_b)):
+        raise ValueError(f"coactivation_match: thresholds must be finite, got {thr_a} and {thr_b}")
+    device = _hip_device("coactivation_match", A[0].device)
+    A = _csr_on(*A, n_rows, A[1].numel(), device)
+    B = None if B is None else _csr_on(*B, n_rows, B[1].numel(), device)
+    return _coactivation(A, B, n_rows, n_latents_a, n_latents_b, float(thr_a), float(thr_b), measure, top_m, device)
+
+
+def _coactivation(A, B, n_rows, Sa, Sb, thr_a, thr_b, measure, top_m, device) -> CoactResult:
+    lib = _lib.load()
+    nnz_a = A[1].numel()
+    nnz_b = nnz_a if B is None else B[1].numel()
+    nbytes = int(lib.saev_coactivation_workspace_bytes(n_rows, Sa, Sb, nnz_a, nnz_b))
+    if nbytes < 0:
+        raise ValueError(f"coactivation_match: unsupported sizes {(n_rows, Sa, Sb, nnz_a, nnz_b)} (all below 2^31)")
+    i32 = dict(device=device, dtype=torch.int32)
+    ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    support_a = torch.empty(Sa, **i32)
+    out = dict(index=torch.empty(Sa, top_m, **i32), intersection=torch.empty(Sa, top_m, **i32), support_a=support_a,
+               support_b=support_a if B is None else torch.empty(Sb, **i32))
+    err = torch.empty(1, **i32)
+    none3 = (None, None, None)
+    with torch.cuda.device(device):
+        rc = lib.saev_coactivation(*map(_ptr, A), nnz_a, Sa, *(none3 if B is None else map(_ptr, B)), nnz_b, Sb, n_rows, thr_a, thr_b,
+                                   _COACT_MEASURES[measure], top_m, _ptr(support_a), None if B is None else _ptr(out["support_b"]),
+                                   _ptr(out["index"]), _ptr(out["intersection"]), _ptr(err), _ptr(ws), nbytes, _stream())
+    _lib.check(lib, None, rc, "saev_coactivation")
+    swapped = None if B is None else (lambda: _coactivation(B, A, n_rows, Sb, Sa, thr_b, thr_a, measure, 1, device))
+    return CoactResult(out, err, ws, measure, top_m, swapped)
+
+
 @dataclasses.dataclass
 class L1LogisticResult:
     """A fit of ``l1_logistic``: ``coef_`` (1, S) for two classes and (K, S) otherwise and ``intercept_`` (float64, on the device; the
