@@ -35,6 +35,10 @@ constexpr int IV_CNT_SLOTS = 256;
 constexpr int IV_TRIPS = 4;                 // trips of a wave over D in flight
 constexpr int IV_MAX_GRID = 2048;           // workgroups; the rows beyond are strided over (8 a CU: the residency of the kernel)
 
+constexpr int CF_CODES_MAX_GRID = 8192;     // workgroups of 256 threads; the code slots, rows and (class, latent) pairs beyond are
+constexpr int CF_ROWS_MAX_GRID = 1024;      // strided over
+constexpr int CF_F1_MAX_GRID = 8192;
+
 constexpr int OP_MASK = 3;
 
 struct IvPlanLayout {
@@ -444,9 +448,9 @@ int saev_class_fire_counts(const int32_t* idx, const float* val, const int32_t* 
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = n_rows * row_cap;
     if (total > 0)
-        hipLaunchKernelGGL(cf_codes_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, s, idx, val, row_nnz,
+        hipLaunchKernelGGL(cf_codes_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, CF_CODES_MAX_GRID)), dim3(256), 0, s, idx, val, row_nnz,
                            (int)row_cap, (long)total, label, row_keep, (int)S, (int)C, thr, (int)T, hist, pos);
-    hipLaunchKernelGGL(cf_rows_kernel, dim3((unsigned)std::min<int64_t>((n_rows + 255) / 256, 1024)), dim3(256), (size_t)C * 4, s, label,
+    hipLaunchKernelGGL(cf_rows_kernel, dim3((unsigned)std::min<int64_t>((n_rows + 255) / 256, CF_ROWS_MAX_GRID)), dim3(256), (size_t)C * 4, s, label,
                        row_keep, (int)n_rows, (int)C, reinterpret_cast<unsigned long long*>(n_rows_c));
     if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");
     return SAEV_OK;
@@ -459,7 +463,7 @@ int saev_class_fire_f1(const uint32_t* hist, const uint32_t* pos, const int64_t*
     if (C * (int64_t)T * S >= 0x80000000LL) return entry_refuse(SAEV_UNSUPPORTED, who, "C * T * S must stay below 2^31");
     if (!hist || !pos || !n_rows_c || !f1 || !best_t) return entry_refuse(SAEV_INVALID_ARG, who, "hist, pos, n_rows_c, f1 or best_t is NULL");
     const int64_t total = C * S;
-    hipLaunchKernelGGL(cf_f1_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, (hipStream_t)stream, hist, pos,
+    hipLaunchKernelGGL(cf_f1_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, CF_F1_MAX_GRID)), dim3(256), 0, (hipStream_t)stream, hist, pos,
                        reinterpret_cast<const long long*>(n_rows_c), (int)S, (int)C, (int)T, latent_mask, f1, best_t);
     if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");
     return SAEV_OK;

@@ -90,6 +90,81 @@ def intervene(x, W, idx, val, row_nnz, edits, n_groups: int, row_group=None, row
     return dict(out=out, mag=mag, m=m, rows_changed=changed, coef=coef)
 
 
+def _coefficients_fast(f: np.ndarray, op: int, value: np.float32):
+    """``coefficient`` on a vector of f: (c float32, applies bool).  SCALE forms value * f exactly in fp64 (48 bits) and
+    checks with an error-free two-sum that the fp64 subtraction of f was exact too, so that the conversion to float32 is
+    the one rounding of fmaf; an element that fails the check goes through ``coefficient``."""
+    f = np.asarray(f, dtype=np.float32)
+    value = np.float32(value)
+    kind = op & 3
+    with np.errstate(all="ignore"):
+        if kind == SET:
+            c = (value - f).astype(np.float32)
+        elif kind == SCALE:
+            p = np.float64(value) * f.astype(np.float64)
+            b = -f.astype(np.float64)
+            s = p + b
+            bb = s - p
+            exact = ((p - (s - bb)) + (b - bb) == 0) & np.isfinite(s)
+            c = s.astype(np.float32)
+            for i in np.nonzero(~exact)[0]:
+                ci = coefficient(f[i], SCALE, value)
+                c[i] = 0 if ci is None else ci
+        else:
+            c = np.full(f.shape, value, dtype=np.float32)
+    applies = c != 0
+    if op & IF_ACTIVE:
+        applies &= f != 0
+    return c, applies
+
+
+def intervene_fast(x, W, idx, val, row_nnz, edits, n_groups: int, row_group=None, row_keep=None):
+    """``intervene`` with the rows of an edit taken together: the same arguments, and ``out``, ``mag``, ``m`` and
+    ``rows_changed`` equal to its on the bits (every row receives its edits in the same order -- the global list, then its
+    group's, the caller's order inside a list -- through the same fp64 operations).  ``coef`` is replaced by ``applied``:
+    for every edit that was applied anywhere, the rows it was applied to.  A list no row belongs to costs nothing."""
+    x = np.asarray(x, dtype=np.float32)
+    W = np.asarray(W, dtype=np.float32)
+    n, D = x.shape
+    cap = idx.shape[1] if idx.ndim == 2 else 0
+    keep = np.ones(n, dtype=bool) if row_keep is None else np.asarray(row_keep).astype(bool)
+    group = np.full(n, -1, dtype=np.int64) if row_group is None else np.asarray(row_group).astype(np.int64)
+    group = np.where((group >= 0) & (group < n_groups), group, -1)
+    nnz = np.full(n, cap, dtype=np.int64) if row_nnz is None else np.clip(np.asarray(row_nnz).astype(np.int64), 0, cap)
+    live = np.arange(cap)[None, :] < nnz[:, None]
+    edit_group = np.array([e[3] for e in edits], dtype=np.int64).reshape(-1)
+    by_list = np.argsort(edit_group, kind="stable")  # the global list first, the caller's order kept inside a list
+    lo = np.searchsorted(edit_group[by_list], np.arange(-1, n_groups), side="left")
+    hi = np.searchsorted(edit_group[by_list], np.arange(-1, n_groups), side="right")
+    out = x.astype(np.float64)
+    mag = np.abs(x).astype(np.float64)
+    m = np.zeros(n, dtype=np.int64)
+    changed = np.zeros(len(edits), dtype=np.int64)
+    applied = {}
+    for g in [-1] + sorted(set(group[keep & (group >= 0)].tolist())):
+        rows = np.nonzero(keep if g == -1 else keep & (group == g))[0]
+        if rows.size == 0:
+            continue
+        for i in by_list[lo[g + 1]:hi[g + 1]]:
+            latent, op, value, _ = edits[i]
+            if cap:
+                match = (idx[rows] == latent) & live[rows]
+                f = np.where(match.any(axis=1), val[rows, np.argmax(match, axis=1)], np.float32(0)).astype(np.float32)
+            else:
+                f = np.zeros(rows.size, dtype=np.float32)
+            c, applies = _coefficients_fast(f, op, np.float32(value))
+            r, c = rows[applies], c[applies].astype(np.float64)
+            if r.size == 0:
+                continue
+            with np.errstate(all="ignore"):
+                out[r] += c[:, None] * W[latent].astype(np.float64)[None, :]
+                mag[r] += np.abs(c)[:, None] * np.abs(W[latent]).astype(np.float64)[None, :]
+            m[r] += 1
+            changed[i] = r.size
+            applied[int(i)] = r
+    return dict(out=out, mag=mag, m=m, rows_changed=changed, applied=applied)
+
+
 def tolerance(mag, m):
     """(m + 1) u / (1 - (m + 1) u) * (|x_d| + sum |c_e| |W_l_e,d|) + m 2^-149, u = 2^-24: the fmaf chain of m links starting
     from x (each link rounds once; gamma_{m+1} also covers the fp64 evaluation of the restatement itself), plus one smallest
@@ -125,6 +200,29 @@ def fire_counts(idx, val, row_nnz, labels, keep, S: int, C: int, thr):
             if m >= 1:
                 hist[c, m - 1, s] += 1
                 pos[m - 1, s] += 1
+    return hist, pos, n_rows_c
+
+
+def fire_counts_fast(idx, val, row_nnz, labels, keep, S: int, C: int, thr):
+    """``fire_counts`` with one ``bincount`` per result: the same arguments, the same three int64 arrays."""
+    thr = np.asarray(thr, dtype=np.float32)
+    T = len(thr)
+    idx = np.asarray(idx)
+    val = np.asarray(val, dtype=np.float32)
+    n, cap = idx.shape
+    labels = np.asarray(labels).astype(np.int64)
+    ok = (labels >= 0) & (labels < C)
+    if keep is not None:
+        ok &= np.asarray(keep).astype(bool)
+    n_rows_c = np.bincount(labels[ok], minlength=C).astype(np.int64)
+    nnz = np.full(n, cap, dtype=np.int64) if row_nnz is None else np.clip(np.asarray(row_nnz).astype(np.int64), 0, cap)
+    with np.errstate(invalid="ignore"):
+        m = (val[:, :, None] > thr[None, None, :]).sum(axis=2)  # strict; NaN > t is False
+    use = ok[:, None] & (np.arange(cap)[None, :] < nnz[:, None]) & (idx >= 0) & (idx < S) & (m >= 1)
+    b, j = np.nonzero(use)
+    s, bin_ = idx[b, j].astype(np.int64), m[b, j].astype(np.int64) - 1
+    hist = np.bincount((labels[b] * T + bin_) * S + s, minlength=C * T * S).astype(np.int64).reshape(C, T, S)
+    pos = np.bincount(bin_ * S + s, minlength=T * S).astype(np.int64).reshape(T, S)
     return hist, pos, n_rows_c
 
 

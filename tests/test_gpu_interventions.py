@@ -27,8 +27,9 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
-def check_edit(x, W, idx, val, row_nnz, edits, n_groups, row_group=None, row_keep=None):
-    """Runs the kernel out of place, in place and once more; compares with the restatement; returns the restatement."""
+def check_edit(x, W, idx, val, row_nnz, edits, n_groups, row_group=None, row_keep=None, expected=None):
+    """Runs the kernel out of place, in place, once more and into a buffer of NaNs; compares with the restatement (``expected`` when
+    the caller has it already); returns the restatement."""
     from saev_amd import engine
 
     S = W.shape[0]
@@ -43,7 +44,7 @@ def check_edit(x, W, idx, val, row_nnz, edits, n_groups, row_group=None, row_kee
         return res.cpu().numpy(), counts.cpu().numpy()
 
     got, counts = run()
-    r = IR.intervene(x, W, idx, val, row_nnz, edits, n_groups, row_group=row_group, row_keep=row_keep)
+    r = expected if expected is not None else IR.intervene(x, W, idx, val, row_nnz, edits, n_groups, row_group=row_group, row_keep=row_keep)
     untouched = r["m"] == 0
     assert (_bits(got[untouched]) == _bits(x[untouched])).all(), "a row without a remaining edit must come back on the bits"
     tol = IR.tolerance(r["mag"], r["m"])
@@ -56,6 +57,8 @@ def check_edit(x, W, idx, val, row_nnz, edits, n_groups, row_group=None, row_kee
     assert (_bits(inplace) == _bits(got)).all() and (counts2 == counts).all(), "in place differs from out of place"
     again, _ = run()
     assert (_bits(again) == _bits(got)).all(), "two calls differ"
+    given, _ = run(out=torch.full_like(xd, float("nan")))  # an element the kernel does not write stays NaN
+    assert (_bits(given) == _bits(got)).all(), "an output buffer passed in differs from one allocated by the call"
     return r
 
 
