@@ -727,6 +727,62 @@ int saev_latent_topk_update(const int32_t* idx, const float* val, const int32_t*
                             const int32_t* indices, const float* data, int64_t nnz, const uint8_t* keep, int64_t n, int64_t S,
                             int64_t row_base, const saev_latent_topk_state* state, void* workspace, int64_t workspace_bytes,
                             void* stream);
+/* LATENT HISTOGRAM (per-latent activation histograms and exact quantiles over a stream of batches), context-free.
+ * THE KEY of a float32 v with bit pattern u is ~u when the sign bit is set, else u | 0x80000000: strictly increasing in v,
+ * invertible.  LEVEL 0 is key >> 20 (sign, exponent and three mantissa bits: 4096 bins, eight to the octave, float32 edges
+ * 2^e (1 + i/8)), level 1 (key >> 10) & 1023, level 2 key & 1023.
+ * An ENTRY is a slot with val != 0 whose latent lies in [0, S) -- the rules of LATENT TOP-K: negatives, denormals and +-Inf are
+ * entries, zeros of both signs are none, NaN and more than one entry per (row, latent) are outside the contract.
+ * saev_latent_hist_update consumes one batch of n rows in one of saev_latent_topk_update's two forms (padded rows or CSR; both or
+ * neither is SAEV_INVALID_ARG) with the optional keep bytes, and ADDS to the caller's ZERO-INITIALISED device state:
+ *   level 0      counts (S x 4096 uint32): counts[j, b] += entries of latent j with level-0 bin b
+ *   level 1, 2   counts (S x T x 1024 uint32): counts[j, t, d] += entries of latent j whose key carries prefix[j, t] (its level-0
+ *                bin at level 1, its top 22 bits at level 2) and whose digit of this level is d; prefix is S x 16 uint32, the first
+ *                T <= 16 of a row live, 0xffffffff = a target already resolved.  Two targets with one prefix count twice.
+ *   every level  *n_rows (int64) += the kept rows of the batch
+ * counts and prefix are 16-byte aligned; a table holds fewer than 2^32 - 1 counters (SAEV_UNSUPPORTED otherwise).  Counts are
+ * uint32: the caller offers fewer than 2^32 rows.  Integer atomics only: the counts are exact and the same for every order and
+ * every split of the batches.  workspace: saev_latent_hist_workspace_bytes(n_entries, S) bytes, 256-byte aligned (the batch's
+ * kept-row count; -1: unsupported).
+ * saev_latent_hist_locate is one launch that reads nothing back.  For latent j let M_j be its entries (over_rows = 0) or the kept
+ * rows *n_rows (over_rows = 1: the M_j - entries silent rows enter as one block of zeros between level-0 bins 2047 and 2048, in
+ * closed form).  For quantile q_i: h = (M_j - 1) q_i as one fp64 product; target 2 i is rank floor(h), target 2 i + 1 rank ceil(h)
+ * of the sorted multiset.  At level 0 it writes count[j] = M_j and, per target, the level-0 bin holding the rank (prefix), the
+ * rank left inside that bin (rank) and resolved: 0 open, 1 inside the zero block (the value is 0.0), 2 empty multiset.  At levels
+ * 1 and 2 it extends prefix by the digit found in the target's own 1024 counters and replaces rank.  After level 2 it also writes
+ * lower, higher (S x Q fp32: the floats of the 32 located bits, exact) and linear (S x Q fp64) =
+ * lower + (h - floor(h)) (higher - lower), each operation rounded once, = lower when lower == higher; NaN in all three when
+ * M_j = 0.  1 <= Q <= 8 (SAEV_UNSUPPORTED), every q in [0, 1], and at levels 1, 2 the state's T = 2 Q.
+ * Arguments are checked before the device is touched; a refused call leaves its message with saev_last_error(NULL); n = 0 (S = 0
+ * for locate) returns SAEV_OK and writes nothing; nothing synchronises. */
+typedef struct {
+    int32_t struct_size;   /* sizeof(saev_latent_hist_state) of the caller (fields past it read as 0) */
+    int32_t level;         /* 0, 1 or 2 */
+    int32_t T;             /* levels 1, 2: live targets per latent */
+    int32_t reserved;
+    uint32_t* counts;
+    int64_t* n_rows;
+    uint32_t* prefix;      /* levels 1, 2 */
+} saev_latent_hist_state;
+typedef struct {
+    int32_t struct_size;   /* sizeof(saev_latent_hist_targets) of the caller */
+    int32_t Q;
+    int32_t over_rows;
+    int32_t reserved;
+    double q[8];
+    uint32_t* prefix;      /* S x 16 */
+    uint32_t* rank;        /* S x 16 */
+    int32_t* resolved;     /* S x 16 */
+    int64_t* count;        /* S */
+    float* lower;          /* S x Q, after level 2 */
+    float* higher;
+    double* linear;
+} saev_latent_hist_targets;
+int64_t saev_latent_hist_workspace_bytes(int64_t n_entries, int64_t S);
+int saev_latent_hist_update(const int32_t* idx, const float* val, const int32_t* row_nnz, int64_t cap, const int64_t* row_ptr,
+                            const int32_t* indices, const float* data, int64_t nnz, const uint8_t* keep, int64_t n, int64_t S,
+                            const saev_latent_hist_state* state, void* workspace, int64_t workspace_bytes, void* stream);
+int saev_latent_hist_locate(const saev_latent_hist_state* state, const saev_latent_hist_targets* targets, int64_t S, void* stream);
 /* LATENT EDITS (the intervention of the reference's contrib/interactive_interp/semseg: set a latent, decode, add the SAE's error
  * back), context-free.  For an SAE x_hat = b_dec + sum_j f_j W_dec[j, :] and edits e = (latent l_e, target t_e(f)),
  *   x' = (x - x_hat) + x_hat_mod = x + sum_e c_e W_dec[l_e, :],   c_e = t_e(f_l) - f_l

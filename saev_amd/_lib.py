@@ -80,6 +80,21 @@ class SaevLatentTopKState(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("k", C.c_int32), ("top_val", C.c_void_p), ("top_row", C.c_void_p), ("top_cnt", C.c_void_p)]
 
 
+class SaevLatentHistState(C.Structure):
+    """include/saev_amd.h: saev_latent_hist_state (the caller's count table of one level; zero-initialised before the first update)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("level", C.c_int32), ("T", C.c_int32), ("reserved", C.c_int32), ("counts", C.c_void_p),
+                ("n_rows", C.c_void_p), ("prefix", C.c_void_p)]
+
+
+class SaevLatentHistTargets(C.Structure):
+    """include/saev_amd.h: saev_latent_hist_targets (the quantiles of saev_latent_hist_locate and what it leaves per target)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("Q", C.c_int32), ("over_rows", C.c_int32), ("reserved", C.c_int32), ("q", C.c_double * 8),
+                ("prefix", C.c_void_p), ("rank", C.c_void_p), ("resolved", C.c_void_p), ("count", C.c_void_p), ("lower", C.c_void_p),
+                ("higher", C.c_void_p), ("linear", C.c_void_p)]
+
+
 class SaevProbe1DCfg(C.Structure):
     """include/saev_amd.h: saev_probe1d_cfg (the solver's hyper-parameters, the reference's names)."""
 
@@ -216,6 +231,10 @@ _SIGNATURES = {
     "saev_latent_topk_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "saev_latent_topk_update": (C.c_int, [P, P, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int64, C.c_int64,
                                           C.POINTER(SaevLatentTopKState), P, C.c_int64, P]),
+    "saev_latent_hist_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "saev_latent_hist_update": (C.c_int, [P, P, P, C.c_int64, P, P, P, C.c_int64, P, C.c_int64, C.c_int64, C.POINTER(SaevLatentHistState), P,
+                                          C.c_int64, P]),
+    "saev_latent_hist_locate": (C.c_int, [C.POINTER(SaevLatentHistState), C.POINTER(SaevLatentHistTargets), C.c_int64, P]),
     "saev_probe1d_workspace_bytes": (C.c_int64, [C.c_int64] * 4),
     "saev_probe1d_layout_of": (C.c_int, [C.c_int64] * 4 + [C.POINTER(SaevProbe1DLayout)]),
     "saev_probe1d_prepare": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, C.c_int64, P]),

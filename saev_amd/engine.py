@@ -716,6 +716,239 @@ class LatentTopK:
                               counts=self.top_cnt.to(torch.int64).cpu())
 
 
+class _LatentHistStream:
+    """What LatentHist and LatentQuantiles share: one batch, in either form, into the count table ``self._state`` describes
+    (saev_latent_hist_update).  Counts are uint32 (held in int32 tensors): an accumulator offered 2^32 rows or more is refused."""
+
+    MAX_ROWS = 2**32
+    T_STRIDE = 16
+
+    def _init_stream(self, who: str, d_sae: int, device) -> None:
+        if d_sae < 1 or d_sae >= 2**31:
+            raise ValueError(f"{who}: unsupported d_sae {d_sae}")
+        self.device = _hip_device(who, device)
+        self.lib = _lib.load()
+        self.d_sae = d_sae
+        self.n_rows = torch.zeros(1, device=self.device, dtype=torch.int64)  # kept rows of the current pass, on the device
+        self._offered = 0
+        self._ws = None
+        self._no_codes = torch.zeros(1, device=self.device, dtype=torch.int32)  # stands in for the codes of a batch that has none
+
+    _keep = LatentTopK._keep
+
+    def _update(self, idx, val, row_nnz, cap: int, row_ptr, indices, data, nnz: int, keep, n: int) -> None:
+        if self._offered + n >= self.MAX_ROWS:
+            raise _lib.SaevError(f"saev_latent_hist_update: {self._offered + n} rows offered to one accumulator (uint32 counts: fewer than 2^32)")
+        need = int(self.lib.saev_latent_hist_workspace_bytes(n * cap if row_ptr is None else nnz, self.d_sae))
+        if need < 0:
+            raise _lib.SaevError("saev_latent_hist_update: more than 2^31 - 1 entries in one batch")
+        if self._ws is None:
+            self._ws = torch.empty(need, device=self.device, dtype=torch.uint8)
+        with torch.cuda.device(self.device):
+            rc = self.lib.saev_latent_hist_update(idx, val, row_nnz, cap, row_ptr, indices, data, nnz, _ptr(self._keep(keep, n)), n, self.d_sae,
+                                                  C.byref(self._state), _ptr(self._ws), self._ws.numel(), _stream())
+        _lib.check(self.lib, None, rc, "saev_latent_hist_update")
+        self._offered += n
+
+    def add(self, idx: torch.Tensor, val: torch.Tensor, row_nnz: torch.Tensor | None = None, keep: torch.Tensor | None = None) -> None:
+        """One batch of padded code rows: idx (n, cap) int32, val (n, cap) float32, row_nnz (n) int32 (None: full rows), keep (n) bool."""
+        if idx.ndim != 2:
+            raise ValueError(f"idx must be (n, cap), got {tuple(idx.shape)}")
+        n, cap = idx.shape
+        idx = _on(idx, torch.int32, (n, cap), "idx", self.device)
+        val = _on(val, torch.float32, (n, cap), "val", self.device)
+        row_nnz = _on(row_nnz, torch.int32, (n,), "row_nnz", self.device)
+        self._accepts()
+        if n == 0:
+            return
+        if cap == 0:  # rows without a slot are still rows
+            idx = val = self._no_codes
+        self._update(_ptr(idx), _ptr(val), _ptr(row_nnz), cap, None, None, None, 0, keep, n)
+
+    def add_csr(self, indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, keep: torch.Tensor | None = None) -> None:
+        """One CSR block on the device: indptr (n + 1) int64 starting at 0, indices (nnz) int32, data (nnz) float32."""
+        if indptr.ndim != 1 or indptr.numel() < 1:
+            raise ValueError(f"indptr must be a vector of n + 1 offsets, got {tuple(indptr.shape)}")
+        n, nnz = indptr.numel() - 1, indices.numel()
+        indptr, indices, data = _csr_on(indptr, indices, data, n, nnz, self.device)
+        self._accepts()
+        if n == 0:
+            return
+        if nnz == 0:
+            indices = data = self._no_codes
+        self._update(None, None, None, 0, _ptr(indptr), _ptr(indices), _ptr(data), nnz, keep, n)
+
+    def _accepts(self) -> None:
+        pass
+
+
+def _u32(t: torch.Tensor) -> torch.Tensor:
+    """uint32 counters held in an int32 tensor, as int64."""
+    return t.to(torch.int64) & 0xFFFFFFFF
+
+
+def hist_window(counts0: torch.Tensor, lo_exp: int = -16, hi_exp: int = 16):
+    """The octaves [2^lo_exp, 2^hi_exp) of level-0 counts (S, 4096), eight bins each: ``(counts, n_neg, edges)`` with counts int64
+    (S, 8 (hi_exp - lo_exp) + 2) -- column 0 the positive entries below the window, the last column those at or above it -- n_neg
+    int64 (S,) the negative entries, and edges float32 (8 (hi_exp - lo_exp) + 1), exactly 2^e (1 + i / 8)."""
+    if not -126 <= lo_exp < hi_exp <= 127:
+        raise ValueError(f"histogram: need -126 <= lo_exp < hi_exp <= 127, got {lo_exp}, {hi_exp}")
+    c = counts0 if counts0.dtype == torch.int64 else _u32(counts0)
+    lo, hi = 2048 + 8 * (lo_exp + 127), 2048 + 8 * (hi_exp + 127)
+    counts = torch.cat([c[:, 2048:lo].sum(1, keepdim=True), c[:, lo:hi], c[:, hi:].sum(1, keepdim=True)], dim=1)
+    bits = (torch.arange(lo, hi + 1, dtype=torch.int64) - 2048) << 20  # the float whose key opens the bin
+    return counts, c[:, :2048].sum(1), bits.to(torch.int32).view(torch.float32)
+
+
+class LatentHist(_LatentHistStream):
+    """Per-latent activation histogram over a stream of batches (include/saev_amd.h: LATENT HISTOGRAM): the level-0
+    count table ``counts0`` (S, 4096) of saev_latent_hist_update -- sign, exponent and three mantissa bits of every code, eight
+    bins to the octave -- and the kept rows ``n_rows``, both on the device.  Integer counts: exact, and the same for every order and
+    every split of the batches.  ``read`` and ``histogram`` are the device-to-host copies."""
+
+    def __init__(self, d_sae: int, device):
+        self._init_stream("LatentHist", d_sae, device)
+        if d_sae * 4096 >= 2**32 - 1:
+            raise ValueError(f"LatentHist: unsupported d_sae {d_sae} (the table holds fewer than 2^32 - 1 counters)")
+        self.counts0 = torch.zeros(d_sae, 4096, device=self.device, dtype=torch.int32)
+        self._state = _lib.SaevLatentHistState(struct_size=C.sizeof(_lib.SaevLatentHistState), level=0, T=0, counts=_ptr(self.counts0),
+                                               n_rows=_ptr(self.n_rows))
+
+    def zero_(self) -> "LatentHist":
+        self.counts0.zero_()
+        self.n_rows.zero_()
+        self._offered = 0
+        return self
+
+    def read(self) -> torch.Tensor:
+        """Host ``counts0`` (S, 4096) int64."""
+        return _u32(self.counts0).cpu()
+
+    def histogram(self, lo_exp: int = -16, hi_exp: int = 16):
+        """``hist_window`` of the table, merged on the device, on the host."""
+        counts, n_neg, edges = hist_window(_u32(self.counts0), lo_exp, hi_exp)
+        return counts.cpu(), n_neg.cpu(), edges
+
+
+@dataclasses.dataclass(frozen=True)
+class LatentQuantilesHost:
+    """What ``LatentQuantiles.result()`` brings back (CPU tensors)."""
+
+    lower: torch.Tensor   # (S, Q) float32: element floor(h) of the sorted multiset, h = (count - 1) q
+    higher: torch.Tensor  # (S, Q) float32: element ceil(h)
+    linear: torch.Tensor  # (S, Q) float64: lower + (h - floor(h)) (higher - lower)
+    count: torch.Tensor   # (S) int64: the size of the latent's multiset (0: NaN in all three)
+
+
+class LatentQuantiles(_LatentHistStream):
+    """Exact per-latent quantiles by a three-pass radix select over the bits of the codes (include/saev_amd.h: LATENT HISTOGRAM;
+    DESIGN.md 3.26).  Feed the SAME rows three times: ``add`` / ``add_csr`` the whole stream, ``next_pass()``, again, ``next_pass()``,
+    again, ``next_pass()``; then ``result()``.  ``over="rows"`` takes every kept row as an element (the rows a latent is silent on are
+    zeros, in closed form), ``over="entries"`` only the stored non-zero codes.  ``next_pass`` reads one device integer back -- the
+    kept rows of the pass, which must be those of the first -- and nothing else leaves the device before ``result``."""
+
+    MAX_Q = 8
+
+    def __init__(self, d_sae: int, q, device, over: str = "rows"):
+        q = [float(v) for v in (q if isinstance(q, (list, tuple)) else torch.as_tensor(q, dtype=torch.float64).reshape(-1).tolist())]
+        if not 1 <= len(q) <= self.MAX_Q:
+            raise ValueError(f"LatentQuantiles: unsupported number of quantiles {len(q)} (1 <= Q <= {self.MAX_Q})")
+        if not all(0.0 <= v <= 1.0 for v in q):
+            raise ValueError(f"LatentQuantiles: every q must lie in [0, 1], got {q}")
+        if over not in ("rows", "entries"):
+            raise ValueError(f"LatentQuantiles: over must be 'rows' or 'entries', got {over!r}")
+        self._init_stream("LatentQuantiles", d_sae, device)
+        self.q, self.over, self.Q, self.T = tuple(q), over, len(q), 2 * len(q)
+        if d_sae * max(4096, self.T * 1024) >= 2**32 - 1:
+            raise ValueError(f"LatentQuantiles: unsupported d_sae {d_sae} with {self.Q} quantiles (a table holds fewer than 2^32 - 1 counters)")
+        S, dev = d_sae, self.device
+        self.counts0 = torch.zeros(S, 4096, device=dev, dtype=torch.int32)
+        self.counts = None  # (S, T, 1024), levels 1 and 2: made when level 0 is located
+        self.prefix = torch.zeros(S, self.T_STRIDE, device=dev, dtype=torch.int32)
+        self.rank = torch.zeros(S, self.T_STRIDE, device=dev, dtype=torch.int32)
+        self.resolved = torch.zeros(S, self.T_STRIDE, device=dev, dtype=torch.int32)
+        self.count = torch.zeros(S, device=dev, dtype=torch.int64)
+        self.lower = torch.zeros(S, self.Q, device=dev, dtype=torch.float32)
+        self.higher = torch.zeros(S, self.Q, device=dev, dtype=torch.float32)
+        self.linear = torch.zeros(S, self.Q, device=dev, dtype=torch.float64)
+        self._targets = _lib.SaevLatentHistTargets(struct_size=C.sizeof(_lib.SaevLatentHistTargets), Q=self.Q, over_rows=int(over == "rows"),
+                                                   q=(C.c_double * 8)(*q), prefix=_ptr(self.prefix), rank=_ptr(self.rank),
+                                                   resolved=_ptr(self.resolved), count=_ptr(self.count), lower=_ptr(self.lower),
+                                                   higher=_ptr(self.higher), linear=_ptr(self.linear))
+        self.n_passes = 0
+        self._rows_first = None
+        self._arm(0)
+
+    def _arm(self, level: int) -> None:
+        table = self.counts0 if level == 0 else self.counts
+        self._state = _lib.SaevLatentHistState(struct_size=C.sizeof(_lib.SaevLatentHistState), level=level, T=0 if level == 0 else self.T,
+                                               counts=_ptr(table), n_rows=_ptr(self.n_rows), prefix=None if level == 0 else _ptr(self.prefix))
+
+    @property
+    def done(self) -> bool:
+        return self.n_passes == 3
+
+    def _accepts(self) -> None:
+        if self.done:
+            raise _lib.SaevError("LatentQuantiles: the three passes are done (read result(); a new selection needs a new object)")
+
+    def next_pass(self) -> None:
+        """Locates every target in the tables of the pass just fed, and arms the next level."""
+        self._accepts()
+        with torch.cuda.device(self.device):
+            rc = self.lib.saev_latent_hist_locate(C.byref(self._state), C.byref(self._targets), self.d_sae, _stream())
+        _lib.check(self.lib, None, rc, "saev_latent_hist_locate")
+        rows = int(self.n_rows.item())  # the one read-back of a pass
+        if self._rows_first is None:
+            self._rows_first = rows
+        elif rows != self._rows_first:
+            raise _lib.SaevError(f"LatentQuantiles: pass {self.n_passes + 1} was fed {rows} kept rows, the first pass {self._rows_first}")
+        self.n_passes += 1
+        if not self.done:
+            if self.counts is None:
+                self.counts0 = None  # level 0 is located: its table makes room for the refine table
+                self.counts = torch.zeros(self.d_sae, self.T, 1024, device=self.device, dtype=torch.int32)
+            else:
+                self.counts.zero_()
+            self.n_rows.zero_()
+            self._offered = 0
+            self._arm(self.n_passes)
+
+    def result(self) -> LatentQuantilesHost:
+        if not self.done:
+            raise _lib.SaevError(f"LatentQuantiles: {self.n_passes} of 3 passes done")
+        return LatentQuantilesHost(lower=self.lower.cpu(), higher=self.higher.cpu(), linear=self.linear.cpu(), count=self.count.cpu())
+
+
+def latent_quantiles(indptr, indices, data, n_rows: int, n_latents: int, q, *, over: str = "rows", chunk_rows: int = 2**20,
+                     device=None, hist: LatentHist | None = None) -> LatentQuantilesHost:
+    """The quantiles ``q`` of every column of a CSR matrix (n_rows, n_latents), on the host (numpy / torch CPU) or on the device:
+    the three passes of ``LatentQuantiles`` over row chunks of ``chunk_rows``.  ``hist`` also receives the chunks, once."""
+    if chunk_rows < 1:
+        raise ValueError(f"latent_quantiles: chunk_rows must be >= 1, got {chunk_rows}")
+    indptr, indices, data = (torch.as_tensor(a) for a in (indptr, indices, data))
+    if indptr.numel() != n_rows + 1:
+        raise ValueError(f"latent_quantiles: indptr must hold n_rows + 1 = {n_rows + 1} offsets, got {indptr.numel()}")
+    device = _hip_device("latent_quantiles", device if device is not None else indptr.device)
+    acc = LatentQuantiles(n_latents, q, device, over)
+    host_ptr = indptr.to(torch.int64).cpu()
+
+    def chunk(r0: int):  # (host data crosses to the device once a pass)
+        r1 = min(n_rows, r0 + chunk_rows)
+        a, b = int(host_ptr[r0]), int(host_ptr[r1])
+        return ((host_ptr[r0:r1 + 1] - a).to(device), indices[a:b].to(device=device, dtype=torch.int32),
+                data[a:b].to(device=device, dtype=torch.float32))
+
+    for level in range(3):
+        for r0 in range(0, n_rows, chunk_rows):
+            block = chunk(r0)
+            acc.add_csr(*block)
+            if level == 0 and hist is not None:
+                hist.add_csr(*block)
+        acc.next_pass()
+    return acc.result()
+
+
 @dataclasses.dataclass(frozen=True)
 class Probe1DHyper:
     """The reference's Sparse1DProbe hyper-parameters (include/saev_amd.h: saev_probe1d_cfg)."""

@@ -12,6 +12,10 @@ Writes under ``<run>/inference/<metadata hash>/``:
     top_tokens.pt      {"values" (k, d_sae) float32, "indices" (k, d_sae) int64, "counts" (d_sae,) int64}: per latent the k largest
                        activations and the global token rows (rows of token_acts.npz) they sit in, what the reference's
                        ``helpers.csr_topk(token_acts, k=k, axis=0)`` returns   (``worker_fn(cfg, top_k_tokens=k)`` only)
+    activation_hist.pt {"counts0" (d_sae, 4096) int32 (int64 once a count passes 2^31 - 1), "n_rows" int}: per latent the histogram
+                       of its non-zero activations over sign, exponent and three mantissa bits (engine.LatentHist;
+                       ``engine.hist_window`` cuts octaves out of it), and the kept tokens (rebuilt from token_acts.npz: its
+                       rows)                                                   (``worker_fn(cfg, activation_hist=True)`` only)
 
 The reference materialises the dense (B, d_sae) ``f_x`` per batch, copies it to the host and lets scipy compress it
 (inference.py:189-246).  Here the codes never leave their sparse form: the HIP encoder returns (idx, val) with
@@ -35,7 +39,7 @@ import torch
 
 from .. import disk, helpers, nn
 from ..data import Metadata, OrderedConfig, OrderedDataLoader
-from ..engine import BatchStats, LatentTopK
+from ..engine import BatchStats, LatentHist, LatentTopK
 from ..metrics import Metrics
 
 logger = logging.getLogger("inference.py")
@@ -123,12 +127,29 @@ def _top_tokens_current(path: pathlib.Path, k: int, d_sae: int) -> bool:
     return tuple(values.shape) == (k, d_sae)
 
 
+ACTIVATION_HIST = "activation_hist.pt"
+
+
+def _save_activation_hist(path: pathlib.Path, hist: LatentHist) -> None:
+    counts0 = hist.counts0  # uint32 counters in an int32 tensor: kept as int32 while every count fits, the file is half the size
+    torch.save({"counts0": hist.read() if bool((counts0 < 0).any()) else counts0.cpu(), "n_rows": int(hist.n_rows.item())}, path)
+
+
+def _activation_hist_current(path: pathlib.Path, d_sae: int) -> bool:
+    """Whether ``path`` holds the table of this many latents."""
+    return path.exists() and tuple(torch.load(path)["counts0"].shape) == (d_sae, 4096)
+
+
 @torch.inference_mode()
-def worker_fn(cfg: Config, *, top_k_tokens: int = 0):
+def worker_fn(cfg: Config, *, top_k_tokens: int = 0, activation_hist: bool = False):
     """``top_k_tokens`` = k > 0 also keeps, per latent, the k largest activations of the pass and their global token rows
     (engine.LatentTopK, fed from the codes on the device) and writes them as ``top_tokens.pt``.  When the pass is up to date, a
     ``top_tokens.pt`` that is missing or holds another k is rebuilt from ``token_acts.npz``.  0 keeps no lists; a pass that rewrites
-    ``token_acts.npz`` without them removes a ``top_tokens.pt`` left by an earlier pass, which would no longer describe it."""
+    ``token_acts.npz`` without them removes a ``top_tokens.pt`` left by an earlier pass, which would no longer describe it.
+
+    ``activation_hist`` also keeps every latent's activation histogram (engine.LatentHist, fed from the codes on the device) and writes
+    it as ``activation_hist.pt``, under the same policy: rebuilt from ``token_acts.npz`` when the pass is up to date and the file is
+    missing or describes another pass, removed by a pass that rewrites ``token_acts.npz`` without it."""
     if top_k_tokens < 0 or top_k_tokens > LatentTopK.MAX_K:
         raise ValueError(f"top_k_tokens must lie in [0, {LatentTopK.MAX_K}], got {top_k_tokens}")
     run = disk.Run(cfg.run)
@@ -137,6 +158,18 @@ def worker_fn(cfg: Config, *, top_k_tokens: int = 0):
     do, reason, fpaths = need_compute(cfg)
     logger.info(reason)
     if not do:
+        if activation_hist and fpaths.token_acts.exists():
+            token_acts = scipy.sparse.load_npz(fpaths.token_acts).tocsr()
+            if not _activation_hist_current(root / ACTIVATION_HIST, token_acts.shape[1]):
+                device = torch.device(cfg.device)
+                if device.type != "cuda":
+                    raise RuntimeError("saev_amd inference runs on a HIP device only (there is no CPU path)")
+                hist = LatentHist(token_acts.shape[1], device)
+                for r0 in range(0, token_acts.shape[0], 2**20):
+                    block = token_acts[r0:r0 + 2**20]
+                    hist.add_csr(torch.from_numpy(block.indptr.astype(np.int64)).to(device), torch.from_numpy(block.indices.astype(np.int32)).to(device),
+                                 torch.from_numpy(block.data.astype(np.float32)).to(device))
+                _save_activation_hist(root / ACTIVATION_HIST, hist)
         if top_k_tokens > 0 and fpaths.token_acts.exists():
             # the pass is up to date; lists that are missing, or were kept for another k, are selected from the saved codes
             token_acts = scipy.sparse.load_npz(fpaths.token_acts).tocsr()
@@ -170,6 +203,7 @@ def worker_fn(cfg: Config, *, top_k_tokens: int = 0):
     # counts and value sums -- from one kernel per batch, TopK or ReLU, masked or not (engine.BatchStats)
     acc = BatchStats(D, S, device, want=("scalars", "col_sum", "n_pos", "value_sum") if cfg.save else ("scalars", "col_sum"))
     top = LatentTopK(S, top_k_tokens, device) if top_k_tokens > 0 else None
+    hist = LatentHist(S, device) if activation_hist else None
     if cfg.save:
         distributions = np.zeros((loader.n_samples, cfg.n_dists), dtype=np.float32)
         csr_data: list[np.ndarray] = []
@@ -212,6 +246,11 @@ def worker_fn(cfg: Config, *, top_k_tokens: int = 0):
                     top.add(idx, val, row_nnz, mask, row_base=row_base)
                 else:
                     eng.add_latent_topk(top, mask, row_base=row_base)
+            if hist is not None:
+                if relu:
+                    hist.add(idx, val, row_nnz, mask)
+                else:
+                    hist.add(*eng.last_codes(b, x_hat=False)[:2], None, mask)
         if not cfg.save:
             continue
         if not relu:
@@ -242,6 +281,10 @@ def worker_fn(cfg: Config, *, top_k_tokens: int = 0):
         _save_top_tokens(root / TOP_TOKENS, lists.values, lists.indices, lists.counts)
     elif cfg.save:
         (root / TOP_TOKENS).unlink(missing_ok=True)  # lists of an earlier pass do not describe the token_acts.npz written below
+    if hist is not None:
+        _save_activation_hist(root / ACTIVATION_HIST, hist)
+    elif cfg.save:
+        (root / ACTIVATION_HIST).unlink(missing_ok=True)
     if cfg.save:
         counts = np.concatenate(csr_counts) if csr_counts else np.zeros(0, dtype=np.int64)
         indptr = np.zeros(counts.shape[0] + 1, dtype=np.int64)
@@ -269,7 +312,7 @@ def worker_fn(cfg: Config, *, top_k_tokens: int = 0):
     return metrics
 
 
-def main(cfgs: Config | list[Config], *, top_k_tokens: int = 0) -> int:
+def main(cfgs: Config | list[Config], *, top_k_tokens: int = 0, activation_hist: bool = False) -> int:
     """Run the configs one after another in this process (the reference can also submit them to Slurm,
     inference.py:288-364; cluster submission is outside this package)."""
     cfgs = [cfgs] if isinstance(cfgs, Config) else list(cfgs)
@@ -277,6 +320,6 @@ def main(cfgs: Config | list[Config], *, top_k_tokens: int = 0) -> int:
         if c.slurm_acct:
             raise NotImplementedError("Slurm submission is not part of saev_amd; run worker_fn on the node directly")
         logger.info("Running config %d/%d locally.", i, len(cfgs))
-        worker_fn(c, top_k_tokens=top_k_tokens)
+        worker_fn(c, top_k_tokens=top_k_tokens, activation_hist=activation_hist)
     logger.info("Jobs done.")
     return 0
