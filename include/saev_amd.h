@@ -73,7 +73,14 @@ typedef struct {
                                         (the k-th largest candidate found must reach every bound used for the row),
                                         with an automatic second launch on guaranteed bounds whenever a prediction
                                         fails; codes and values are the same either way (saev_bound_state reports z
-                                        and how often the second launch was needed).                                 */
+                                        and how often the second launch was needed);
+                                      2 guaranteed bounds, except in the streamed f16r training step of a plain TopK context
+                                        (saev_train_step on consecutive batches of one size): there a row's bound is
+                                        c * rho_lo * ||x_b - mu||, rho_lo the smallest ratio (exact k-th largest
+                                        pre-activation) / ||x_b - mu|| over the rows of the previous step and c a safety
+                                        factor steered on the device, verified and repeated like mode 1.  A first step, a step
+                                        after saev_params_touched, another batch size or any other forward in between takes
+                                        the guaranteed bounds.                                                       */
     int32_t max_backward_rows;     /* 0 = max_batch.  Larger: the backward may cover that many rows (saev_backward_override:
                                       the rows of ALL data-parallel ranks); sizes only the backward's pair order, slice-major
                                       copies and partial rows -- the forward's buffers (candidate lists, dense fallback,
@@ -1253,13 +1260,22 @@ const float* saev_last_x_hat(saev_ctx* ctx);
  * n_rows must equal the batch of the last saev_step_forward (anything else is SAEV_INVALID_ARG). */
 int saev_copy_last(saev_ctx* ctx, int32_t n_rows, int32_t* idx_out, float* val_out, float* x_hat_out, void* stream);
 
-/* State of the predicted-bound mechanism (saev_cfg.bound_mode = 1), read back from the device (synchronises `stream`):
- * the current z, how many fused-encoder launches used predicted bounds and how many of those had to be repeated with
- * guaranteed bounds, and the mean candidate-list length of the last launch. */
+/* State of the predicted-bound mechanism (saev_cfg.bound_mode = 1 or 2), read back from the device (synchronises `stream`):
+ * the current z (mode 2: the safety factor c, 0.5 .. 0.95), how many fused-encoder launches used predicted bounds and how many
+ * of those had to be repeated with guaranteed bounds, and the mean candidate-list length of the last launch (mode 2: of the
+ * last step that collected ratios, predicted or not).  Mode 2 counts a launch only when the prediction was really used: steps
+ * that take the guaranteed bounds -- see bound_mode -- leave `launches` and `repeats` alone. */
 int saev_bound_state(saev_ctx* ctx, float* z, int64_t* launches, int64_t* repeats, float* mean_candidates, void* stream);
+/* bound_mode 2, read back likewise: rho_lo, the smallest ratio (exact k-th largest pre-activation) / ||x_b - mu|| over the rows of
+ * the last step that left one (NaN: none -- no such step yet, or it ended on the dense route), and how many steps of a pause of
+ * the prediction are still to come on the device (0: not paused).  NaN and 0 in the other modes. */
+int saev_bound_ratio(saev_ctx* ctx, float* rho_lo, int64_t* pause_left, void* stream);
 
 /* Timing hooks for bench.py: wall duration in ms of the encoder kernel of the last step, measured
- * with HIP events on `stream` (call after the stream has been synchronised). */
+ * with HIP events on `stream` (call after the stream has been synchronised).  With bound_mode 2 the events bracket the
+ * step's FIRST fused-encoder launch: the predicted one in a predicting step, the guaranteed one in every other step (a pause
+ * included).  On a step whose prediction failed the guaranteed repeat is a second encoder launch that is not timed, and on the
+ * few steps the device holds back before the host has seen a pause the first launch exits at once: the figure is too small there. */
 int saev_enable_kernel_timing(saev_ctx* ctx, int32_t enable);
 float saev_last_encoder_ms(saev_ctx* ctx);
 

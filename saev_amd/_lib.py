@@ -277,6 +277,7 @@ _SIGNATURES = {
     "saev_last_x_hat": (P, [P]),
     "saev_copy_last": (C.c_int, [P, C.c_int32, P, P, P, P]),
     "saev_bound_state": (C.c_int, [P, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_float), P]),
+    "saev_bound_ratio": (C.c_int, [P, C.POINTER(C.c_float), C.POINTER(C.c_int64), P]),
     "saev_enable_kernel_timing": (C.c_int, [P, C.c_int32]),
     "saev_last_encoder_ms": (C.c_float, [P]),
 }

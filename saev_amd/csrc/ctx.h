@@ -173,6 +173,14 @@ struct saev_ctx {
     int rs_lat_range = 0, rs_n_ranges = 0;
     int32_t* tau_max = nullptr;   // (max_batch) largest predicted bound used per row
     float* heur_state = nullptr;  // [0] z  [1] failed predictions  [2] predicted-bound launches  [3] mean list length
+    // norm-predicted bounds (bound_mode 2; kernels.h: RhoArgs): controller state, partials of the ratio reduction, the rows' bounds
+    // and the exact k-th largest values of the last final select
+    float *rho_state = nullptr, *rho_scratch = nullptr, *row_bound = nullptr, *kth_val = nullptr;
+    bool rho_valid = false;       // the previous forward was a streamed training step of this mode that left rho_lo for this one
+    int rho_n = 0;                // ... over this many rows
+    int rho_step = 0;             // this forward: 0 not involved, 1 collects the ratios only, 2 predicts as well
+    int32_t rho_serial_seen = 0;  // the controller's last pause the host has taken note of (pinned words stale_host[4], [5]) ...
+    int rho_pause_left = 0;       // ... and how many of its steps are still to come
     float *f16r_scales = nullptr, *mu = nullptr, *xnorm = nullptr, *b_shift = nullptr, *dot_part = nullptr, *xabs_part = nullptr,
           *sq_part = nullptr, *wmax_prev = nullptr;
     bool wmax_known = false;

@@ -185,11 +185,12 @@ int create_context(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_ba
         if (c->cfg.encoder_mode == SAEV_ENCODER_F16R) { A(dot_part, (size_t)2 * (c->Dp / 32) * c->S_pad); A(sq_part, (size_t)2 * (c->Dp / 32) * c->S_pad); A(wmax_prev, 1); }
         if (c->cfg.encoder_mode == SAEV_ENCODER_F16R) { A(surv_idx, MB * REFINE_CAP); A(surv_val, MB * REFINE_CAP); A(surv_cnt, MB); }
     }
-    c->stream_ok = c->fwd_slices && c->cfg.bound_mode == 0 && c->dbg.prep_route == 0 && D % 32 == 0 && c->Dp == (int)D;
+    c->stream_ok = c->fwd_slices && c->cfg.bound_mode != 1 && c->dbg.prep_route == 0 && D % 32 == 0 && c->Dp == (int)D;
     if (c->stream_ok) {
         A(WeS, S * D); A(xn_part, (size_t)(D / 32) * c->MB_pad * 2);
         A(amax_part, (size_t)(c->MB_pad / 256) * (D / 32)); A(cmax_part, (size_t)(c->MB_pad / 256) * (D / 32)); A(b_seen, S);
         A(mu_keep, D); A(xside_keep, 4);
+        if (c->cfg.bound_mode == 2) { A(rho_state, 16); A(rho_scratch, 32); A(row_bound, MB); A(kth_val, MB); }
     }
     if (c->stream_ok || c->cfg.encoder_mode == SAEV_ENCODER_BF16) A(wchk, (size_t)2 * ((S + 255) / 256) * ((D + 31) / 32));
     A(toks, S); A(fired, S); A(dead, S); A(flags, 16); A(upper, 1); A(stats, 1);
@@ -218,7 +219,7 @@ int create_context(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_ba
         if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess &&
             hipHostGetDevicePointer(reinterpret_cast<void**>(&c->stale_dev), hp, 0) == hipSuccess) {
             c->stale_host = static_cast<int32_t*>(hp);
-            c->stale_host[0] = 0; c->stale_host[1] = 0;
+            for (int i = 0; i < 16; ++i) c->stale_host[i] = 0;  // ([4], [5]: the pauses of the norm-predicted bounds, RhoArgs::host)
         } else {
             if (hp) hipHostFree(hp);
             c->stale_host = nullptr; c->stale_dev = nullptr;  // (the device-side part of the check still works)
@@ -231,6 +232,12 @@ int create_context(const saev_cfg* cfg, const saev_debug_cfg* dbg, const saev_ba
     {
         const float init[8] = {2.6f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // z starts where a Gaussian row of 32 k latents has ~8 k values above its bound
         hipMemcpy(c->heur_state, init, sizeof(init), hipMemcpyHostToDevice);
+    }
+    if (c->rho_state) {
+        // c starts at 0.9; [6] = NaN: no ratio yet (kernels.h: RhoArgs)
+        const float init[16] = {0.9f, 0.f, 0.f, 0.f, 0.f, 0.f, __builtin_nanf(""), 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        hipMemcpy(c->rho_state, init, sizeof(init), hipMemcpyHostToDevice);
+        hipMemset(c->rho_scratch, 0, 32 * sizeof(float));
     }
     hipMemset(c->rowstats, 0, MB * sizeof(RowStats));
     if (c->xs) hipMemset(c->xs, 0, (size_t)c->MB_pad * 2 * c->Dp * sizeof(_Float16));
@@ -476,12 +483,26 @@ int saev_bound_state(saev_ctx* c, float* z, int64_t* launches, int64_t* repeats,
     if (!c) return SAEV_INVALID_ARG;
     float h[4] = {0.f, 0.f, 0.f, 0.f};
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(c, hipMemcpyAsync(h, c->heur_state, sizeof(h), hipMemcpyDeviceToHost, s));
+    // (the norm-predicted bounds keep the same four figures in their own state: [0] is their safety factor c)
+    HIPCHK(c, hipMemcpyAsync(h, c->rho_state != nullptr ? c->rho_state : c->heur_state, sizeof(h), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (z) *z = h[0];
     if (repeats) *repeats = (int64_t)h[1];
     if (launches) *launches = (int64_t)h[2];
     if (mean_candidates) *mean_candidates = h[3];
+    return SAEV_OK;
+}
+
+int saev_bound_ratio(saev_ctx* c, float* rho_lo, int64_t* pause_left, void* stream) {
+    if (!c) return SAEV_INVALID_ARG;
+    float h[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, __builtin_nanf(""), 0.f};
+    hipStream_t s = (hipStream_t)stream;
+    if (c->rho_state != nullptr) {
+        HIPCHK(c, hipMemcpyAsync(h, c->rho_state, sizeof(h), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    if (rho_lo) *rho_lo = h[6];
+    if (pause_left) *pause_left = (int64_t)h[5];
     return SAEV_OK;
 }
 

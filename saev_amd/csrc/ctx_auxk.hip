@@ -339,8 +339,13 @@ int saev_step_dead(saev_ctx* c, int64_t n_rows_global, void* stream) {
     if (c->stats_pending) {
         c->stats_pending = false;
         d.dead_list = c->cfg.k_aux > 0 ? c->dead_list : nullptr;
+        RhoArgs rho{};  // (a step of the norm-predicted bounds: this launch reduces its ratios and steers the safety factor)
+        if (c->rho_step != 0) {
+            rho.kth = c->kth_val; rho.xnorm = c->xnorm; rho.state = c->rho_state; rho.flags = c->flags; rho.scratch = c->rho_scratch;
+            rho.k = c->cfg.top_k; rho.host = c->stale_dev != nullptr ? c->stale_dev + 4 : nullptr;
+        }
         HIPCHK(c, launch_stats_dead(c->rowstats, c->n_last, c->cfg.d_model, c->P_last, c->cfg.alpha, c->upper_c, c->flags + 2, c->stats,
-                                    c->stats_scratch, c->stats_lists ? c->cand_cnt : nullptr, CAND_CAP, d, s));
+                                    c->stats_scratch, c->stats_lists ? c->cand_cnt : nullptr, CAND_CAP, d, s, c->rho_step != 0 ? &rho : nullptr));
         c->dead_list_ready = d.dead_list != nullptr;
     } else {
         HIPCHK(c, launch_dead_update(d, s));

@@ -126,7 +126,7 @@ static int prepare_dense_scaled(saev_ctx* c, const float* x, int n, const float*
 }
 
 static int run_encoder(saev_ctx* c, const float* x, int n, int epi, float* h_out, const int32_t* flag, int when,
-                       hipStream_t s, bool predicted = false, const float* x_scale = nullptr) {
+                       hipStream_t s, bool predicted = false, const float* x_scale = nullptr, bool norm_bounds = false) {
     // F16R: only the TopK pass is approximate-then-refined; a dense h must be exact, so it comes from the fp32 kernel
     const bool f16r = c->cfg.encoder_mode == SAEV_ENCODER_F16R;
     if (c->cfg.encoder_mode != SAEV_ENCODER_F32 && !(f16r && epi == EPI_DENSE)) {
@@ -145,6 +145,7 @@ static int run_encoder(saev_ctx* c, const float* x, int n, int epi, float* h_out
         a.cand_cap = CAND_CAP; a.cand_stride = CAND_STRIDE;
         a.enable_flag = flag; a.enable_when = when;
         if (predicted) { a.heur_z = c->heur_state; a.tau_max = c->tau_max; }
+        if (norm_bounds) a.row_bound = c->row_bound;  // (pre_encode2_kernel has formed them, and the keys the select stage verifies)
         // the 64-group variant (32 < k <= 64, e.g. 82 k latents at k = 64) refreshes on every tile: with twice the codes
         // per row and many more tiles per workgroup its lists would outgrow their 4 096 entries otherwise
         a.refresh_first = 8;
@@ -217,7 +218,7 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
     const int K = c->cfg.top_k;
     int32_t* need_dense = c->flags + 1;
     const bool f16r_mode = c->cfg.encoder_mode == SAEV_ENCODER_F16R;
-    const bool predict_mode = fused_supported(c->cfg) && c->cfg.bound_mode != 0 && c->cfg.encoder_mode != SAEV_ENCODER_F32 &&
+    const bool predict_mode = fused_supported(c->cfg) && c->cfg.bound_mode == 1 && c->cfg.encoder_mode != SAEV_ENCODER_F32 &&
                               f16_ngroups(c) == 32;
     const bool one_launch_pre = fused_supported(c->cfg) && !predict_mode;  // margins + encoder state + list flags in one launch
     if (c->follow_stream) {
@@ -271,6 +272,7 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
                     HIPCHK(c, launch_refine_exact(sc, s));
                 }
                 sc.row_margin = nullptr; sc.tau_max = nullptr;
+                if (c->rho_step != 0) sc.kth_out = c->kth_val;  // (the exact k-th largest values: the next step's bounds scale from them)
                 sc.cand_cnt = c->surv_cnt; sc.cand_val = c->surv_val; sc.cand_idx = c->surv_idx; sc.cand_cap = REFINE_CAP; sc.cand_stride = REFINE_CAP;
             }
             HIPCHK(c, launch_select_cand(sc, s));
@@ -279,7 +281,7 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
         // Predicted bounds (gemm_encode_f16x3.hip, heur_z) for the fp16-image encoders with k <= 32: first a launch whose row
         // bounds are a prediction, verified by the select stage; only if that fails anywhere -- flag `bad1` -- the launch
         // with guaranteed bounds, which is otherwise skipped on the device (every kernel of it exits at once).
-        const bool predict = c->cfg.bound_mode != 0 && ng == 32 && c->cfg.encoder_mode != SAEV_ENCODER_F32;
+        const bool predict = c->cfg.bound_mode == 1 && ng == 32 && c->cfg.encoder_mode != SAEV_ENCODER_F32;
         int32_t *bad1 = c->flags + 9, *run2 = c->flags + 10, *gate = c->flags + 11;
         if (predict) {
             HIPCHK(c, launch_heur_gate(c->heur_state, pre_flag, gate, s));  // gate: no prediction this time
@@ -325,6 +327,8 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
                 pe.amax_part = c->amax_part; pe.cmax_part = c->cmax_part; pe.n_img = ((n + 255) / 256) * (D_ / 32);
                 pe.upper = c->upper; pe.stats = c->stats; pe.stale = c->flags + 12; pe.stale_host = c->stale_dev;
                 pe.xside_keep = c->followers.empty() ? nullptr : c->xside_keep;
+                pe.rho_mode = c->rho_step; pe.rho_state = c->rho_state; pe.row_bound = c->row_bound; pe.tau_max = c->tau_max;
+                pe.rho_bad = bad1; pe.rho_gate = gate;
                 HIPCHK(c, launch_pre_encode2(pe, s));
                 if (c->train_fused) c->mu_serial++;
             } else
@@ -332,11 +336,34 @@ static int encode_topk_impl(saev_ctx* c, const float* x, int n, int32_t* idx_out
                                         c->wnorm_scratch, (S_ + 255) / 256, f16r_mode ? scl(c) : nullptr, const_cast<int32_t*>(pre_flag),
                                         c->wmax_prev, c->row_margin, c->flags + 1, s));
             timing_begin(c, s);  // the events bracket the encoder kernel alone
-            int rc = run_encoder(c, x, n, EPI_TOPK, nullptr, pre_flag, 0, s);
-            if (rc != SAEV_OK) return rc;
-            timing_end(c, s);
-            rc = select_stage(need_dense, 0, need_dense, nullptr, c->flags + 1, pre_flag);
-            if (rc != SAEV_OK) return rc;
+            if (c->stream_step && c->rho_step == 2) {
+                // Norm-predicted bounds: pre_encode2_kernel has formed the rows' bounds from the previous step's ratios
+                // and set `gate` (0: use them).  The select stage verifies them; if a row's k-th largest candidate misses its bound, a
+                // list overflows or the gate is closed -- flag `bad1` -- the launch with guaranteed bounds follows, which is otherwise
+                // left on the device (every kernel of it exits at once).  Its encoder runs on `run_enc` = bad1 and not the step's
+                // force-dense flag: a step whose images are unusable goes straight to the dense route, as it always did.
+                // (A pause the controller decides on reaches the host through a pinned word -- saev_step_forward -- and the
+                // paused steps take the plain branch below: this one then costs the device-gated steps in between only.)
+                int32_t* const run_enc = c->flags + 14;
+                int rc = run_encoder(c, x, n, EPI_TOPK, nullptr, gate, 0, s, false, nullptr, true);
+                if (rc != SAEV_OK) return rc;
+                timing_end(c, s);
+                rc = select_stage(bad1, 0, bad1, c->tau_max, bad1, gate);
+                if (rc != SAEV_OK) return rc;
+                HIPCHK(c, launch_repeat_init(c->cand_cnt, n, c->gmax, ng * c->gmax_stride, bad1, pre_flag, run_enc, s));
+                rc = run_encoder(c, x, n, EPI_TOPK, nullptr, run_enc, 1, s);
+                if (rc != SAEV_OK) return rc;
+                HIPCHK(c, launch_overflow_check(c->cand_cnt, n, CAND_CAP, pre_flag, need_dense, c->flags + 2, c->flags + 3, s, need_dense,
+                                                run2, nullptr, bad1));
+                rc = select_stage(run2, 1, need_dense, nullptr, c->flags + 1, run2);
+                if (rc != SAEV_OK) return rc;
+            } else {
+                int rc = run_encoder(c, x, n, EPI_TOPK, nullptr, pre_flag, 0, s);
+                if (rc != SAEV_OK) return rc;
+                timing_end(c, s);
+                rc = select_stage(need_dense, 0, need_dense, nullptr, c->flags + 1, pre_flag);
+                if (rc != SAEV_OK) return rc;
+            }
         }
     } else {
         HIPCHK(c, launch_init_i32(need_dense, 1, 1, s));
@@ -374,6 +401,7 @@ int saev_encode_topk(saev_ctx* c, const float* x, int32_t n, int32_t* idx_out, f
     // launches would also clear the step's statistics and max |x|, which are not this call's to touch.
     c->stream_step = false;
     c->follow_stream = false;
+    c->rho_step = 0; c->rho_valid = false;  // (norm-predicted bounds belong to consecutive training steps)
     return encode_topk_impl(c, x, n, idx_out, val_out, c->flags, s);
 }
 
@@ -615,6 +643,27 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
     c->follow_stream = borrowed && c->borrow_streamed && c->stream_ok && c->wimg_fresh && c->wimg_mu_serial == c->leader->fwd_mu_serial &&
                        c->wenc_ready == nullptr && c->fwd_step && c->cfg.encoder_mode == SAEV_ENCODER_F16R;
     c->fwd_reused_wimg = c->stream_step || c->follow_stream;  // (the bf16 encoder decides in prepare_encoder)
+    {
+        // Norm-predicted bounds (bound_mode 2): for the streamed training step of a plain TopK context on its own.  Such a step
+        // leaves the smallest ratio of its rows for the next one; the next one predicts if nothing else came in between (another kind
+        // of forward, a full preparation -- parameters announced as touched, a new centre --, another batch size).
+        const bool rho_mode = c->cfg.bound_mode == 2 && c->rho_state != nullptr && c->stream_step && !borrowed && !btk && training &&
+                              c->train_fused && c->P == 1 && c->followers.empty() && c->cfg.encoder_mode == SAEV_ENCODER_F16R &&
+                              fused_supported(c->cfg) && f16_ngroups(c) == 32;
+        // (a pause the device-side controller has decided on -- tail.hip: rho_controller -- arrives in two pinned words, serial and
+        // length, without a synchronisation; until the host has seen it the device's own gate holds the prediction back.  A paused
+        // step is a plain guaranteed step that leaves its ratios: none of the repeat's predicated launches)
+        if (rho_mode && c->stale_host != nullptr) {
+            const volatile int32_t* hw = c->stale_host + 4;
+            const int32_t serial = hw[0];
+            if (serial != c->rho_serial_seen) { c->rho_serial_seen = serial; c->rho_pause_left = hw[1]; }
+        }
+        const bool paused = rho_mode && c->rho_pause_left > 0;
+        if (paused) c->rho_pause_left--;
+        c->rho_step = rho_mode ? ((c->rho_valid && c->rho_n == n && !paused) ? 2 : 1) : 0;
+        c->rho_valid = rho_mode;
+        c->rho_n = n;
+    }
     if (c->gather_pool != nullptr && !c->stream_step)  // (the batch as a contiguous matrix first: every other route reads x itself)
         HIPCHK(c, launch_gather_rows(c->gather_pool, c->gather_rows, n, D, const_cast<float*>(x), s));
     if (c->stream_step) {
@@ -714,7 +763,7 @@ int saev_step_forward(saev_ctx* c, const float* x, int32_t n, int64_t n_rows_glo
     for (int p = 0; p < c->P; ++p) c->cuts_last[p] = c->cuts[p];  // a later saev_set_prefixes must not reach this step's backward
     // (list statistics from the candidate counters themselves unless the fused encoder is out of play or predicts bounds,
     // where overflow_check_kernel leaves them in flags[2..3])
-    const bool lists = !btk && fused_supported(c->cfg) && !(c->cfg.bound_mode != 0 && c->cfg.encoder_mode != SAEV_ENCODER_F32 && f16_ngroups(c) == 32);
+    const bool lists = !btk && fused_supported(c->cfg) && !(c->cfg.bound_mode == 1 && c->cfg.encoder_mode != SAEV_ENCODER_F32 && f16_ngroups(c) == 32);
     c->stats_pending = false;
     if (c->train_fused && training) {  // (saev_train_step: the tracker update that follows takes this reduction into its launch)
         c->stats_pending = true;

@@ -75,6 +75,7 @@ __device__ __forceinline__ f32x16 mfma1(half8 a, half8 b, f32x16 c) {
 // v_mfma_f32_32x32x16_{bf16,f16} per block, fp32 accumulate; everything after the contraction is identical.  AR = 2
 // is the first pass of SAEV_ENCODER_F16R: its pre-activations carry a bounded rounding error, the candidate cut is
 // lowered by a per-row margin (a.row_margin) and select.hip recomputes the survivors exactly in fp32.
+// encode_m16_kernel<2, 0>: row bounds given by the caller (EncodeF16Args::row_bound), no bound phase.
 // HEUR: predicted row bounds (EncodeF16Args::heur_z) -- its own instantiation, so that the guaranteed-bound kernel's
 // register allocation is not disturbed by code it never runs.
 template <int EPI, int NG, int AR, bool HEUR = false>
@@ -768,6 +769,15 @@ __global__ __launch_bounds__(HTHREADS, 2) void encode_m16_kernel(EncodeF16Args a
         stage_kstep(0, st_begin * HTS, kmap(0));
         if (nks > 1) stage_kstep(1, st_begin * HTS, kmap(1));
     }
+    // NG == 0: the rows' bounds come from outside (EncodeF16Args::row_bound), one load per workgroup; no bound phase below
+    float tau_row[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (NG == 0) {
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) {
+            const int b = b0 + wb * 64 + jb * 16 + l15;
+            tau_row[jb] = (b < B) ? fmaxf(a.row_bound[b], -3.0e38f) - a.row_margin[b] : 3.0e38f;
+        }
+    }
 
     for (int st = st_begin; st < st_end; ++st) {
         const int s0 = st * HTS;
@@ -973,7 +983,7 @@ __global__ __launch_bounds__(HTHREADS, 2) void encode_m16_kernel(EncodeF16Args a
 #undef GPTR
                 __syncthreads();
             }
-        } else if (refresh) {
+        } else if (NG != 0 && refresh) {
             // group maxima of this tile: group = (sb & 1) * 16 + 4 * kg + e
 #pragma unroll
             for (int jb = 0; jb < 4; ++jb) {
@@ -1082,8 +1092,13 @@ __global__ __launch_bounds__(HTHREADS, 2) void encode_m16_kernel(EncodeF16Args a
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb) {
             const int b = b0 + wb * 64 + jb * 16 + l15;
-            float tau = fmaxf(key2f(sm.tau_key[wb * 64 + jb * 16 + l15]), -3.0e38f);
-            if (a.row_margin != nullptr) tau -= (b < B) ? a.row_margin[b] : 0.f;
+            float tau;
+            if constexpr (NG == 0) {
+                tau = tau_row[jb];
+            } else {
+                tau = fmaxf(key2f(sm.tau_key[wb * 64 + jb * 16 + l15]), -3.0e38f);
+                if (a.row_margin != nullptr) tau -= (b < B) ? a.row_margin[b] : 0.f;
+            }
             uint32_t m = 0;  // bit 31 - i: value i = 4 * sb + e reaches the bound
 #pragma unroll
             for (int sb = 0; sb < 8; ++sb)
@@ -1148,7 +1163,8 @@ hipError_t launch_encode_f16x3(const EncodeF16Args& a, int epi, hipStream_t stre
     const size_t smem = sizeof(HSmem);
     static bool attr_set = false;
     if (!attr_set) {
-        const void* fns[12] = {reinterpret_cast<const void*>(&encode_m16_kernel<1>),
+        const void* fns[13] = {reinterpret_cast<const void*>(&encode_m16_kernel<1>),
+                              reinterpret_cast<const void*>(&encode_m16_kernel<2, 0>),
                               reinterpret_cast<const void*>(&encode_m16_kernel<2>),
                               reinterpret_cast<const void*>(&encode_m16_kernel<1, 64>),
                               reinterpret_cast<const void*>(&encode_m16_kernel<2, 64>),
@@ -1174,6 +1190,10 @@ hipError_t launch_encode_f16x3(const EncodeF16Args& a, int epi, hipStream_t stre
         if (a.arith == 1) LAUNCH_ENC(EPI_DENSE, 32, 1);
         else if (a.arith == 2) LAUNCH_ENC(EPI_DENSE, 32, 2);
         else LAUNCH_ENC(EPI_DENSE, 32, 0);
+    } else if (a.ngroups <= 32 && a.row_bound != nullptr) {
+        // bounds from outside (norm-predicted): f16r only, its own instantiation without a bound phase
+        if (a.arith != 2 || a.row_margin == nullptr) return hipErrorInvalidValue;
+        LAUNCH_M16(2, 0);
     } else if (a.ngroups <= 32 && a.heur_z != nullptr) {
         if (a.arith == 1) LAUNCH_ENC(EPI_TOPK, 32, 1, true);
         else if (a.arith == 2) LAUNCH_ENC(EPI_TOPK, 32, 2, true);

@@ -52,6 +52,11 @@ struct SelectDenseArgs {
                            // that is rarely armed then retires in one round of workgroups); 0: one workgroup per row
 };
 hipError_t launch_select_dense(const SelectDenseArgs& a, hipStream_t stream);
+// The repeat of a step whose predicted bounds failed (*bad != 0): candidate counters and group maxima back to their initial state,
+// *run_enc = the guaranteed encoder is to run (bad and not the step's force-dense flag).  Unarmed: *run_enc = 0, nothing else.
+// One round of workgroups that walk the entries.
+hipError_t launch_repeat_init(int32_t* cand_cnt, int n_rows, int32_t* gmax, int n_gmax, const int32_t* bad, const int32_t* pre_flag,
+                              int32_t* run_enc, hipStream_t stream);
 
 struct SelectCandArgs {
     const int32_t* cand_cnt;
@@ -92,6 +97,9 @@ struct SelectCandArgs {
     const float* sum_bias;
     int sum_n;
     size_t sum_plane;
+    // optional (a final cut on exact values): kth_out[row] = the row's k-th largest value, NaN for a row with fewer than k entries
+    // (what the next step's norm-predicted bounds are scaled from: RhoArgs)
+    float* kth_out;
 };
 hipError_t launch_refine_exact(const SelectCandArgs& a, hipStream_t stream);
 constexpr int REFINE_CAP = 512;
@@ -432,9 +440,26 @@ struct DeadArgs {
 };
 hipError_t launch_dead_update(const DeadArgs& a, hipStream_t stream);
 // launch_stats_reduce (with_aux = 0) and launch_dead_update in one launch (a fused train step: the two meet nowhere)
+// Norm-predicted TopK bounds: bound_b = c * rho_lo * ||x_b - mu||, rho_lo = the smallest ratio (exact k-th
+// largest pre-activation) / ||x_b - mu|| over the rows of the PREVIOUS step.  The final select leaves the k-th largest values
+// (SelectCandArgs::kth_out), the statistics launch of the step reduces the ratios and steers c, pre_encode2_kernel of the next step
+// forms the bounds.  state: [0] c  [1] failed predictions  [2] predicted launches  [3] mean list length of the last launch
+// [4] steps in a row that did not pay  [5] launches left without prediction  [6] rho_lo for the next step (NaN: none)
+// [7] how often prediction has been switched off lately (sets the length of the next pause)  [8] paying steps in a row
+// [9] pauses so far (the serial the host sees)
+struct RhoArgs {
+    const float* kth;       // (n_rows) or NULL: nothing to do
+    const float* xnorm;     // (2 n_rows): [2 b] = ||x_b - mu||
+    float* state;           // (16)
+    const int32_t* flags;   // the context's flag block: [1] need_dense, [9] prediction failed (or was not tried), [11] gate (0: predicted,
+                            // 1: switched off by the controller, 2: no prediction asked for)
+    float* scratch;         // (32) per-workgroup partials
+    int k;
+    int32_t* host;          // optional, pinned: [0] serial of the last pause the controller decided on, [1] its length in steps
+};
 hipError_t launch_stats_dead(const RowStats* rs, int n_rows, int D, int P, float alpha, const float* upper, const int32_t* n_overflow,
                              saev_step_stats* stats, double* scratch, const int32_t* cand_cnt, int cand_cap, const DeadArgs& d,
-                             hipStream_t stream);
+                             hipStream_t stream, const RhoArgs* rho = nullptr);
 hipError_t launch_absmax(const float* x, long n, float* out_zeroed, hipStream_t stream);
 hipError_t launch_gather_rows(const float* pool, const int64_t* rows, int n_rows, int D, float* out, hipStream_t stream);
 hipError_t launch_scatter_dense(const int32_t* idx, const float* val, int n_rows, int k, int stride, int S, float* f,
@@ -478,6 +503,9 @@ struct EncodeF16Args {
     // INT32_MIN, receives the largest bound used for each row (the select stage verifies the prediction against it)
     const float* heur_z;
     int32_t* tau_max;
+    // EPI_TOPK, ngroups == 32, arith == 2: row bounds given from outside (n_rows; pre_encode2_kernel's norm-predicted bounds, which
+    // also fills tau_max itself).  The kernel keeps everything >= row_bound - row_margin and has no bound phase at all.
+    const float* row_bound;
     // EPI_TOPK: the guaranteed bound of a row is refreshed on a workgroup's first `refresh_first` tiles and on every
     // `refresh_every`-th (a power of two) after that
     int refresh_first, refresh_every;
@@ -555,6 +583,9 @@ struct PreEncode2Args {
     int32_t* stale; int32_t* stale_host;     // XprepArgs::stale (consumed and cleared here); optional pinned word the host polls
     float* xside_keep;                       // optional: [1] = 1 when this step's x images are unusable (XprepArgs::xside_keep)
     saev_step_stats* stats;                  // zeroed
+    // norm-predicted bounds (RhoArgs): rho_mode 0 none; 1 no prediction this step (gate word = 2); 2 predict unless the controller's
+    // state says otherwise.  Writes row_bound / tau_max (n_rows) and the flag words bad (flags[9]) and gate (flags[11]).
+    int rho_mode; const float* rho_state; float* row_bound; int32_t* tau_max; int32_t* rho_bad; int32_t* rho_gate;
     int nb_rows;                             // (set by the launcher)
 };
 hipError_t launch_pre_encode2(PreEncode2Args a, hipStream_t stream);

@@ -276,6 +276,7 @@ __device__ __forceinline__ void select_cand_row(const SelectCandArgs& a, int row
         }
         return;
     }
+    if (a.kth_out != nullptr && lane == 0) a.kth_out[row] = n >= a.k ? ukey2f(T) : __builtin_nanf("");
     int cgt = 0, ceq = 0;
 #pragma unroll
     for (int e = 0; e < EPL; ++e) { cgt += __popcll(__ballot(key[e] > T)); ceq += __popcll(__ballot(key[e] == T)); }
@@ -385,6 +386,7 @@ __device__ __forceinline__ void select_cand_row_stream(const SelectCandArgs& a, 
     }
     const uint32_t T = stream_kth_largest(cv, ci, n, k, lane);
     if (a.tau_max != nullptr && lane == 0 && (n < a.k || ukey2f(T) < key2f(a.tau_max[row]))) *a.invalid = 1;
+    if (a.kth_out != nullptr && lane == 0) a.kth_out[row] = n >= a.k ? ukey2f(T) : __builtin_nanf("");
     const int cgt = stream_count(cv, ci, n, 0u, 1, T, 0, lane), ceq = stream_count(cv, ci, n, 0u, 2, T, 0, lane);
     const int need = k - cgt;
     int32_t idx_cut = 0x7fffffff;
@@ -441,6 +443,10 @@ __device__ __forceinline__ void select_small_row(const SelectCandArgs& a, int ro
     if (a.tau_max != nullptr) {
         const float kth = ukey2f(__shfl(key, max(k - 1, 0), 64));
         if (lane == 0 && (n < a.k || kth < key2f(a.tau_max[row]))) *a.invalid = 1;
+    }
+    if (a.kth_out != nullptr) {
+        const float kth = ukey2f(__shfl(key, max(k - 1, 0), 64));
+        if (lane == 0) a.kth_out[row] = n >= a.k ? kth : __builtin_nanf("");
     }
     const bool win = lane < k;
     sort_by_idx_and_store(a, row, k, win ? idx : 0x7fffffff, win ? ukey2f(key) : 0.f, lane);
@@ -512,6 +518,17 @@ __global__ void encoder_init_kernel(int32_t* cand_cnt, int n_rows, int32_t* gmax
     if (i < n_rows) cand_cnt[i] = 0;
     if (i < n_gmax) gmax[i] = INT32_MIN;
     if (tau_max != nullptr && i < n_rows) tau_max[i] = INT32_MIN;
+}
+__global__ __launch_bounds__(256) void repeat_init_kernel(int32_t* cand_cnt, int n_rows, int32_t* gmax, int n_gmax, const int32_t* bad,
+                                                          const int32_t* pre_flag, int32_t* run_enc) {
+    const bool armed = *bad != 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *run_enc = (armed && *pre_flag == 0) ? 1 : 0;
+    if (!armed) return;
+    const int n = max(n_rows, n_gmax);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        if (i < n_rows) cand_cnt[i] = 0;
+        if (i < n_gmax) gmax[i] = INT32_MIN;
+    }
 }
 // per-step scalars in one pass: the stats block, max|x| and the force-dense flag
 __global__ void step_zero_kernel(saev_step_stats* stats, float* upper, int32_t* flag0) {
@@ -882,6 +899,11 @@ __global__ __launch_bounds__(256) void pre_encode_kernel(int32_t* cand_cnt, int 
 //     check of pre_encode_kernel, the step's flags and statistics block;
 //   * workgroups past the rows: the next centring vector mu = column sums / n (only a step whose Adam will rebuild the W images
 //     with it moves mu: `update_mu`).
+// norm-predicted bounds: no prediction while the controller has them switched off or the previous step left no usable ratio
+__device__ __forceinline__ bool rho_gate_closed(const float* st) {
+    const float c = st[0], rho = st[6];
+    return st[5] > 0.f || !(rho - rho == 0.f) || !(c > 0.f);
+}
 __global__ __launch_bounds__(256) void pre_encode2_kernel(PreEncode2Args a) {
     __shared__ float sh[5][4];
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -934,6 +956,11 @@ __global__ __launch_bounds__(256) void pre_encode2_kernel(PreEncode2Args a) {
         *a.pre_flag = pre;
         *a.wmax_prev = wmax;
         a.flags1[0] = pre; a.flags1[1] = 0; a.flags1[2] = 0;
+        if (a.rho_mode != 0) {  // gate: 0 predict, 1 the controller says no (or the step goes dense anyway), 2 not asked for
+            const int g = a.rho_mode != 2 ? 2 : ((pre != 0 || rho_gate_closed(a.rho_state)) ? 1 : 0);
+            *a.rho_gate = g;
+            *a.rho_bad = g != 0 ? 1 : 0;
+        }
         *a.upper = amax;
         *a.stats = saev_step_stats{};
         const float xs_next = (cmax > 0.f && cmax < 3.0e38f) ? exp2f(13.0f - floorf(log2f(cmax))) : x_scale;
@@ -960,6 +987,13 @@ __global__ __launch_bounds__(256) void pre_encode2_kernel(PreEncode2Args a) {
     const float xn = back * sqrtf(s2) * 1.000001f, xd = back * sqrtf(d2) * 1.000002f;  // (rounded up: they bound errors)
     if (a.xnorm != nullptr) { a.xnorm[2 * i] = xn; a.xnorm[2 * i + 1] = xd; }
     a.margin[i] = f16r_margin(xn, xd, wmax, dwmax, bmax, a.D, x_scale);
+    // norm-predicted bound of the row (kernels.h: RhoArgs): c * rho_lo * ||x_b - mu||, from what the previous step's statistics
+    // launch left; every workgroup reads the same read-only state, so all rows see one decision
+    if (a.rho_mode == 2 && !rho_gate_closed(a.rho_state)) {
+        const float bound = a.rho_state[0] * a.rho_state[6] * xn;
+        a.row_bound[i] = bound;
+        a.tau_max[i] = f2key(bound);
+    }
 }
 __global__ void follower_scales_kernel(const float* xside, const float* wmax, float* scales, int32_t* pre_flag, int keep_w) {
     if (threadIdx.x != 0) return;
@@ -1092,6 +1126,13 @@ hipError_t launch_init_i32(int32_t* p, int32_t v, int n, hipStream_t stream) {
     return hipGetLastError();
 }
 
+hipError_t launch_repeat_init(int32_t* cand_cnt, int n_rows, int32_t* gmax, int n_gmax, const int32_t* bad, const int32_t* pre_flag,
+                              int32_t* run_enc, hipStream_t stream) {
+    const int n = std::max(n_rows, n_gmax);
+    hipLaunchKernelGGL(repeat_init_kernel, dim3(std::max(1, std::min((n + 255) / 256, 256))), dim3(256), 0, stream, cand_cnt, n_rows, gmax,
+                       n_gmax, bad, pre_flag, run_enc);
+    return hipGetLastError();
+}
 hipError_t launch_encoder_init(int32_t* cand_cnt, int n_rows, int32_t* gmax, int n_gmax, hipStream_t stream, int32_t* tau_max,
                                const int32_t* enable_flag, int enable_when) {
     const int n = n_rows > n_gmax ? n_rows : n_gmax;

@@ -631,7 +631,53 @@ struct StatsArgs {
     const RowStats* rs; int n_rows, D, P; float alpha; int with_aux; const float* upper; const int32_t* n_overflow;
     saev_step_stats* stats; const int32_t* n_dead_dev; double* scratch; const int32_t* cand_cnt; int cand_cap;
 };
-__device__ __forceinline__ void stats_reduce_body(const StatsArgs& A, int bid, int n_blocks) {
+// The controller of the norm-predicted TopK bounds (kernels.h: RhoArgs), one thread at the end of a step.  A failed prediction
+// (the step was repeated with guaranteed bounds) takes c down by 5 %, a good one lets it climb by 0.05 % while the lists are
+// still longer than 3 k, up to 0.95.  A prediction does not PAY when it failed or when it left lists of more than max(12 k, 256)
+// candidates per row (no shorter than the guaranteed bounds': data whose ratios spread widely, e.g. a trained dictionary on low-rank
+// activations, where a lower c only lengthens the lists until they overflow).  Three such steps in a row switch prediction off for
+// 256 steps, four times as long every time it happens again (at most 65 536), and back to 256 after 256 paying steps in a row.
+__device__ __forceinline__ void rho_controller(const RhoArgs& R, float rho_min, float cand_mean) {
+    float* st = R.state;
+    const int gate = R.flags[11], bad = R.flags[9], dense = R.flags[1];
+    float c = st[0];
+    if (gate == 0) {
+        st[2] += 1.f;
+        if (bad != 0) {
+            c -= 0.05f;
+            st[1] += 1.f;
+        } else if (cand_mean > 3.f * (float)R.k) {
+            c += 0.0005f;
+        }
+        if (bad != 0 || cand_mean > fmaxf(12.f * (float)R.k, 256.f)) {
+            st[4] += 1.f;
+            st[8] = 0.f;
+            if (st[4] >= 3.f) {
+                st[4] = 0.f;
+                st[5] = 256.f * exp2f(2.f * st[7]);
+                st[7] = fminf(st[7] + 1.f, 4.f);
+                st[9] += 1.f;
+                if (R.host != nullptr) {  // (length first, then the serial the host compares: it reads them in the other order)
+                    R.host[1] = (int32_t)st[5];
+                    __threadfence_system();
+                    R.host[0] = (int32_t)st[9];
+                }
+                if (bad != 0) c = 0.85f;
+            }
+        } else {
+            st[4] = 0.f;
+            st[8] += 1.f;
+            if (st[8] >= 256.f) st[7] = 0.f;
+        }
+        st[0] = fminf(fmaxf(c, 0.5f), 0.95f);
+    } else if (st[5] > 0.f) {  // (a step without prediction, paused here or -- once the host has seen the pause -- there)
+        st[5] -= 1.f;
+    }
+    st[3] = cand_mean;
+    // (a step that took the exact dense route has no final select: nothing to scale the next bounds from)
+    st[6] = (dense == 0 && rho_min < 3.0e38f) ? rho_min : __builtin_nanf("");
+}
+__device__ __forceinline__ void stats_reduce_body(const StatsArgs& A, int bid, int n_blocks, const RhoArgs& R = RhoArgs{}) {
     const RowStats* rs = A.rs; const int n_rows = A.n_rows, D = A.D, P = A.P; const float alpha = A.alpha; const int with_aux = A.with_aux;
     const float* upper = A.upper; const int32_t* n_overflow = A.n_overflow; saev_step_stats* stats = A.stats;
     const int32_t* n_dead_dev = A.n_dead_dev; double* scratch = A.scratch; const int32_t* cand_cnt = A.cand_cnt; const int cand_cap = A.cand_cap;
@@ -644,7 +690,12 @@ __device__ __forceinline__ void stats_reduce_body(const StatsArgs& A, int bid, i
     double s[NS] = {0, 0, 0, 0, 0, 0, 0, 0};  // [6] rows with cand_cnt > cap, [7] max cand_cnt
     const int per = (n_rows + n_blocks - 1) / n_blocks;
     const int r0 = bid * per, r1 = min(n_rows, r0 + per);
+    float rho_min = 3.4e38f;
     for (int r = r0 + threadIdx.x; r < r1; r += 1024) {
+        if (R.kth != nullptr) {  // (rows without a usable ratio -- fewer than k entries, a zero or non-finite norm -- do not take part)
+            const float q = R.kth[r] / R.xnorm[2 * r];
+            if (q - q == 0.f) rho_min = fminf(rho_min, q);
+        }
         const RowStats v = rs[r];
         s[0] += v.sse_scaled; s[1] += v.l0; s[2] += v.l1; s[3] += with_aux ? v.aux_sse : 0.f;
         s[4] += v.sse64; s[5] += v.sumsq64;
@@ -658,10 +709,25 @@ __device__ __forceinline__ void stats_reduce_body(const StatsArgs& A, int bid, i
     for (int i = 0; i < 7; ++i) s[i] = wave_sum_d(s[i]);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s[7] = fmax(s[7], __shfl_xor(s[7], o, 64));
+    __shared__ float sh_rho[16], sh_cnt[16];
+    if (R.kth != nullptr) {
+        float csum = 0.f;  // (list lengths, for the mean: counts up to 16 384 x 4 096 are exact in fp32 per wave and close enough after)
+        if (cand_cnt != nullptr)
+            for (int r = r0 + threadIdx.x; r < r1; r += 1024) csum += (float)min(cand_cnt[r], cand_cap);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { rho_min = fminf(rho_min, __shfl_xor(rho_min, o, 64)); csum += __shfl_xor(csum, o, 64); }
+        if ((threadIdx.x & 63) == 0) { sh_rho[threadIdx.x >> 6] = rho_min; sh_cnt[threadIdx.x >> 6] = csum; }
+    }
     if ((threadIdx.x & 63) == 0)
         for (int i = 0; i < NS; ++i) sh[threadIdx.x >> 6][i] = s[i];
     __syncthreads();
     int* ticket = reinterpret_cast<int*>(scratch + 16 * NS);
+    if (R.kth != nullptr && threadIdx.x == 64) {
+        float m = 3.4e38f, t = 0.f;
+        for (int w = 0; w < 16; ++w) { m = fminf(m, sh_rho[w]); t += sh_cnt[w]; }
+        __hip_atomic_store(&R.scratch[bid], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&R.scratch[16 + bid], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (threadIdx.x < NS) {  // one lane per statistic: the slice's value, written through to where the last workgroup reads it
         const int i = threadIdx.x;
         double t = 0.0;
@@ -684,8 +750,18 @@ __device__ __forceinline__ void stats_reduce_body(const StatsArgs& A, int bid, i
         const int b = threadIdx.x / NS, i = threadIdx.x % NS;
         part[b][i] = b < n_blocks ? __hip_atomic_load(&scratch[b * NS + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
     }
+    __shared__ float rho_part[32];
+    if (R.kth != nullptr && threadIdx.x >= 128 && threadIdx.x < 160) {
+        const int j = threadIdx.x - 128;
+        rho_part[j] = (j & 15) < n_blocks ? __hip_atomic_load(&R.scratch[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (j < 16 ? 3.4e38f : 0.f);
+    }
     __syncthreads();
     if (threadIdx.x != 0) return;
+    if (R.kth != nullptr) {
+        float m = 3.4e38f, t = 0.f;
+        for (int b = 0; b < 16; ++b) { m = fminf(m, rho_part[b]); t += rho_part[16 + b]; }
+        rho_controller(R, m, t / (float)max(n_rows, 1));
+    }
     {
         double t[NS] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int b = 0; b < n_blocks; ++b) {
@@ -727,8 +803,8 @@ hipError_t dispatch_nv(int D, F&& f) {
 
 __global__ __launch_bounds__(1024) void stats_reduce_kernel(StatsArgs A) { stats_reduce_body(A, blockIdx.x, gridDim.x); }
 // the forward's statistics and the tracker update of a fused train step in one launch (they meet nowhere)
-__global__ __launch_bounds__(1024) void stats_dead_kernel(StatsArgs A, int n_stat, DeadArgs d) {
-    if ((int)blockIdx.x < n_stat) stats_reduce_body(A, blockIdx.x, n_stat);
+__global__ __launch_bounds__(1024) void stats_dead_kernel(StatsArgs A, int n_stat, DeadArgs d, RhoArgs R) {
+    if ((int)blockIdx.x < n_stat) stats_reduce_body(A, blockIdx.x, n_stat, R);
     else dead_update_body(d, (int)blockIdx.x - n_stat, (int)gridDim.x - n_stat);
 }
 
@@ -828,9 +904,9 @@ hipError_t launch_stats_reduce(const RowStats* rs, int n_rows, int D, int P, flo
 }
 hipError_t launch_stats_dead(const RowStats* rs, int n_rows, int D, int P, float alpha, const float* upper, const int32_t* n_overflow,
                              saev_step_stats* stats, double* scratch, const int32_t* cand_cnt, int cand_cap, const DeadArgs& d,
-                             hipStream_t stream) {
+                             hipStream_t stream, const RhoArgs* rho) {
     const int nb = std::max(1, std::min(16, (n_rows + 1023) / 1024));
     const StatsArgs A{rs, n_rows, D, P, alpha, 0, upper, n_overflow, stats, nullptr, scratch, cand_cnt, cand_cap};
-    hipLaunchKernelGGL(stats_dead_kernel, dim3(nb + (d.S + 1023) / 1024), dim3(1024), 0, stream, A, nb, d);
+    hipLaunchKernelGGL(stats_dead_kernel, dim3(nb + (d.S + 1023) / 1024), dim3(1024), 0, stream, A, nb, d, rho != nullptr ? *rho : RhoArgs{});
     return hipGetLastError();
 }

@@ -38,10 +38,12 @@ class EngineConfig:
     shard_world: int = 1       # > 1: flat buffers padded so that this many data-parallel ranks can each own 1/N of the tail
     max_backward_rows: int = 0  # 0 = max_batch; the GLOBAL batch for the sparse-state exchange (gathered backward over every
                                 # rank's rows): sizes the backward's scratch only, the forward's buffers stay at max_batch
-    # TopK candidate bounds of the fused encoder: "guaranteed" (default), or "predicted": verified extrapolated bounds
-    # with an automatic guaranteed-bound re-run when a prediction fails -- same codes either way; measured no faster over
-    # a training run (tools/experiments/README.md), kept as an option.  SAEV_AMD_BOUNDS overrides the default
-    bounds: str = dataclasses.field(default_factory=lambda: os.environ.get("SAEV_AMD_BOUNDS", "guaranteed"))
+    # TopK candidate bounds of the fused encoder.  "guaranteed": running minimum over group maxima, always.  "norm" (default): the
+    # same, except in the streamed f16r train step of a plain TopK engine, where a row's bound is predicted from its norm and the
+    # previous step's exact k-th largest values, verified, and the step repeated on the device with guaranteed bounds if a row
+    # fails.  "predicted": the older in-tile mean + z sigma predictor in every launch -- measured no faster over a
+    # training run (tools/experiments/README.md), kept as an option.  Same codes in all three.  SAEV_AMD_BOUNDS overrides the default
+    bounds: str = dataclasses.field(default_factory=lambda: os.environ.get("SAEV_AMD_BOUNDS", "norm"))
     # "f32": exact fp32 MFMA; "f16x3": split-fp16 MFMA at fp32 accuracy (16/3 of the f32 matrix rate);
     # "bf16": bf16-rounded encoder operands, one MFMA product, fp32 accumulate (everything else stays fp32);
     # "f16r": one fp16 MFMA product as a bounded-error first pass + exact fp32 recomputation of the surviving candidates.
@@ -1693,8 +1695,8 @@ class SaeEngine:
         self.chunk_a, self.chunk_b = lay.chunk_a, lay.chunk_b
         self.offsets = {"W_dec": lay.off_W_dec, "b_dec": lay.off_b_dec, "W_enc": lay.off_W_enc, "b_enc": lay.off_b_enc}
         self.shapes = {"W_dec": (S, D), "b_dec": (D,), "W_enc": (D, S), "b_enc": (S,)}
-        if cfg.bounds not in ("guaranteed", "predicted"):
-            raise ValueError(f"EngineConfig.bounds (SAEV_AMD_BOUNDS) must be 'guaranteed' or 'predicted', got {cfg.bounds!r}")
+        if cfg.bounds not in ("guaranteed", "predicted", "norm"):
+            raise ValueError(f"EngineConfig.bounds (SAEV_AMD_BOUNDS) must be 'guaranteed', 'predicted' or 'norm', got {cfg.bounds!r}")
         if cfg.encoder not in ("f32", "f16x3", "bf16", "f16r"):
             raise ValueError(f"EngineConfig.encoder (SAEV_AMD_ENCODER) must be one of f32, f16x3, bf16, f16r, got {cfg.encoder!r}")
         if cfg.activation not in ("topk", "relu", "batch_topk", "relu_train"):
@@ -1750,7 +1752,7 @@ class SaeEngine:
             normalize_w_dec=int(cfg.normalize_w_dec), remove_parallel_grads=int(cfg.remove_parallel_grads),
             max_batch=cfg.max_batch, encoder_mode={"f32": 0, "f16x3": 1, "bf16": 2, "f16r": 3}[cfg.encoder],
             aux_dead_cap=cfg.aux_dead_cap, shard_world=cfg.shard_world,
-            bound_mode={"guaranteed": 0, "predicted": 1}[cfg.bounds], max_backward_rows=cfg.max_backward_rows,
+            bound_mode={"guaranteed": 0, "predicted": 1, "norm": 2}[cfg.bounds], max_backward_rows=cfg.max_backward_rows,
             activation={"topk": _lib.ACT_TOPK, "relu": _lib.ACT_RELU, "batch_topk": _lib.ACT_BATCHTOPK, "relu_train": _lib.ACT_RELU}[cfg.activation],
         )
         dbg = _lib.SaevDebugCfg(
@@ -2441,11 +2443,17 @@ class SaeEngine:
         return int(self.lib.saev_dead_readbacks(self.ctx))
 
     def bound_state(self) -> dict:
-        """z of the predicted bounds, launches that used them, how many had to be repeated, mean list length of the last."""
+        """z of the predicted bounds (``bounds="norm"``: their safety factor c), launches that used them, how many had to be
+        repeated, mean list length of the last."""
         z, mc = C.c_float(), C.c_float()
         n, r = C.c_int64(), C.c_int64()
         self._chk(self.lib.saev_bound_state(self.ctx, C.byref(z), C.byref(n), C.byref(r), C.byref(mc), _stream()), "saev_bound_state")
-        return {"z": z.value, "launches": n.value, "repeats": r.value, "mean_candidates": mc.value}
+        out = {"z": z.value, "launches": n.value, "repeats": r.value, "mean_candidates": mc.value}
+        if self.cfg.bounds == "norm":  # (their ratio and what is left of a pause: saev_bound_ratio)
+            rho, left = C.c_float(), C.c_int64()
+            self._chk(self.lib.saev_bound_ratio(self.ctx, C.byref(rho), C.byref(left), _stream()), "saev_bound_ratio")
+            out.update(rho_lo=rho.value, pause_left=left.value)
+        return out
 
     def enable_kernel_timing(self, on: bool = True):
         self._chk(self.lib.saev_enable_kernel_timing(self.ctx, int(on)), "saev_enable_kernel_timing")
