@@ -1104,6 +1104,59 @@ int saev_latent_auroc(const int64_t* row_ptr, const int32_t* indices, const floa
                       int64_t* fire_pos, int64_t* fire_neg, double* sum_pos, double* sum_neg, /* S x T each */
                       int64_t* pos,                                               /* C */
                       void* workspace, int64_t workspace_bytes, void* stream);
+/* LATENT SPATIAL (the third property of a good latent in the reference's contrib/mimics logbook -- spatial coherence -- and idea 4
+ * of its README, "spatial activation heatmaps": where on the patch grid a latent fires, per group of images), context-free;
+ * DESIGN.md 3.27.  For every latent j and every group g of images: the exact counts behind adjacency, clustering and position
+ * consistency (saev_amd/spatial.py), the per-cell maps, and the activation-weighted moments of the firing positions.
+ * INPUT: x is CSR over N = n_images * T rows, T = gh * gw: row_ptr, indices, data and nnz as LATENT AP takes them (absolute
+ * positions, nnz = row_ptr[N] - row_ptr[0] given by the host).  Rows must be CANONICAL: at most one entry per (row, latent).  Row
+ * i * T + p is position p of image i, at grid row r = p / gw and grid column c = p % gw.  group_i32 (n_images int32, device):
+ * group_i32[i] in [-1, G); an image of group -1 contributes to nothing.
+ * LIMITS (SAEV_UNSUPPORTED, and -1 from the workspace-size function): 1 <= G <= 64; 1 <= gh, gw and T <= 4096; 1 <= N, S < 2^31 and
+ * 0 <= nnz < 2^31; S * G * T < 2^31.  N != n_images * gh * gw is SAEV_INVALID_ARG.
+ * EVENT RULE: a stored entry FIRES when value > thr (fp32 compare), thr >= 0 given by the host.  NaN never fires; a stored 0, a
+ * negative value and a value equal to thr do not fire; +Inf fires.
+ * INTEGER OUTPUTS (S x G int64 each, exact).  With F(j, i) the firing positions of latent j in image i and m = |F(j, i)|, summed
+ * over the images i of group g:
+ *   n_events       sum of m
+ *   n_images_fire  images with m >= 1
+ *   pairs_h        pairs {(r, c), (r, c + 1)} with both positions in F -- never across the end of a grid row
+ *   pairs_v        pairs {(r, c), (r + 1, c)} with both positions in F -- never into the next image
+ *   sum_m2         sum of m^2
+ *   overlap        sum over p of count_map[j, g, p]^2
+ * count_map (S x G x T int32): count_map[j, g, p] = the images of g in which j fires at p.  n_group_images (G int64) = the images of
+ * group g.
+ * MOMENTS (S x G x 5 fp64): moments[j, g, :] = sum v, sum v r, sum v c, sum v r^2, sum v c^2 over the firing entries.  v is widened
+ * exactly to fp64, r^2 and c^2 are integers, and each product is formed in fp64 and is exact (24 bits by at most 24).  Each sum
+ * starts at +0 and takes its terms one at a time in ASCENDING ROW order -- no blocking, no partial sums.  sum_map (S x G x T fp64,
+ * may be NULL): sum_map[j, g, p] = the same sum of v per cell, in ascending image order.  A non-finite sum is what IEEE gives
+ * (+Inf at r = 0 makes sum v r NaN).
+ * DETERMINISM: no floating-point atomic.  The outputs of (j, g) depend on j's events and the group ids only -- not on other latents,
+ * on G beyond g, on the launch or on timing: two calls give the same bits, and a latent scored alone gives the bits it has among
+ * others.  The entry overwrites every output wholly; the caller need not clear them.
+ * ERRORS: arguments are checked before the device is touched, in this order: a negative size (N, S, nnz, n_images, gh, gw, G);
+ * N, S or nnz of 2^31 or more; N or S of 0; G outside [1, 64]; the grid (gh or gw of 0, T above 4096); N != n_images * gh * gw;
+ * S * G * T of 2^31 or more; thr negative or NaN; row_ptr NULL; indices or data NULL with nnz > 0; group_i32 NULL; an output other
+ * than sum_map NULL; the workspace NULL or too small; the workspace not 256-byte aligned.  The message is left with
+ * saev_last_error(NULL).  err is int32[0] at BYTE 0 of the workspace: 0, or the largest of SAEV_LATENT_SPATIAL_ERR_GROUP (a group id
+ * outside [-1, G)) and SAEV_LATENT_SPATIAL_ERR_LATENT (an index outside [0, S)) met on the device.  Both are found in the first pass
+ * over the entries (the group ids of images without entries in a pass over group_i32), before any index is used as an address;
+ * the caller reads err when it next synchronises, and the outputs are void if it is not 0.  Nothing is allocated, nothing is read
+ * back and nothing synchronises.
+ * WORKSPACE: saev_latent_spatial_workspace_bytes(n_images, T, S, G, nnz) bytes of device memory, 256-byte aligned: 12 bytes per
+ * stored entry, 12 per latent and the counting sort's table of at most 2^26 counters -- never an N x S or nnz x G array.
+ * LIMIT: a latent's events are walked by one wave, 64 at a time; a latent that fires on most rows is a serial walk. */
+#define SAEV_LATENT_SPATIAL_ERR_GROUP 1
+#define SAEV_LATENT_SPATIAL_ERR_LATENT 2
+int64_t saev_latent_spatial_workspace_bytes(int64_t n_images, int64_t T, int64_t S, int64_t G, int64_t nnz);
+int saev_latent_spatial(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t n_images,
+                        int64_t gh, int64_t gw, int64_t S, const int32_t* group_i32, int64_t G, float thr,
+                        int64_t* n_group_images,                                    /* G */
+                        int64_t* n_events, int64_t* n_images_fire, int64_t* pairs_h, int64_t* pairs_v, int64_t* sum_m2,
+                        int64_t* overlap,                                           /* S x G each */
+                        double* moments,                                            /* S x G x 5 */
+                        int32_t* count_map, double* sum_map,                        /* S x G x T each; sum_map may be NULL */
+                        void* workspace, int64_t workspace_bytes, void* stream);
 /* SPARSE LINEAR (the training half of the concept audit, the reference's contrib/trait_discovery tdiscovery.classification:
  * aggregate_to_images and the LogisticRegression(penalty="l1") of train_worker_fn), context-free; DESIGN.md 3.20.
  *

@@ -249,6 +249,8 @@ _SIGNATURES = {
     "saev_probe_ap": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, P, C.c_int32, P, P, P, P, C.c_int32, P, P, C.c_int64, P]),
     "saev_latent_auroc_workspace_bytes": (C.c_int64, [C.c_int64] * 5),
     "saev_latent_auroc": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, C.c_int64, P]),
+    "saev_latent_spatial_workspace_bytes": (C.c_int64, [C.c_int64] * 5),
+    "saev_latent_spatial": (C.c_int, [P, P, P] + [C.c_int64] * 6 + [P, C.c_int64, C.c_float] + [P] * 10 + [P, C.c_int64, P]),
     "saev_pool_images_range": (C.c_int64, []),
     "saev_pool_images": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, P, P, P]),
     "saev_l1_logistic_workspace_bytes": (C.c_int64, [C.c_int64] * 3),

@@ -1270,6 +1270,81 @@ def latent_auroc(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor
     return LatentAUROCResult(out, ws, layout, (n_rows, n_latents, n_classes, nnz))
 
 
+class LatentSpatialResult(_Checked):
+    """What ``latent_spatial`` leaves on the device.  (S, G) int64: ``n_events``, ``n_images_fire``, ``pairs_h``, ``pairs_v``,
+    ``sum_m2`` and ``overlap``; ``moments`` (S, G, 5) float64 (sum v, sum v r, sum v c, sum v r^2, sum v c^2); ``count_map``
+    (S, G, gh, gw) int32; ``sum_map`` (S, G, gh, gw) float64 or None; ``n_group_images`` (G) int64.  ``grid`` is (gh, gw).  The call
+    itself does not synchronise; the first read of a result -- or ``check()`` -- reads the device's error word (one synchronisation)
+    and raises ValueError if it is not 0 (include/saev_amd.h: LATENT SPATIAL).  ``saev_amd.spatial`` turns the integers into scores."""
+
+    _WHO = "latent_spatial"
+    _ERRORS = {1: "a group id lies outside [-1, n_groups)", 2: "a column index lies outside [0, n_latents)"}
+
+    def __init__(self, out: dict, ws, grid):
+        super().__init__(out, ws[0:4].view(torch.int32), self._ERRORS, self._WHO)
+        self._ws, self.grid = ws, grid
+
+    n_group_images = property(lambda self: self._read("n_group_images"))
+    n_events = property(lambda self: self._read("n_events"))
+    n_images_fire = property(lambda self: self._read("n_images_fire"))
+    pairs_h = property(lambda self: self._read("pairs_h"))
+    pairs_v = property(lambda self: self._read("pairs_v"))
+    sum_m2 = property(lambda self: self._read("sum_m2"))
+    overlap = property(lambda self: self._read("overlap"))
+    moments = property(lambda self: self._read("moments"))
+    count_map = property(lambda self: self._read("count_map"))
+    sum_map = property(lambda self: self._read("sum_map"))
+
+
+def latent_spatial(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, *, n_images: int, grid: tuple[int, int], n_latents: int,
+                   groups: torch.Tensor, n_groups: int, threshold: float = 0.0, sum_map: bool = True, nnz: int | None = None) -> LatentSpatialResult:
+    """Where every latent fires on the (gh, gw) patch grid, per group of images: the exact counts behind the spatial-coherence scores
+    of ``saev_amd.spatial`` and the per-cell maps (include/saev_amd.h: LATENT SPATIAL).  x as CSR on the device over
+    ``n_images * gh * gw`` rows (indptr int64, indices int32, data float32; ``nnz`` as for ``latent_ap``), row ``i * gh * gw + p``
+    being position p of image i; ``groups`` (n_images) int32 / int64 in [-1, n_groups), -1 leaving the image out; an entry fires when
+    it is > ``threshold`` (>= 0).  ``sum_map=False`` leaves the (S, G, gh, gw) float64 map out.  One call, one workspace, no
+    synchronisation; there is no CPU path."""
+    who = "latent_spatial"
+    gh, gw = (int(g) for g in grid)
+    if gh < 1 or gw < 1 or gh * gw > 4096:
+        raise ValueError(f"{who}: unsupported grid {gh} x {gw} (gh, gw >= 1 and at most 4096 positions)")
+    tpi = gh * gw
+    for name, v, hi in (("n_images", n_images, 2**31 // tpi + 1), ("n_latents", n_latents, 2**31), ("n_groups", n_groups, 65)):
+        if not 1 <= v < hi:
+            raise ValueError(f"{who}: unsupported {name} {v} (1 <= {name} < {hi})")
+    n_rows = n_images * tpi
+    if n_latents * n_groups * tpi >= 2**31:
+        raise ValueError(f"{who}: n_latents * n_groups * gh * gw = {n_latents * n_groups * tpi} must stay below 2^31 (score the latents in slices)")
+    if not threshold >= 0:
+        raise ValueError(f"{who}: threshold {threshold} must be at least 0")
+    device = _hip_device(who, indptr.device)
+    stored = indices.numel()
+    nnz = stored if nnz is None else int(nnz)
+    if not 0 <= nnz < 2**31 or nnz > stored:
+        raise ValueError(f"{who}: unsupported nnz {nnz} (0 <= nnz < 2^31, and at most the {stored} entries of indices)")
+    csr = _csr_on(indptr, indices, data, n_rows, stored, device)
+    if groups.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"groups must be int32 or int64, got {groups.dtype}")
+    groups = _on(groups.to(torch.int32), torch.int32, (n_images,), "groups", device)
+    lib = _lib.load()
+    need = lib.saev_latent_spatial_workspace_bytes(n_images, tpi, n_latents, n_groups, nnz)
+    if need < 0:
+        raise ValueError(f"{who}: unsupported shape")
+    ws = torch.empty(need, device=device, dtype=torch.uint8)
+    pairs = (n_latents, n_groups)
+    i64, f64 = dict(device=device, dtype=torch.int64), dict(device=device, dtype=torch.float64)
+    out = dict(n_group_images=torch.empty(n_groups, **i64), n_events=torch.empty(pairs, **i64), n_images_fire=torch.empty(pairs, **i64),
+               pairs_h=torch.empty(pairs, **i64), pairs_v=torch.empty(pairs, **i64), sum_m2=torch.empty(pairs, **i64),
+               overlap=torch.empty(pairs, **i64), moments=torch.empty(*pairs, 5, **f64),
+               count_map=torch.empty(*pairs, gh, gw, device=device, dtype=torch.int32),
+               sum_map=torch.empty(*pairs, gh, gw, **f64) if sum_map else None)
+    with torch.cuda.device(device):
+        rc = lib.saev_latent_spatial(*map(_ptr, csr), nnz, n_rows, n_images, gh, gw, n_latents, _ptr(groups), n_groups, float(threshold),
+                                     *map(_ptr, out.values()), _ptr(ws), ws.numel(), _stream())
+    _lib.check(lib, None, rc, who)
+    return LatentSpatialResult(out, ws, (gh, gw))
+
+
 class PoolResult(_Checked):
     """What ``pool_images`` leaves on the device: ``pooled`` (n_images, n_latents) float32.  The call itself does not synchronise; the
     first read of ``pooled`` reads the device's error word (one synchronisation) and raises ValueError if it is not 0.  ``ranges`` is
