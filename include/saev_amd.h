@@ -1157,6 +1157,76 @@ int saev_latent_spatial(const int64_t* row_ptr, const int32_t* indices, const fl
                         double* moments,                                            /* S x G x 5 */
                         int32_t* count_map, double* sum_map,                        /* S x G x T each; sum_map may be NULL */
                         void* workspace, int64_t workspace_bytes, void* stream);
+/* LATENT EXEMPLARS (ideas 1 and 5 of the reference's contrib/mimics README: per-class activation grids with labels, and the
+ * counter-example explorer -- the wrong class's images that fire strongly, the right class's images that stay silent),
+ * context-free; DESIGN.md 3.28.  For every latent j and every group g of images: the k strongest firing images, the k weakest firing
+ * images and the first k silent ones, each firing image with its max-pooled value and the patch where that maximum sits.
+ * INPUT: as LATENT SPATIAL takes it.  x is CSR over N = n_images * T rows: row_ptr int64 (absolute positions), indices int32, data
+ * fp32, nnz = row_ptr[N] - row_ptr[0] given by the host.  Row i * T + p is patch p of image i; T = 1: the rows are images already.
+ * At most one entry per (row, latent); rows need not be sorted by column.  group_i32 (n_images int32, device): group_i32[i] in
+ * [-1, G); -1 leaves the image out.  thr >= 0 and k >= 1 given by the host.
+ * EVENT: a stored entry is an event when its latent lies in [0, S), its value is > thr (fp32 compare: NaN and a value equal to thr
+ * are never events, +Inf is) and its image's group is >= 0.
+ * PER IMAGE: image i FIRES for latent j when it holds at least one event of j.  Then M(i, j) is the largest event value -- because
+ * thr >= 0 the pool_images("max") value -- and P(i, j) the SMALLEST patch index that attains it.
+ * OUTPUTS (saev_latent_exemplars_out; latent-major, every one written whole by the call: the caller need not clear them):
+ *   n_group_images  G int64: the images of group g (n_g below)
+ *   n_fire          S x G int32: the firing images of the group
+ *   top_val fp32, top_img int32, top_patch int32 (S x G x k each): the group's firing images in the order (M descending, image
+ *                   ascending), the first min(k, n_fire) of them: M, i and P
+ *   bot_val, bot_img, bot_patch: the same in the order (M ascending, image ascending).  An image stands in both lists when
+ *                   n_fire < 2 k
+ *   silent_img      S x G x k int32: the first min(k, n_g - n_fire) images of the group that do NOT fire, in ascending image order
+ * Unused slots hold val 0.0, img -1, patch -1.
+ * LIMITS (SAEV_UNSUPPORTED; -1 from the workspace-size function for those on its arguments): 1 <= n_images, S < 2^31 and
+ * 0 <= nnz < 2^31; 1 <= G <= 64; 1 <= k <= 32; 1 <= T <= 4096; n_images * T < 2^31; S * G * k < 2^31.  nnz = 0 is valid: every list
+ * is empty and the silent lists are the first k members of each group.
+ * DETERMINISM: no floating-point atomic and no read-back.  Both orders are total, so the outputs of (j, g) depend on j's events and
+ * the group ids only -- not on other latents, on the other groups, on the launch or on timing: two calls give the same bits, a
+ * latent scored alone (a CSR of that one column) gives the bits it has among others, and so does a group scored alone.
+ * ERRORS: arguments are checked before the device is touched, in this order: the refusals every (N, S, C, nnz) analysis entry makes
+ * on (n_images, S, nnz) -- a negative size; n_images, S or nnz of 2^31 or more; n_images or S of 0 --; G outside [1, 64]; k outside
+ * [1, 32]; T outside [1, 4096]; n_images * T of 2^31 or more; S * G * k of 2^31 or more; thr negative or NaN; row_ptr NULL;
+ * indices or data NULL with nnz > 0; group_i32 NULL; out NULL or its struct_size unset; an output NULL; the workspace NULL or too
+ * small; the workspace not 256-byte aligned.  The message is left with saev_last_error(NULL).  err is int32[0] at BYTE 0 of the
+ * workspace: 0, or the largest of SAEV_LATENT_EXEMPLARS_ERR_GROUP (a group id outside [-1, G)) and
+ * SAEV_LATENT_EXEMPLARS_ERR_LATENT (an index outside [0, S)) met on the device, found before any index is used as an address; the
+ * caller reads err when it next synchronises, and the outputs are void if it is not 0.  Nothing is allocated, nothing is read back
+ * and nothing synchronises.
+ * WORKSPACE: saev_latent_exemplars_workspace_bytes(nnz, S, n_images, G) bytes of device memory, 256-byte aligned: 12 bytes per
+ * stored entry, 12 per latent, 8 per image and the counting sort's table of at most 2^26 counters -- never an n_images x S array.
+ * LIMIT: a latent's events are walked by one wave, 64 at a time; a latent that fires on most rows is a serial walk.
+ *
+ * saev_latent_patch_rows gathers the patch vectors behind chosen (latent, image) pairs, for the overlays: for query q,
+ * out[q, p] (Q x T fp32) = the STORED value of latent q_latent[q] in row q_image[q] * T + p on the bits -- whatever its sign, event
+ * or not -- or 0.0 where the row stores none (the first stored one where a row breaks the contract and stores two).  A query with
+ * image -1, the padding of the lists above, gives a row of zeros.  err (one int32 on the device, zeroed by the call): 0, or the
+ * largest of SAEV_LATENT_EXEMPLARS_ERR_LATENT (a q_latent outside [0, S)) and SAEV_LATENT_EXEMPLARS_ERR_IMAGE (a q_image outside
+ * [-1, n_images)) met; such a query's row is zeros.  Refusals, in order: those of the (N, S, C, nnz) entries on (n_images, S, nnz);
+ * T outside [1, 4096]; n_images * T of 2^31 or more; Q negative; Q * T of 2^31 or more; then, unless Q = 0 -- which returns SAEV_OK
+ * and writes nothing --, row_ptr NULL; indices or data NULL with nnz > 0; q_latent, q_image, out or err NULL. */
+#define SAEV_LATENT_EXEMPLARS_ERR_GROUP 1
+#define SAEV_LATENT_EXEMPLARS_ERR_LATENT 2
+#define SAEV_LATENT_EXEMPLARS_ERR_IMAGE 3
+typedef struct {
+    int32_t struct_size;     /* sizeof(saev_latent_exemplars_out) of the caller (fields past it read as NULL) */
+    int32_t reserved;
+    int64_t* n_group_images; /* G */
+    int32_t* n_fire;         /* S x G */
+    float* top_val;          /* S x G x k, as the six below */
+    int32_t* top_img;
+    int32_t* top_patch;
+    float* bot_val;
+    int32_t* bot_img;
+    int32_t* bot_patch;
+    int32_t* silent_img;
+} saev_latent_exemplars_out;
+int64_t saev_latent_exemplars_workspace_bytes(int64_t nnz, int64_t S, int64_t n_images, int64_t G);
+int saev_latent_exemplars(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, const int32_t* group_i32,
+                          int64_t n_images, int64_t T, int64_t S, int64_t G, int64_t k, float thr, const saev_latent_exemplars_out* out,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+int saev_latent_patch_rows(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t n_images, int64_t T,
+                           int64_t S, const int32_t* q_latent, const int32_t* q_image, int64_t Q, float* out, int32_t* err, void* stream);
 /* SPARSE LINEAR (the training half of the concept audit, the reference's contrib/trait_discovery tdiscovery.classification:
  * aggregate_to_images and the LogisticRegression(penalty="l1") of train_worker_fn), context-free; DESIGN.md 3.20.
  *

@@ -87,6 +87,13 @@ class SaevLatentHistState(C.Structure):
                 ("n_rows", C.c_void_p), ("prefix", C.c_void_p)]
 
 
+class SaevLatentExemplarsOut(C.Structure):
+    """include/saev_amd.h: saev_latent_exemplars_out (where saev_latent_exemplars leaves its lists; device pointers)."""
+
+    OUTPUTS = ("n_group_images", "n_fire", "top_val", "top_img", "top_patch", "bot_val", "bot_img", "bot_patch", "silent_img")
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32)] + [(name, C.c_void_p) for name in OUTPUTS]
+
+
 class SaevLatentHistTargets(C.Structure):
     """include/saev_amd.h: saev_latent_hist_targets (the quantiles of saev_latent_hist_locate and what it leaves per target)."""
 
@@ -251,6 +258,9 @@ _SIGNATURES = {
     "saev_latent_auroc": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, C.c_int64, P]),
     "saev_latent_spatial_workspace_bytes": (C.c_int64, [C.c_int64] * 5),
     "saev_latent_spatial": (C.c_int, [P, P, P] + [C.c_int64] * 6 + [P, C.c_int64, C.c_float] + [P] * 10 + [P, C.c_int64, P]),
+    "saev_latent_exemplars_workspace_bytes": (C.c_int64, [C.c_int64] * 4),
+    "saev_latent_exemplars": (C.c_int, [P, P, P, C.c_int64, P] + [C.c_int64] * 5 + [C.c_float, C.POINTER(SaevLatentExemplarsOut), P, C.c_int64, P]),
+    "saev_latent_patch_rows": (C.c_int, [P, P, P] + [C.c_int64] * 4 + [P, P, C.c_int64, P, P, P]),
     "saev_pool_images_range": (C.c_int64, []),
     "saev_pool_images": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, P, P, P]),
     "saev_l1_logistic_workspace_bytes": (C.c_int64, [C.c_int64] * 3),

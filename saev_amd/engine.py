@@ -1345,6 +1345,127 @@ def latent_spatial(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tens
     return LatentSpatialResult(out, ws, (gh, gw))
 
 
+class LatentExemplarsResult(_Checked):
+    """What ``latent_exemplars`` leaves on the device.  ``n_group_images`` (G) int64; ``n_fire`` (S, G) int32; (S, G, k) each:
+    ``top_val`` float32, ``top_img`` and ``top_patch`` int32 -- the group's firing images by (max-pooled value descending, image
+    ascending) --, ``bot_val``, ``bot_img``, ``bot_patch`` -- by (value ascending, image ascending) -- and ``silent_img`` int32, the
+    first images of the group that do not fire.  Unused slots hold 0.0, -1, -1.  The call itself does not synchronise; the first read
+    of a result -- or ``check()`` -- reads the device's error word (one synchronisation) and raises ValueError if it is not 0
+    (include/saev_amd.h: LATENT EXEMPLARS)."""
+
+    _WHO = "latent_exemplars"
+    _ERRORS = {1: "a group id lies outside [-1, n_groups)", 2: "a column index lies outside [0, n_latents)"}
+    ARRAYS = _lib.SaevLatentExemplarsOut.OUTPUTS
+
+    def __init__(self, out: dict, ws, k: int, tokens_per_image: int):
+        super().__init__(out, ws[0:4].view(torch.int32), self._ERRORS, self._WHO)
+        self._ws, self.k, self.tokens_per_image = ws, k, tokens_per_image
+
+    n_group_images = property(lambda self: self._read("n_group_images"))
+    n_fire = property(lambda self: self._read("n_fire"))
+    top_val = property(lambda self: self._read("top_val"))
+    top_img = property(lambda self: self._read("top_img"))
+    top_patch = property(lambda self: self._read("top_patch"))
+    bot_val = property(lambda self: self._read("bot_val"))
+    bot_img = property(lambda self: self._read("bot_img"))
+    bot_patch = property(lambda self: self._read("bot_patch"))
+    silent_img = property(lambda self: self._read("silent_img"))
+
+
+def _exemplar_rows(who: str, n_images: int, tokens_per_image: int, n_latents: int) -> None:
+    """The shape refusals ``latent_exemplars`` and ``latent_patch_rows`` share (they mirror the C entries')."""
+    if not 1 <= tokens_per_image <= 4096:
+        raise ValueError(f"{who}: unsupported tokens_per_image {tokens_per_image} (1 <= tokens_per_image <= 4096)")
+    for name, v, hi in (("n_images", n_images, -(-2**31 // tokens_per_image)), ("n_latents", n_latents, 2**31)):
+        if not 1 <= v < hi:
+            raise ValueError(f"{who}: unsupported {name} {v} (1 <= {name} < {hi})")
+
+
+def latent_exemplars(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, *, n_images: int, tokens_per_image: int, n_latents: int,
+                     groups: torch.Tensor, n_groups: int, k: int, threshold: float = 0.0, nnz: int | None = None) -> LatentExemplarsResult:
+    """Which images to look at: for every latent and every group of images the ``k`` strongest firing images, the ``k`` weakest firing
+    images and the first ``k`` silent ones, each firing image with its max-pooled value and the lowest patch that attains it
+    (include/saev_amd.h: LATENT EXEMPLARS).  x as CSR on the device over ``n_images * tokens_per_image`` rows (indptr
+    int64, indices int32, data float32; ``nnz`` as for ``latent_spatial``), row ``i * tokens_per_image + p`` being patch p of image i;
+    ``groups`` (n_images) int32 / int64 in [-1, n_groups), -1 leaving the image out; an entry is an event when it is > ``threshold``
+    (>= 0).  Pooled on the fly, exact and deterministic; one call, one workspace, no synchronisation; there is no CPU path."""
+    who = "latent_exemplars"
+    _exemplar_rows(who, n_images, tokens_per_image, n_latents)
+    for name, v, hi in (("n_groups", n_groups, 65), ("k", k, 33)):
+        if not 1 <= v < hi:
+            raise ValueError(f"{who}: unsupported {name} {v} (1 <= {name} < {hi})")
+    if n_latents * n_groups * k >= 2**31:
+        raise ValueError(f"{who}: n_latents * n_groups * k = {n_latents * n_groups * k} must stay below 2^31 (score the latents in slices)")
+    if not threshold >= 0:
+        raise ValueError(f"{who}: threshold {threshold} must be at least 0")
+    device = _hip_device(who, indptr.device)
+    stored = indices.numel()
+    nnz = stored if nnz is None else int(nnz)
+    if not 0 <= nnz < 2**31 or nnz > stored:
+        raise ValueError(f"{who}: unsupported nnz {nnz} (0 <= nnz < 2^31, and at most the {stored} entries of indices)")
+    csr = _csr_on(indptr, indices, data, n_images * tokens_per_image, stored, device)
+    if groups.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"groups must be int32 or int64, got {groups.dtype}")
+    groups = _on(groups.to(torch.int32), torch.int32, (n_images,), "groups", device)
+    lib = _lib.load()
+    need = lib.saev_latent_exemplars_workspace_bytes(nnz, n_latents, n_images, n_groups)
+    if need < 0:
+        raise ValueError(f"{who}: unsupported shape")
+    ws = torch.empty(need, device=device, dtype=torch.uint8)
+    lists = (n_latents, n_groups, k)
+    i32, f32 = dict(device=device, dtype=torch.int32), dict(device=device, dtype=torch.float32)
+    out = dict(n_group_images=torch.empty(n_groups, device=device, dtype=torch.int64), n_fire=torch.empty(n_latents, n_groups, **i32),
+               top_val=torch.empty(lists, **f32), top_img=torch.empty(lists, **i32), top_patch=torch.empty(lists, **i32),
+               bot_val=torch.empty(lists, **f32), bot_img=torch.empty(lists, **i32), bot_patch=torch.empty(lists, **i32),
+               silent_img=torch.empty(lists, **i32))
+    struct = _lib.SaevLatentExemplarsOut(struct_size=C.sizeof(_lib.SaevLatentExemplarsOut), **{name: _ptr(t) for name, t in out.items()})
+    with torch.cuda.device(device):
+        rc = lib.saev_latent_exemplars(*map(_ptr, csr), nnz, _ptr(groups), n_images, tokens_per_image, n_latents, n_groups, k, float(threshold),
+                                       C.byref(struct), _ptr(ws), ws.numel(), _stream())
+    _lib.check(lib, None, rc, who)
+    return LatentExemplarsResult(out, ws, k, tokens_per_image)
+
+
+_PATCH_ROWS_ERRORS = {2: "a queried latent lies outside [0, n_latents)", 3: "a queried image lies outside [-1, n_images)"}
+
+
+def latent_patch_rows(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, latents: torch.Tensor, images: torch.Tensor, *,
+                      n_images: int, tokens_per_image: int, n_latents: int) -> torch.Tensor:
+    """The patch vectors behind chosen (latent, image) pairs: ``latents`` and ``images`` (int32 / int64, any equal shape) give
+    ``(*shape, tokens_per_image)`` float32 with the STORED value of the latent in every row of the image, on the bits, and 0.0 where
+    a row stores none; an image of -1 -- a padding slot of ``latent_exemplars``' lists -- gives zeros (include/saev_amd.h: LATENT
+    EXEMPLARS).  x as ``latent_exemplars`` takes it.  Reads the device's error word before it returns (one synchronisation) and
+    raises ValueError for a latent outside [0, n_latents) or an image outside [-1, n_images); there is no CPU path."""
+    who = "latent_patch_rows"
+    _exemplar_rows(who, n_images, tokens_per_image, n_latents)
+    if tuple(latents.shape) != tuple(images.shape):
+        raise ValueError(f"{who}: latents {tuple(latents.shape)} and images {tuple(images.shape)} must have one shape")
+    for name, t in (("latents", latents), ("images", images)):
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{name} must be int32 or int64, got {t.dtype}")
+    shape, n_q = tuple(latents.shape), latents.numel()
+    if n_q * tokens_per_image >= 2**31:
+        raise ValueError(f"{who}: {n_q} queries of {tokens_per_image} tokens must stay below 2^31 values (gather in slices)")
+    device = _hip_device(who, indptr.device)
+    stored = indices.numel()
+    if stored >= 2**31:
+        raise ValueError(f"{who}: unsupported nnz {stored} (0 <= nnz < 2^31)")
+    csr = _csr_on(indptr, indices, data, n_images * tokens_per_image, stored, device)
+    q_latent = _on(latents.to(torch.int32).reshape(-1), torch.int32, (n_q,), "latents", device)
+    q_image = _on(images.to(torch.int32).reshape(-1), torch.int32, (n_q,), "images", device)
+    out = torch.empty(n_q, tokens_per_image, device=device, dtype=torch.float32)
+    if n_q == 0:
+        return out.reshape(*shape, tokens_per_image)
+    err = torch.empty(1, device=device, dtype=torch.int32)
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        rc = lib.saev_latent_patch_rows(*map(_ptr, csr), stored, n_images, tokens_per_image, n_latents, _ptr(q_latent), _ptr(q_image), n_q, _ptr(out),
+                                        _ptr(err), _stream())
+    _lib.check(lib, None, rc, who)
+    _check_err_word(err, _PATCH_ROWS_ERRORS, who)
+    return out.reshape(*shape, tokens_per_image)
+
+
 class PoolResult(_Checked):
     """What ``pool_images`` leaves on the device: ``pooled`` (n_images, n_latents) float32.  The call itself does not synchronise; the
     first read of ``pooled`` reads the device's error word (one synchronisation) and raises ValueError if it is not 0.  ``ranges`` is
