@@ -1104,7 +1104,51 @@ int saev_latent_auroc(const int64_t* row_ptr, const int32_t* indices, const floa
                       int64_t* fire_pos, int64_t* fire_neg, double* sum_pos, double* sum_neg, /* S x T each */
                       int64_t* pos,                                               /* C */
                       void* workspace, int64_t workspace_bytes, void* stream);
-/* LATENT SPATIAL (the third property of a good latent in the reference's contrib/mimics logbook -- spatial coherence -- and idea 4
+/* LATENT OPERATING POINTS (the second property of a good latent in the reference's contrib/mimics logbook: "high precision and
+ * recall ... for some threshold"), context-free; DESIGN.md 3.29.  For every latent j and every binary task t: the threshold theta at
+ * which the rule "a >= theta => positive" has the best F1, the one at which it has the best Youden J, and the confusion counts at
+ * both, for all S x T pairs in one call, EXACT: the scores are ratios of integers and the argmax is decided on the integers.
+ * CARRIED OVER FROM LATENT AUROC UNCHANGED: x, the shapes and their limits (1 <= T <= 4096), the two label forms, the event rule (a
+ * stored +-0.0 is no event; negative values and +-Inf are ordered events; a row without an event has activation 0; NaN is outside the
+ * contract), role (0 out, 1 negative, 2 positive), n_pos, n_neg, pos, the error word and its three codes, the workspace and what is
+ * left in it, the argument checks before the device is touched; nothing is allocated, nothing is read back, nothing synchronises;
+ * integer atomics only, and only in the shared front half (class counts, the sort's digit counts, the error word).
+ * CANDIDATES: for latent j and task t, over the task's included rows only: "predict nothing" (reported theta = +Inf, TP = FP = 0), and
+ * every distinct activation value v of those rows (the rows without an event contribute the value 0), with
+ *   TP(v) / FP(v) = the task's positives / negatives with a >= v (fp32 comparison).
+ * OBJECTIVES, both maximised over the candidates on integers:
+ *   F1 = 2 TP / (TP + FP + n_pos): candidate a beats candidate b iff TP_a (TP_b + FP_b + n_pos) > TP_b (TP_a + FP_a + n_pos) as
+ *        unsigned 64-bit products of factors below 2^32;
+ *   J  = TP / n_pos - FP / n_neg: J2 = TP n_neg - FP n_pos compared as int64, |J2| < 2^62.
+ * TIES go to the HIGHER threshold, "predict nothing" being the highest.  So a value whose rows change neither count of the task
+ * never wins, the winning J2 is >= 0 with 0 meaning "predict nothing", and a winner with TP + FP = 0 is "predict nothing".  An event
+ * value of +Inf that wins reports theta = +Inf as well, with TP + FP > 0; theta = -Inf predicts every included row.
+ * OUTPUTS (device, S x T each): f1 (fp64) = (2.0 * (double)TP) / (double)(TP + FP + n_pos), one division, no contraction, NaN
+ * (0x7ff8000000000000) when n_pos = 0; f1_thr (fp32) the winning threshold; f1_tp, f1_fp (int64) the counts there; j2 (int64) the
+ * winning TP n_neg - FP n_pos; youden (fp64) = (double)j2 / ((double)n_pos * (double)n_neg), NaN when n_pos n_neg = 0; j_thr (fp32),
+ * j_tp, j_fp (int64).  And n_pos, n_neg (T int64), pos (C int64) as LATENT AUROC leaves them.  Precision TP / (TP + FP) and recall
+ * TP / n_pos at either point follow from the counts.  ONE ORIENTATION, "high activation => positive": a caller who wants the other
+ * swaps the role bytes 1 and 2 in a second task row.
+ * DETERMINISM as LATENT AUROC: a pair's outputs depend on its own latent's events, the row classes and its own row of role only.
+ * FLAGS: 0, or SAEV_OPERATING_SORTED: the caller vouches that the workspace was left by saev_latent_auroc or saev_latent_operating
+ * called with the same x, N, S, C, nnz, labels, T and role, and passes that call's n_pos, n_neg and pos back: they are INPUTS then.
+ * The entry then neither counts the classes, nor sorts, nor builds the role table, nor clears the error word (it stays what that
+ * call left); x and role are checked for NULL as always and not read, the labels are read.  Without the flag everything is rebuilt.
+ * ERRORS: the shape and label refusals of LATENT AUROC in its order, then: role NULL; one of the nine per-pair outputs NULL; a bit of
+ * flags other than SAEV_OPERATING_SORTED; n_pos, n_neg or pos NULL; a workspace that is NULL or smaller than
+ * saev_latent_operating_workspace_bytes (all SAEV_INVALID_ARG); a workspace that is not 256-byte aligned.
+ * WORKSPACE: saev_latent_operating_workspace_bytes(N, S, C, T, nnz) = saev_latent_auroc_workspace_bytes(N, S, C, T, nnz), the same
+ * layout. */
+#define SAEV_OPERATING_SORTED 1
+int64_t saev_latent_operating_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t T, int64_t nnz);
+int saev_latent_operating(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+                          const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32,
+                          const uint8_t* role, int64_t T, int32_t flags,              /* T x C */
+                          double* f1, float* f1_thr, int64_t* f1_tp, int64_t* f1_fp,  /* S x T each */
+                          int64_t* j2, double* youden, float* j_thr, int64_t* j_tp, int64_t* j_fp, /* S x T each */
+                          int64_t* n_pos, int64_t* n_neg, int64_t* pos,               /* T, T, C: outputs, or inputs with the flag */
+                          void* workspace, int64_t workspace_bytes, void* stream);
+/* LATENT SPATIAL(the third property of a good latent in the reference's contrib/mimics logbook -- spatial coherence -- and idea 4
  * of its README, "spatial activation heatmaps": where on the patch grid a latent fires, per group of images), context-free;
  * DESIGN.md 3.27.  For every latent j and every group g of images: the exact counts behind adjacency, clustering and position
  * consistency (saev_amd/spatial.py), the per-cell maps, and the activation-weighted moments of the firing positions.

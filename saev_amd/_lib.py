@@ -145,6 +145,7 @@ EDIT_SET, EDIT_SCALE, EDIT_ADD, EDIT_IF_ACTIVE = 0, 1, 2, 4
 ACT_TOPK, ACT_RELU, ACT_BATCHTOPK = 0, 1, 2
 ROW_OVERFLOW = -7  # saev_status SAEV_ROW_OVERFLOW
 BATCH_OVERWRITE = 1
+OPERATING_SORTED = 1  # SAEV_OPERATING_SORTED
 ROW_NORM_WORKSPACE_BYTES = 8192
 
 
@@ -256,6 +257,8 @@ _SIGNATURES = {
     "saev_probe_ap": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, P, C.c_int32, P, P, P, P, C.c_int32, P, P, C.c_int64, P]),
     "saev_latent_auroc_workspace_bytes": (C.c_int64, [C.c_int64] * 5),
     "saev_latent_auroc": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, C.c_int64, P]),
+    "saev_latent_operating_workspace_bytes": (C.c_int64, [C.c_int64] * 5),
+    "saev_latent_operating": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, P, P, P, P, C.c_int64, C.c_int32] + [P] * 12 + [P, C.c_int64, P]),
     "saev_latent_spatial_workspace_bytes": (C.c_int64, [C.c_int64] * 5),
     "saev_latent_spatial": (C.c_int, [P, P, P] + [C.c_int64] * 6 + [P, C.c_int64, C.c_float] + [P] * 10 + [P, C.c_int64, P]),
     "saev_latent_exemplars_workspace_bytes": (C.c_int64, [C.c_int64] * 4),

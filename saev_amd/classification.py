@@ -126,11 +126,8 @@ def latent_ap_matrix(token_acts_csr, labels_flat: np.ndarray, *, ignore_label_id
     return res.ap.cpu().numpy(), classes, res.n_pos.cpu().numpy()
 
 
-def latent_auroc_matrix(token_acts_csr, labels_flat: np.ndarray, *, ignore_label_ids=(0,), ignored_as_negative: bool = False, device=None):
-    """(auroc_sc (d_sae, n_seg_classes) float64, classes (n_seg_classes) int64, n_pos_c (n_seg_classes) int64): the exact tie-aware
-    AUROC of EVERY latent against every segmentation class, one-vs-rest, over the columns of ``latent_ap_matrix`` -- threshold-free
-    and, unlike AP, independent of the class's prevalence (``engine.latent_auroc``; DESIGN.md 3.23).  A row with an ignored label is
-    left out of every task; with ``ignored_as_negative`` those rows form a class of their own that is negative in every task."""
+def _one_vs_rest(token_acts_csr, labels_flat, ignore_label_ids, ignored_as_negative):
+    """(csr, labels_flat, classes, remap, roles) of the one-vs-rest tasks ``latent_auroc_matrix`` describes."""
     labels_flat = np.ascontiguousarray(labels_flat)
     if labels_flat.dtype != np.uint8 or labels_flat.ndim != 1:
         raise ValueError(f"labels_flat must be a uint8 vector, got {labels_flat.dtype} {labels_flat.shape}.")
@@ -147,11 +144,36 @@ def latent_auroc_matrix(token_acts_csr, labels_flat: np.ndarray, *, ignore_label
         n_classes = n_tasks + 1
     roles = np.ones((n_tasks, n_classes), dtype=np.uint8)
     roles[np.arange(n_tasks), np.arange(n_tasks)] = 2
+    return csr, labels_flat, classes, remap, roles
+
+
+def latent_auroc_matrix(token_acts_csr, labels_flat: np.ndarray, *, ignore_label_ids=(0,), ignored_as_negative: bool = False, device=None):
+    """(auroc_sc (d_sae, n_seg_classes) float64, classes (n_seg_classes) int64, n_pos_c (n_seg_classes) int64): the exact tie-aware
+    AUROC of EVERY latent against every segmentation class, one-vs-rest, over the columns of ``latent_ap_matrix`` -- threshold-free
+    and, unlike AP, independent of the class's prevalence (``engine.latent_auroc``; DESIGN.md 3.23).  A row with an ignored label is
+    left out of every task; with ``ignored_as_negative`` those rows form a class of their own that is negative in every task."""
+    csr, labels_flat, classes, remap, roles = _one_vs_rest(token_acts_csr, labels_flat, ignore_label_ids, ignored_as_negative)
+    n_classes = roles.shape[1]
     dev = _device(device)
     n, s = csr.shape
     res = engine.latent_auroc(*_csr_on(csr, dev), n, s, n_classes, labels=torch.from_numpy(labels_flat).to(dev), remap=torch.from_numpy(remap).to(dev),
                               roles=torch.from_numpy(roles).to(dev))
     return res.auroc.cpu().numpy(), classes, res.n_pos.cpu().numpy()
+
+
+def latent_operating_matrix(token_acts_csr, labels_flat: np.ndarray, *, ignore_label_ids=(0,), ignored_as_negative: bool = False, device=None):
+    """(points, classes (n_seg_classes) int64, n_pos_c, n_neg_c (n_seg_classes) int64): the best operating point of EVERY latent
+    against every segmentation class, one-vs-rest, over the tasks of ``latent_auroc_matrix`` (``engine.latent_operating``; DESIGN.md
+    3.29).  ``points`` is a dict of (d_sae, n_seg_classes) arrays: ``f1`` and ``youden`` float64, ``f1_thr`` and ``j_thr`` float32 (the
+    rule is "activation >= threshold"; +Inf with no predicted row is "predict nothing"), ``f1_tp``, ``f1_fp``, ``j2``, ``j_tp``
+    and ``j_fp`` int64, and ``precision_f1``, ``recall_f1``, ``tpr_j``, ``fpr_j`` float64."""
+    csr, labels_flat, classes, remap, roles = _one_vs_rest(token_acts_csr, labels_flat, ignore_label_ids, ignored_as_negative)
+    dev = _device(device)
+    n, s = csr.shape
+    res = engine.latent_operating(*_csr_on(csr, dev), n, s, roles.shape[1], labels=torch.from_numpy(labels_flat).to(dev), remap=torch.from_numpy(remap).to(dev),
+                                  roles=torch.from_numpy(roles).to(dev))
+    points = {k: getattr(res, k).cpu().numpy() for k in res.PAIRS + ("precision_f1", "recall_f1", "tpr_j", "fpr_j")}
+    return points, classes, res.n_pos.cpu().numpy(), res.n_neg.cpu().numpy()
 
 
 def extract_feature_ranking(classifier: object, cls_type: str) -> tuple[np.ndarray, np.ndarray]:

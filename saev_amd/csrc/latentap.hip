@@ -31,7 +31,8 @@
 //   top rows a gather from row and starts.
 //
 // LATENT AUROC (include/saev_amd.h: LATENT AUROC) shares the sort too and walks lane = task; its kernels (au_*) carry
-// their own description further down.
+// their own description further down.  LATENT OPERATING POINTS (include/saev_amd.h: LATENT OPERATING POINTS) walks the
+// same sorted events with the same role table (op_walk_kernel) and may take both from a workspace a call before it has filled.
 //
 // Integer atomics only (digit counts in LDS, class counts, the error word); nothing is read back, nothing synchronises.
 #include "entry_util.h"
@@ -693,6 +694,158 @@ __global__ __launch_bounds__(256) void au_walk_kernel(AuWalk a) {
     a.sum_neg[at] = sn;
 }
 
+// ---------------------------------------------------------------- operating points -------------------------------------------------------
+
+// LATENT OPERATING POINTS (include/saev_amd.h: LATENT OPERATING POINTS): per (latent, task) the threshold at which
+// "a >= theta => positive" has the best F1 and the one with the best Youden J, with the confusion counts there, decided on integers.
+//   walk     a wave per (latent, 64 tasks), lane = task, over the events la_sort left, with au_walk_kernel's role table, its LDS / L2
+//            choice and its batches of eight role bytes.  A lane keeps the running TP, FP and J2 = TP n_neg - FP n_pos (an addition per
+//            event, no product) and its two best candidates in registers.  A tie group closes where the key changes, for every lane at
+//            once, and every close is a candidate; a later (lower) candidate replaces the best only when it is STRICTLY better, which
+//            is the tie rule, and a group that changed neither count of a lane compares equal and so never wins there.  The F1
+//            comparison is two 32 x 32 -> 64 products (TP and TP + FP + n_pos stay below 2^32).
+//   zero     the rows without an event are one candidate at theta = 0 between the last positive and the first negative event: its
+//            counts are n_pos / n_neg minus ALL of the lane's events of that role.  A latent without negative events meets the block
+//            behind its last event, where the running counts are those totals; one with negative events (the last sorted key says
+//            so) is walked once before to count them, as la_terms_kernel does.
+struct OpWalk {
+    const int64_t* starts;
+    const uint32_t* key;
+    const int32_t* row;
+    const uint8_t* u8;
+    const int32_t* remap;
+    const int32_t* i32;
+    const uint8_t* table;
+    const long long* n_pos;
+    const long long* n_neg;
+    double* f1;
+    float* f1_thr;
+    long long* f1_tp;
+    long long* f1_fp;
+    long long* j2;
+    double* youden;
+    float* j_thr;
+    long long* j_tp;
+    long long* j_fp;
+    int N, S, C, T, Tp;
+};
+
+// a wave per (latent, 64 tasks), lane = task.  grid: (ceil(S / 4), Tp / 64); LDS: (C + 1) x 64 bytes of dynamic LDS
+template <bool LDS>
+__global__ __launch_bounds__(256) void op_walk_kernel(OpWalk a) {
+#pragma clang fp contract(off)
+    extern __shared__ uint8_t op_slice[];
+    const int lane = threadIdx.x & 63;
+    const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int t = blockIdx.y * 64 + lane;  // (< Tp)
+    if (LDS) {  // the four waves share the task group: its slice of the table, a 64-byte row as 16 words
+        const int words = (a.C + 1) * 16;
+        for (int w = threadIdx.x; w < words; w += 256)
+            reinterpret_cast<uint32_t*>(op_slice)[w] =
+                *reinterpret_cast<const uint32_t*>(a.table + (size_t)(w >> 4) * a.Tp + (size_t)blockIdx.y * 64 + (size_t)(w & 15) * 4);
+        __syncthreads();
+    }
+    if (j >= a.S) return;
+    const bool active = t < a.T;
+    const uint8_t* mine = LDS ? op_slice + lane : a.table + t;  // + (class + 1) * stride: this lane's role of a class
+    const size_t stride = LDS ? 64 : (size_t)a.Tp;
+    const int64_t s0 = a.starts[j], s1 = a.starts[j + 1];
+    const uint32_t np = active ? (uint32_t)a.n_pos[t] : 0u, nn = active ? (uint32_t)a.n_neg[t] : 0u;  // (both below 2^31)
+
+    // with negative events the zero block sits inside the walk: count the lane's events of either role first
+    const bool has_neg = s1 > s0 && a.key[s1 - 1] >= 0x80000000u;
+    uint32_t Pev = 0, Qev = 0;
+    if (has_neg) {
+        for (int64_t base = s0; base < s1; base += 64) {
+            const int64_t e = base + lane;
+            const int mycl = e < s1 ? la_class(a.u8, a.remap, a.i32, a.row[e], a.C) : -1;  // (behind s1: class -1, the table's row of zeros)
+            const int cnt = (int)min((int64_t)64, s1 - base);
+            for (int i0 = 0; i0 < cnt; i0 += AU_BATCH) {
+                int rs[AU_BATCH];
+#pragma unroll
+                for (int u = 0; u < AU_BATCH; ++u) rs[u] = mine[(size_t)(__shfl(mycl, i0 + u, 64) + 1) * stride];
+#pragma unroll
+                for (int u = 0; u < AU_BATCH; ++u) {
+                    Pev += rs[u] == 2 ? 1u : 0u;
+                    Qev += rs[u] == 1 ? 1u : 0u;
+                }
+            }
+        }
+    }
+
+    const float inf = __uint_as_float(0x7f800000u);
+    uint32_t TP = 0, FP = 0;
+    long long J2 = 0;
+    uint32_t fTP = 0, fD = np, fFP = 0;  // the best F1 so far: "predict nothing"
+    float fthr = inf;
+    long long bJ2 = 0;                   // the best J so far: "predict nothing"
+    uint32_t jTP = 0, jFP = 0;
+    float jthr = inf;
+    uint32_t curk = 0;
+    bool open = false, zero_done = false;
+    const auto candidate = [&](float theta) {  // the rule "a >= theta" with the running counts; equality keeps the earlier, higher one
+        const uint32_t D = TP + FP + np;
+        if ((unsigned long long)TP * fD > (unsigned long long)fTP * D) { fTP = TP; fD = D; fFP = FP; fthr = theta; }
+        if (J2 > bJ2) { bJ2 = J2; jTP = TP; jFP = FP; jthr = theta; }
+    };
+    const auto zero_block = [&]() {  // (no group is open)
+        zero_done = true;
+        const uint32_t p0 = np - (has_neg ? Pev : TP), q0 = nn - (has_neg ? Qev : FP);
+        TP += p0;
+        FP += q0;
+        J2 += (long long)p0 * (long long)nn - (long long)q0 * (long long)np;
+        candidate(0.f);
+    };
+    for (int64_t base = s0; base < s1; base += 64) {
+        const int64_t e = base + lane;
+        uint32_t myk = 0;
+        int mycl = -1;
+        if (e < s1) { myk = a.key[e]; mycl = la_class(a.u8, a.remap, a.i32, a.row[e], a.C); }
+        const int cnt = (int)min((int64_t)64, s1 - base);
+        for (int i0 = 0; i0 < cnt; i0 += AU_BATCH) {
+            uint32_t ks[AU_BATCH];
+            int rs[AU_BATCH];
+#pragma unroll
+            for (int u = 0; u < AU_BATCH; ++u) {  // (behind cnt: class -1, the table's row of zeros)
+                ks[u] = __shfl(myk, i0 + u, 64);
+                rs[u] = mine[(size_t)(__shfl(mycl, i0 + u, 64) + 1) * stride];
+            }
+#pragma unroll
+            for (int u = 0; u < AU_BATCH; ++u) {
+                if (i0 + u < cnt) {
+                    const uint32_t k = ks[u];
+                    if (open && k != curk) {  // the group is closed, for every lane
+                        candidate(ukey2f(~curk));
+                        open = false;
+                    }
+                    if (!zero_done && k >= 0x80000000u) zero_block();  // (a negative key differs from every positive one: no group is open)
+                    curk = k;
+                    open = true;
+                    const bool isp = rs[u] == 2, isn = rs[u] == 1;
+                    TP += isp ? 1u : 0u;
+                    FP += isn ? 1u : 0u;
+                    J2 += isp ? (long long)nn : 0ll;
+                    J2 -= isn ? (long long)np : 0ll;
+                }
+            }
+        }
+    }
+    if (open) candidate(ukey2f(~curk));
+    if (!zero_done) zero_block();
+    if (!active) return;
+    const long long nan = 0x7ff8000000000000LL;
+    const size_t at = (size_t)j * a.T + t;
+    a.f1[at] = np > 0 ? (2.0 * (double)fTP) / (double)fD : __longlong_as_double(nan);
+    a.f1_thr[at] = fthr;
+    a.f1_tp[at] = (long long)fTP;
+    a.f1_fp[at] = (long long)fFP;
+    a.j2[at] = bJ2;
+    a.youden[at] = (np > 0 && nn > 0) ? (double)bJ2 / ((double)np * (double)nn) : __longlong_as_double(nan);
+    a.j_thr[at] = jthr;
+    a.j_tp[at] = (long long)jTP;
+    a.j_fp[at] = (long long)jFP;
+}
+
 // ---------------------------------------------------------------- host -------------------------------------------------------------------
 
 // what la_open leaves for the rest of an entry
@@ -706,10 +859,11 @@ struct LaOpen {
 
 // the front half of both entries: the refusals they share, the layout, err and pos cleared and the class counts enqueued (la_sort
 // is the back half).  `own` is the refusal of the entry's own arguments (NULL: none); it is raised where each entry has always made
-// those checks, behind the label forms and before the workspace
-int la_open(const char* who, const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
-            const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, int64_t* pos, const char* own, void* workspace,
-            int64_t workspace_bytes, void* stream, LaOpen* o) {
+// those checks, behind the label forms and before the workspace.  la_check is the refusals and the layout alone: what an entry that
+// takes a sorted workspace over keeps of it
+int la_check(const char* who, const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+             const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, int64_t* pos, const char* own, void* workspace,
+             int64_t workspace_bytes, void* stream, LaOpen* o) {
     if (const int rc = entry_check_shape(who, N, S, C, nnz)) return rc;
     if (!row_ptr) return entry_refuse(SAEV_INVALID_ARG, who, "row_ptr is NULL");
     if (nnz > 0 && (!indices || !data)) return entry_refuse(SAEV_INVALID_ARG, who, "indices and data come with nnz > 0");
@@ -724,6 +878,13 @@ int la_open(const char* who, const int64_t* row_ptr, const int32_t* indices, con
     o->ws = static_cast<uint8_t*>(workspace);
     o->err = reinterpret_cast<int32_t*>(o->ws + o->L.off_err);
     o->pos = reinterpret_cast<unsigned long long*>(pos);
+    return SAEV_OK;
+}
+
+int la_open(const char* who, const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+            const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, int64_t* pos, const char* own, void* workspace,
+            int64_t workspace_bytes, void* stream, LaOpen* o) {
+    if (const int rc = la_check(who, row_ptr, indices, data, nnz, N, S, C, class_u8, remap, class_i32, pos, own, workspace, workspace_bytes, stream, o)) return rc;
     bool ok = hipMemsetAsync(o->err, 0, 64, o->s) == hipSuccess;
     ok = ok && hipMemsetAsync(pos, 0, (size_t)(8 * C), o->s) == hipSuccess;
     if (!ok) return entry_refuse(SAEV_HIP_ERROR, who, "hipMemsetAsync failed");
@@ -833,6 +994,54 @@ int saev_latent_auroc(const int64_t* row_ptr, const int32_t* indices, const floa
     const size_t slice = (size_t)(C + 1) * 64;
     if (slice <= (size_t)AU_LDS_MAX_BYTES) hipLaunchKernelGGL(au_walk_kernel<true>, grid, dim3(256), slice, s, a);
     else hipLaunchKernelGGL(au_walk_kernel<false>, grid, dim3(256), 0, s, a);
+    if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");
+    return SAEV_OK;
+}
+
+int64_t saev_latent_operating_workspace_bytes(int64_t N, int64_t S, int64_t C, int64_t T, int64_t nnz) {
+    return saev_latent_auroc_workspace_bytes(N, S, C, T, nnz);
+}
+
+int saev_latent_operating(const int64_t* row_ptr, const int32_t* indices, const float* data, int64_t nnz, int64_t N, int64_t S, int64_t C,
+                          const uint8_t* class_u8, const int32_t* remap, const int32_t* class_i32, const uint8_t* role, int64_t T, int32_t flags,
+                          double* f1, float* f1_thr, int64_t* f1_tp, int64_t* f1_fp, int64_t* j2, double* youden, float* j_thr, int64_t* j_tp,
+                          int64_t* j_fp, int64_t* n_pos, int64_t* n_neg, int64_t* pos, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* who = "saev_latent_operating";
+    if (const int rc = entry_check_shape(who, N, S, C, nnz)) return rc;
+    if (T < 1 || T > AU_MAX_T) return entry_refuse(SAEV_UNSUPPORTED, who, "the number of tasks must lie in [1, 4096]");
+    const int64_t need = saev_latent_operating_workspace_bytes(N, S, C, T, nnz);
+    const bool sorted = (flags & SAEV_OPERATING_SORTED) != 0;
+    const char* own = !role ? "role must not be NULL"
+        : (!f1 || !f1_thr || !f1_tp || !f1_fp || !j2 || !youden || !j_thr || !j_tp || !j_fp)
+            ? "f1, f1_thr, f1_tp, f1_fp, j2, youden, j_thr, j_tp and j_fp must not be NULL"
+        : (flags & ~SAEV_OPERATING_SORTED) ? "flags holds a bit other than SAEV_OPERATING_SORTED"
+        : (sorted && (!n_pos || !n_neg || !pos)) ? "with SAEV_OPERATING_SORTED n_pos, n_neg and pos are inputs and must not be NULL"
+        : (!n_pos || !n_neg || !pos) ? "n_pos, n_neg and pos must not be NULL"
+        : (!workspace || workspace_bytes < need) ? "workspace smaller than saev_latent_operating_workspace_bytes(N, S, C, T, nnz)"
+        : nullptr;
+    LaOpen o;
+    const int rc = sorted ? la_check(who, row_ptr, indices, data, nnz, N, S, C, class_u8, remap, class_i32, pos, own, workspace, workspace_bytes, stream, &o)
+                          : la_open(who, row_ptr, indices, data, nnz, N, S, C, class_u8, remap, class_i32, pos, own, workspace, workspace_bytes, stream, &o);
+    if (rc) return rc;
+    hipStream_t s = o.s;
+    const int Tp = (int)au_tp(T);
+    uint8_t* table = o.ws + o.L.total_bytes;
+    long long* np = reinterpret_cast<long long*>(n_pos);
+    long long* nn = reinterpret_cast<long long*>(n_neg);
+    LaSorted e{reinterpret_cast<const int64_t*>(o.ws + o.L.off_starts), reinterpret_cast<const uint32_t*>(o.ws + o.L.off_key),
+               reinterpret_cast<const int32_t*>(o.ws + o.L.off_row)};  // (where la_sort leaves them)
+    if (!sorted) {
+        hipLaunchKernelGGL(au_roles_kernel, dim3((unsigned)(Tp / 64), (unsigned)(C + 1)), dim3(64), 0, s, role, (int)C, (int)T, Tp, table, o.err);
+        hipLaunchKernelGGL(au_counts_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s, table, o.pos, (int)C, (int)T, Tp, np, nn);
+        e = la_sort(o.L, o.ws, row_ptr, indices, data, nnz, N, S, s);
+    }
+    OpWalk a{e.starts, e.key, e.row, class_u8, remap, class_i32, table, np, nn, f1, f1_thr, reinterpret_cast<long long*>(f1_tp),
+             reinterpret_cast<long long*>(f1_fp), reinterpret_cast<long long*>(j2), youden, j_thr, reinterpret_cast<long long*>(j_tp),
+             reinterpret_cast<long long*>(j_fp), (int)N, (int)S, (int)C, (int)T, Tp};
+    const dim3 grid((unsigned)((S + 3) / 4), (unsigned)(Tp / 64));
+    const size_t slice = (size_t)(C + 1) * 64;
+    if (slice <= (size_t)AU_LDS_MAX_BYTES) hipLaunchKernelGGL(op_walk_kernel<true>, grid, dim3(256), slice, s, a);
+    else hipLaunchKernelGGL(op_walk_kernel<false>, grid, dim3(256), 0, s, a);
     if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");
     return SAEV_OK;
 }

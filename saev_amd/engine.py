@@ -1134,10 +1134,12 @@ class LatentAPResult(_APResult):
     best_class = property(lambda self: self._read("best_class"))
 
 
-def _ap_open(who: str, indptr, indices, data, n_rows: int, n_latents: int, n_classes: int, labels, remap, nnz, top_k: int = 0, n_tasks: int | None = None):
-    """What ``latent_ap``, ``probe_ap`` and ``latent_auroc`` do before their C entry: the size checks, the nnz rule, the CSR triple and
-    the labels on the device, the layout and a workspace of its size (with ``n_tasks``: of ``latent_auroc``'s size, which begins with
-    that layout).  Returns (lib, device, nnz, the ten leading arguments of either entry, ws, layout)."""
+def _ap_open(who: str, indptr, indices, data, n_rows: int, n_latents: int, n_classes: int, labels, remap, nnz, top_k: int = 0, n_tasks: int | None = None,
+             ws=None):
+    """What ``latent_ap``, ``probe_ap``, ``latent_auroc`` and ``latent_operating`` do before their C entry: the size checks, the nnz
+    rule, the CSR triple and the labels on the device, the layout and a workspace of its size (with ``n_tasks``: of ``latent_auroc``'s
+    size, which begins with that layout; with ``ws``: that workspace, checked against the size).  Returns (lib, device, nnz, the ten
+    leading arguments of either entry, ws, layout)."""
     for name, v, hi in (("n_rows", n_rows, 2**31), ("n_latents", n_latents, 2**31), ("n_classes", n_classes, 4097)):
         if not 1 <= v < hi:
             raise ValueError(f"{who}: unsupported {name} {v} (1 <= {name} < {hi})")
@@ -1154,7 +1156,10 @@ def _ap_open(who: str, indptr, indices, data, n_rows: int, n_latents: int, n_cla
     layout = _lib.SaevLatentAPLayout()
     _lib.check(lib, None, lib.saev_latent_ap_layout_of(n_rows, n_latents, n_classes, nnz, C.byref(layout)), "saev_latent_ap_layout_of")
     total = layout.total_bytes if n_tasks is None else lib.saev_latent_auroc_workspace_bytes(n_rows, n_latents, n_classes, n_tasks, nnz)
-    ws = torch.empty(total, device=device, dtype=torch.uint8)
+    if ws is None:
+        ws = torch.empty(total, device=device, dtype=torch.uint8)
+    elif ws.numel() != total or ws.device != device:
+        raise ValueError(f"{who}: the workspace to reuse holds {ws.numel()} bytes on {ws.device}, this call needs {total} on {device}")
     return lib, device, nnz, csr, classes, ws, layout
 
 
@@ -1268,6 +1273,86 @@ def latent_auroc(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor
                                    *map(_ptr, out.values()), _ptr(ws), ws.numel(), _stream())
     _lib.check(lib, None, rc, "saev_latent_auroc")
     return LatentAUROCResult(out, ws, layout, (n_rows, n_latents, n_classes, nnz))
+
+
+class LatentOperatingResult(_APResult):
+    """What ``latent_operating`` leaves on the device, (S, T) each: ``f1`` float64 (NaN for a task without positives), ``f1_thr``
+    float32, ``f1_tp`` and ``f1_fp`` int64 (the best F1 of the rule "a >= f1_thr", the threshold and the confusion counts there);
+    ``j2`` int64 (TP n_neg - FP n_pos at its best), ``youden`` float64 (NaN for a task without positives or without negatives),
+    ``j_thr`` float32, ``j_tp`` and ``j_fp`` int64; and ``n_pos``, ``n_neg`` (T) and ``class_counts`` (C) int64.  A threshold of +Inf
+    with no predicted row is "predict nothing".  ``precision_f1``, ``recall_f1``, ``tpr_j`` and ``fpr_j`` (S, T) float64 are formed
+    from the counts on the device (NaN where the denominator is 0).  The call itself does not synchronise; the first read of a
+    result -- or ``check()`` -- reads the device's error word (one synchronisation) and raises ValueError if it is not 0
+    (include/saev_amd.h: LATENT OPERATING POINTS)."""
+
+    _WHO = "latent_operating"
+    _ERRORS = LatentAUROCResult._ERRORS
+    PAIRS = ("f1", "f1_thr", "f1_tp", "f1_fp", "j2", "youden", "j_thr", "j_tp", "j_fp")
+
+    f1 = property(lambda self: self._read("f1"))
+    f1_thr = property(lambda self: self._read("f1_thr"))
+    f1_tp = property(lambda self: self._read("f1_tp"))
+    f1_fp = property(lambda self: self._read("f1_fp"))
+    j2 = property(lambda self: self._read("j2"))
+    youden = property(lambda self: self._read("youden"))
+    j_thr = property(lambda self: self._read("j_thr"))
+    j_tp = property(lambda self: self._read("j_tp"))
+    j_fp = property(lambda self: self._read("j_fp"))
+    n_pos = property(lambda self: self._read("n_pos"))
+    n_neg = property(lambda self: self._read("n_neg"))
+    class_counts = property(lambda self: self._read("class_counts"))
+
+    @staticmethod
+    def _ratio(num, den):
+        den = den.to(torch.float64)
+        return torch.where(den > 0, num.to(torch.float64) / den.clamp_min(1.0), torch.full_like(den, float("nan")))
+
+    precision_f1 = property(lambda self: self._ratio(self.f1_tp, self.f1_tp + self.f1_fp))
+    recall_f1 = property(lambda self: self._ratio(self.f1_tp, self.n_pos[None, :].expand_as(self.f1_tp)))
+    tpr_j = property(lambda self: self._ratio(self.j_tp, self.n_pos[None, :].expand_as(self.j_tp)))
+    fpr_j = property(lambda self: self._ratio(self.j_fp, self.n_neg[None, :].expand_as(self.j_fp)))
+
+
+def latent_operating(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_rows: int, n_latents: int, n_classes: int, *,
+                     labels: torch.Tensor, remap: torch.Tensor | None = None, roles: torch.Tensor, nnz: int | None = None,
+                     reuse: "LatentAUROCResult | LatentOperatingResult | None" = None) -> LatentOperatingResult:
+    """For every latent and every binary task the threshold at which "a >= theta => positive" has the best F1 and the one with the
+    best Youden J, with the confusion counts at both, exact (include/saev_amd.h: LATENT OPERATING POINTS).  x,
+    ``labels``, ``remap``, ``roles`` and ``nnz`` as for ``latent_auroc``.  ``reuse``: the result of a ``latent_auroc`` or
+    ``latent_operating`` call ON THE SAME ARGUMENTS (the caller vouches for that; the shapes are checked here, before any device
+    work): its workspace -- sorted events and role table -- and its counts are taken over and nothing is sorted again; the new result
+    shares them.  One call, no synchronisation; there is no CPU path."""
+    who = "latent_operating"
+    if roles.dim() != 2 or roles.dtype != torch.uint8:
+        raise ValueError(f"{who}: roles must be a (n_tasks, n_classes) uint8 matrix, got {roles.dtype} {tuple(roles.shape)}")
+    n_tasks = roles.shape[0]
+    if not 1 <= n_tasks <= 4096:
+        raise ValueError(f"{who}: unsupported n_tasks {n_tasks} (1 <= n_tasks <= 4096)")
+    stored = indices.numel() if nnz is None else int(nnz)
+    if reuse is not None:
+        if not isinstance(reuse, (LatentAUROCResult, LatentOperatingResult)):
+            raise ValueError(f"{who}: reuse takes a LatentAUROCResult or a LatentOperatingResult, got {type(reuse).__name__}")
+        have = (*reuse.shape, reuse._out["n_pos"].numel())
+        if have != (n_rows, n_latents, n_classes, stored, n_tasks):
+            raise ValueError(f"{who}: the result to reuse has (n_rows, n_latents, n_classes, nnz, n_tasks) = {have}, this call "
+                             f"{(n_rows, n_latents, n_classes, stored, n_tasks)}")
+    lib, device, nnz, csr, classes, ws, layout = _ap_open(who, indptr, indices, data, n_rows, n_latents, n_classes, labels, remap, nnz, n_tasks=n_tasks,
+                                                          ws=None if reuse is None else reuse._ws)
+    roles = _on(roles, torch.uint8, (n_tasks, n_classes), "roles", device)
+    pairs = (n_latents, n_tasks)
+    i64, f64, f32 = (dict(device=device, dtype=dt) for dt in (torch.int64, torch.float64, torch.float32))
+    out = dict(f1=torch.empty(pairs, **f64), f1_thr=torch.empty(pairs, **f32), f1_tp=torch.empty(pairs, **i64), f1_fp=torch.empty(pairs, **i64),
+               j2=torch.empty(pairs, **i64), youden=torch.empty(pairs, **f64), j_thr=torch.empty(pairs, **f32), j_tp=torch.empty(pairs, **i64),
+               j_fp=torch.empty(pairs, **i64))
+    if reuse is None:
+        out.update(n_pos=torch.empty(n_tasks, **i64), n_neg=torch.empty(n_tasks, **i64), class_counts=torch.empty(n_classes, **i64))
+    else:
+        out.update({k: reuse._out[k] for k in ("n_pos", "n_neg", "class_counts")})
+    with torch.cuda.device(device):
+        rc = lib.saev_latent_operating(*map(_ptr, csr), nnz, n_rows, n_latents, n_classes, *map(_ptr, classes), _ptr(roles), n_tasks,
+                                       0 if reuse is None else _lib.OPERATING_SORTED, *map(_ptr, out.values()), _ptr(ws), ws.numel(), _stream())
+    _lib.check(lib, None, rc, "saev_latent_operating")
+    return LatentOperatingResult(out, ws, layout, (n_rows, n_latents, n_classes, nnz))
 
 
 class LatentSpatialResult(_Checked):
