@@ -8,7 +8,7 @@ FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wno-pass-failed -Wno-unuse
 
 all: saev_amd/libsaev_amd.so
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/common.h $(CSRC)/entry_util.h include/saev_amd.h
+build/%.o: $(CSRC)/%.hip $(CSRC)/kernels.h $(CSRC)/common.h $(CSRC)/entry_util.h $(CSRC)/latent_major.h include/saev_amd.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 

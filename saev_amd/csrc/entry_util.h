@@ -1,7 +1,8 @@
 // What the context-free analysis entries share (latenttopk.hip, probe1d.hip, latentap.hip, sparselinear.hip): how a
-// workspace is carved, how a call is refused, the refusals common to the (N, S, C, nnz) entries, and the two device pieces the
-// CSR-reading units need -- the row of a stored entry and the single-workgroup exclusive scan (the wave scan under it is
-// wave_scan_incl of common.h, which kmeans.hip uses too).  Everything inlines: a unit's code
+// workspace is carved, how a call is refused, the refusals common to the (N, S, C, nnz) entries, and the device pieces the
+// CSR-reading units need -- the row of a stored entry, the streamed accumulators' view of one batch of codes and the
+// single-workgroup exclusive scan (the wave scan under it is wave_scan_incl of common.h, which kmeans.hip uses too).  The
+// latent-major regroup built on these is latent_major.h.  Everything inlines: a unit's code
 // objects are what they were when it carried its own copy.
 #pragma once
 #include "common.h"
@@ -23,6 +24,18 @@ struct WsCarve {
         return o;
     }
 };
+
+// The part rule of the latent-major counting sorts (latent_major.h, probe1d.hip): the stored entries are cut into at most LM_PARTS
+// contiguous parts (4 096 bought the place pass an eighth and cost 200 MB of count table: its stores are the floor), parts x S
+// counters stay at or below 2^26, and a part is a whole number of 64-entry trips
+constexpr int LM_PARTS = 1024;
+
+static inline int lm_parts(int64_t S, int64_t nnz) {
+    int64_t p = std::min<int64_t>(LM_PARTS, (nnz + 63) / 64);
+    p = std::min<int64_t>(p, std::max<int64_t>(1, ((int64_t)1 << 26) / std::max<int64_t>(S, 1)));
+    return (int)std::max<int64_t>(p, 1);
+}
+static inline int64_t lm_part_len(int64_t nnz, int parts) { return std::max<int64_t>(64, ((nnz + parts - 1) / parts + 63) / 64 * 64); }
 
 // leaves "who: what" as the thread's last error (saev_last_error(NULL)) and returns `code`
 static inline int entry_refuse(int code, const char* who, const char* what) {
@@ -64,6 +77,53 @@ __device__ __forceinline__ int csr_row_of(const int64_t* row_ptr, int N, int64_t
         if (row_ptr[mid] <= p) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// one batch of codes in either form (padded rows: idx != nullptr; CSR: row_ptr != nullptr), as the streamed accumulators take it
+// (latenttopk.hip, latenthist.hip)
+struct BatchCodes {
+    const int32_t* idx;
+    const float* val;
+    const int32_t* row_nnz;
+    int cap;
+    const int64_t* row_ptr;
+    const int32_t* indices;
+    const float* data;
+    const uint8_t* keep;
+    long total;  // code slots n cap, or stored entries
+    int n, S;
+};
+
+// entry e of the batch: false when it is no entry (padding, masked row, zero, latent out of range).  Without WANT_ROW a CSR entry's
+// row is bisected for only when rows are masked, and *row is left alone
+template <bool WANT_ROW>
+__device__ __forceinline__ bool batch_entry(const BatchCodes& c, long e, int* lat, float* x, int* row) {
+    int r = 0, i;
+    float v;
+    if (c.idx != nullptr) {
+        const long rr = e / c.cap;
+        const int slot = (int)(e - rr * c.cap);
+        r = (int)rr;
+        if (c.keep != nullptr && c.keep[r] == 0) return false;
+        if (c.row_nnz != nullptr && slot >= c.row_nnz[r]) return false;  // (a count above cap reads as cap: slot < cap always)
+        i = c.idx[e];
+        v = c.val[e];
+    } else {
+        const int64_t p = c.row_ptr[0] + e;
+        if (p >= c.row_ptr[c.n]) return false;
+        if (WANT_ROW || c.keep != nullptr) {
+            r = csr_row_of(c.row_ptr, c.n, p);
+            if (c.keep != nullptr && c.keep[r] == 0) return false;
+        }
+        i = c.indices[p];
+        v = c.data[p];
+    }
+    if (i < 0 || i >= c.S) return false;
+    if (v == 0.f) return false;  // zeros of both signs are not entries
+    *lat = i;
+    *x = v;
+    if (WANT_ROW) *row = r;
+    return true;
 }
 
 // Exclusive prefix sums of S elements by ONE workgroup of THREADS, THREADS elements a round so that every load and store is

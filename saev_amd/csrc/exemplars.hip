@@ -3,9 +3,9 @@
 // lowest patch that attains it -- pooled on the fly from the token CSR, never through an n_images x S matrix -- and
 // saev_latent_patch_rows, the gather of the stored patch vectors of chosen (latent, image) pairs.
 //
-//   prepare  the events latent-major in ascending row order, as spatial.hip's prepare leaves them (its count, parts, scan and place
-//            kernels restated here with this entry's error codes; that unit is left as it is).  Two small kernels also leave, for
-//            the silent lists, n_group_images, the first slot of every group, each image's rank inside its group and the groups'
+//   prepare  the events latent-major in ascending row order: the regroup of latent_major.h with this entry's
+//            error codes (a valid latent, the image's group in [0, G), value > thr).  Two small kernels also leave, for the silent lists,
+//            n_group_images, the first slot of every group, each image's rank inside its group and the groups'
 //            member lists in ascending image order: a stable counting sort of the n_images group ids, one wave per group, the rank
 //            of an image among the 64 of a trip from a ballot.
 //   walk     a wave per latent, 64 events a trip.  Lane = event first: a latent's rows ascend, so an image's events are consecutive;
@@ -25,7 +25,7 @@
 // between the wave-wide fill before the first trip and the wave-wide copy after the last, and the wave's LDS stores are drained at
 // both of those borders.  No floating-point atomic, no read-back.  A latent that fires on most rows is one wave's serial walk
 // (DESIGN.md 7).
-#include "entry_util.h"
+#include "latent_major.h"
 
 #include <algorithm>
 #include <cmath>
@@ -36,36 +36,20 @@ namespace {
 constexpr int EX_MAX_G = 64;
 constexpr int EX_MAX_K = 32;
 constexpr int EX_MAX_T = 4096;
-constexpr int EX_PARTS = 1024;  // as spatial.hip's SP_PARTS
-constexpr int EX_SCAN_THREADS = 1024;
 constexpr int EX_ROWS_THREADS = 256;
 constexpr int EX_ROWS_MAX_BLOCKS = 1 << 16;
 
-int ex_parts(int64_t S, int64_t nnz) {
-    int64_t p = std::min<int64_t>(EX_PARTS, (nnz + 63) / 64);
-    p = std::min<int64_t>(p, std::max<int64_t>(1, ((int64_t)1 << 26) / std::max<int64_t>(S, 1)));
-    return (int)std::max<int64_t>(p, 1);
-}
-int64_t ex_part_len(int64_t nnz, int parts) { return std::max<int64_t>(64, ((nnz + parts - 1) / parts + 63) / 64 * 64); }
-
 // byte offsets into the workspace (all multiples of 256); the error word comes first
 struct ExLayout {
-    int64_t parts, part_len, total_bytes;
-    int64_t off_err, off_starts, off_tot, off_cnt, off_fire_row, off_row, off_val, off_rank, off_members, off_gstart;
+    int64_t off_err;
+    LmLayout lm;
+    int64_t off_rank, off_members, off_gstart, total_bytes;
 };
 
 void ex_layout(int64_t nnz, int64_t S, int64_t n_images, ExLayout* L) {
-    *L = ExLayout{};
-    L->parts = ex_parts(S, nnz);
-    L->part_len = ex_part_len(nnz, (int)L->parts);
     WsCarve ws;
     L->off_err = ws.take(64);
-    L->off_starts = ws.take(8 * (S + 1));
-    L->off_tot = ws.take(4 * S);
-    L->off_cnt = ws.take(4 * L->parts * S);
-    L->off_fire_row = ws.take(4 * nnz);
-    L->off_row = ws.take(4 * nnz);
-    L->off_val = ws.take(4 * nnz);
+    lm_carve(ws, S, nnz, &L->lm);
     L->off_rank = ws.take(4 * n_images);
     L->off_members = ws.take(4 * n_images);
     L->off_gstart = ws.take(4 * (EX_MAX_G + 1));
@@ -73,16 +57,6 @@ void ex_layout(int64_t nnz, int64_t S, int64_t n_images, ExLayout* L) {
 }
 
 // ---------------------------------------------------------------- prepare ----------------------------------------------------------------
-
-// n_group[g] = images of group g; a group id outside [-1, G) is reported
-__global__ __launch_bounds__(256) void ex_groups_kernel(const int32_t* __restrict__ group, long n_images, int G, unsigned long long* __restrict__ n_group,
-                                                        int32_t* __restrict__ err) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_images; i += (long)gridDim.x * 256) {
-        const int g = group[i];
-        if (g < -1 || g >= G) atomicMax(err, SAEV_LATENT_EXEMPLARS_ERR_GROUP);
-        else if (g >= 0) atomicAdd(n_group + g, 1ull);
-    }
-}
 
 // one wave per group g: gstart[g] = the members of the groups before it (gstart[G] = all members, left by the last wave), and in
 // ascending image order members[gstart[g] + r] = the r-th image of g, rank[that image] = r.  An image of no group keeps no rank: its
@@ -107,101 +81,6 @@ __global__ __launch_bounds__(64) void ex_members_kernel(const int32_t* __restric
             if (start + r < n_images) members[start + r] = i;  // (always: the groups partition at most n_images images)
         }
         run += __popcll(mask);
-    }
-}
-
-// the first pass over the entries: fire_row[e] = the row of entry e when it is an event (a valid latent, value > thr, its image in
-// a group of [0, G)), else -1; cnt[part][latent] counts the events
-__global__ __launch_bounds__(256) void ex_count_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ indices,
-                                                       const float* __restrict__ data, const int32_t* __restrict__ group, long nnz, int N, int S,
-                                                       int T, int G, float thr, long part_len, int32_t* __restrict__ fire_row,
-                                                       int32_t* __restrict__ cnt, int32_t* __restrict__ err) {
-    const int64_t p0 = row_ptr[0];
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (long)gridDim.x * 256) {
-        const int col = indices[p0 + e];
-        const int row = csr_row_of(row_ptr, N, p0 + e);
-        const int g = group[row / T];
-        int keep = -1;
-        if (col < 0 || col >= S) atomicMax(err, SAEV_LATENT_EXEMPLARS_ERR_LATENT);
-        else if (g < -1 || g >= G) atomicMax(err, SAEV_LATENT_EXEMPLARS_ERR_GROUP);
-        else if (g >= 0 && data[p0 + e] > thr) {  // NaN compares false
-            keep = row;
-            atomicAdd(cnt + (e / part_len) * S + col, 1);
-        }
-        fire_row[e] = keep;
-    }
-}
-
-// cnt[p][l] -> the events of latent l in parts before p; tot[l] = all of them
-__global__ __launch_bounds__(256) void ex_parts_kernel(int32_t* __restrict__ cnt, int parts, int S, int32_t* __restrict__ tot) {
-    const long l = (long)blockIdx.x * 256 + threadIdx.x;
-    if (l >= S) return;
-    int run = 0;
-    for (int p = 0; p < parts; p += 8) {  // eight loads in flight: a store to cnt would otherwise hold back the next load
-        int t[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t[q] = p + q < parts ? cnt[(size_t)(p + q) * S + l] : 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            if (p + q < parts) cnt[(size_t)(p + q) * S + l] = run;
-            run += t[q];
-        }
-    }
-    tot[l] = run;
-}
-
-__global__ __launch_bounds__(EX_SCAN_THREADS) void ex_scan_kernel(const int32_t* __restrict__ tot, int S, int64_t* __restrict__ starts) {
-    const long long end = block_scan_rounds<EX_SCAN_THREADS, long long, long>(
-        S, [&](long l) { return (long long)tot[l]; }, [&](long l, long long start) { starts[l] = start; });
-    if (threadIdx.x == 0) starts[S] = end;
-}
-
-// one wave per part (see the head of probe1d.hip): the rank of an event among the 64 of its trip by comparing lanes, the trip's base
-// by one integer atomic on a cursor only this wave touches
-__global__ __launch_bounds__(64) void ex_place_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ indices, const float* __restrict__ data,
-                                                      const int32_t* __restrict__ fire_row, long nnz, int S, long part_len,
-                                                      const int64_t* __restrict__ starts, int32_t* __restrict__ cnt,
-                                                      int32_t* __restrict__ row_out, float* __restrict__ val_out) {
-    const int lane = threadIdx.x;
-    const long part = blockIdx.x;
-    const long first = part * part_len, last = min(first + part_len, nnz);
-    const int64_t p0 = row_ptr[0];
-    int32_t* cur = cnt + (size_t)part * S;
-    // a trip's loads are issued one trip ahead: the atomic below returns a value, and nothing else hides its latency in a wave
-    // that works alone
-    int col_next = -1, row_next = -1;
-    float v_next = 0.f;
-    auto load = [&](long e) {
-        col_next = row_next = -1;
-        v_next = 0.f;
-        if (e < last) {
-            row_next = fire_row[e];
-            col_next = indices[p0 + e];
-            v_next = data[p0 + e];
-            if (row_next < 0 || col_next < 0 || col_next >= S) col_next = -1;  // (a kept row has its latent inside [0, S))
-        }
-    };
-    load(first + lane);
-    for (long g = first; g < last; g += 64) {
-        const int col = col_next, row = row_next;
-        const float v = v_next;
-        load(g + 64 + lane);
-        const int64_t start = col >= 0 ? starts[col] : 0;
-        int rank = 0, same = 0, leader = 64;
-#pragma unroll 16
-        for (int i = 0; i < 64; ++i) {
-            const bool match = col >= 0 && __builtin_amdgcn_readlane(col, i) == col;
-            same += match;
-            rank += match && i < lane;
-            leader = match && leader == 64 ? i : leader;
-        }
-        int base = 0;
-        if (col >= 0 && leader == lane) base = atomicAdd(cur + col, same);
-        base = __shfl(base, leader & 63, 64);
-        if (col >= 0) {
-            const int64_t at = start + base + rank;
-            if (at >= 0 && at < nnz) { row_out[at] = row; val_out[at] = v; }  // (always: the segments partition the events)
-        }
     }
 }
 
@@ -413,37 +292,19 @@ int saev_latent_exemplars(const int64_t* row_ptr, const int32_t* indices, const 
 
     hipStream_t s = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
-    int32_t* err = reinterpret_cast<int32_t*>(ws + L.off_err);
-    int64_t* starts = reinterpret_cast<int64_t*>(ws + L.off_starts);
-    int32_t* tot = reinterpret_cast<int32_t*>(ws + L.off_tot);
-    int32_t* cnt = reinterpret_cast<int32_t*>(ws + L.off_cnt);
-    int32_t* fire_row = reinterpret_cast<int32_t*>(ws + L.off_fire_row);
-    int32_t* row = reinterpret_cast<int32_t*>(ws + L.off_row);
-    float* val = reinterpret_cast<float*>(ws + L.off_val);
+    const LmLists ev = lm_lists(ws, L.lm);
     int32_t* rank = reinterpret_cast<int32_t*>(ws + L.off_rank);
     int32_t* members = reinterpret_cast<int32_t*>(ws + L.off_members);
     int32_t* gstart = reinterpret_cast<int32_t*>(ws + L.off_gstart);
-    const int64_t N = n_images * T;
-    bool ok = hipMemsetAsync(err, 0, 64, s) == hipSuccess;
-    ok = ok && hipMemsetAsync(cnt, 0, (size_t)(4 * L.parts * S), s) == hipSuccess;
-    ok = ok && hipMemsetAsync(o.n_group_images, 0, (size_t)(8 * G), s) == hipSuccess;
+    bool ok = hipMemsetAsync(o.n_group_images, 0, (size_t)(8 * G), s) == hipSuccess;
     ok = ok && hipMemsetAsync(rank, 0, (size_t)(4 * n_images), s) == hipSuccess;
+    ok = ok && lm_regroup<SAEV_LATENT_EXEMPLARS_ERR_LATENT, SAEV_LATENT_EXEMPLARS_ERR_GROUP>(
+                    row_ptr, indices, data, nnz, n_images * T, S, group_i32, n_images, T, G, thr, o.n_group_images, ev,
+                    reinterpret_cast<int32_t*>(ws + L.off_err), s);
     if (!ok) return entry_refuse(SAEV_HIP_ERROR, who, "hipMemsetAsync failed");
-    unsigned long long* n_group = reinterpret_cast<unsigned long long*>(o.n_group_images);
-    hipLaunchKernelGGL(ex_groups_kernel, dim3((unsigned)std::min<int64_t>((n_images + 255) / 256, 1024)), dim3(256), 0, s, group_i32, (long)n_images,
-                       (int)G, n_group, err);
-    hipLaunchKernelGGL(ex_members_kernel, dim3((unsigned)G), dim3(64), 0, s, group_i32, (int)n_images, (int)G, n_group, gstart, rank, members);
-    if (nnz > 0)
-        hipLaunchKernelGGL(ex_count_kernel, dim3((unsigned)std::min<int64_t>((nnz + 255) / 256, 8192)), dim3(256), 0, s, row_ptr, indices, data, group_i32,
-                           (long)nnz, (int)N, (int)S, (int)T, (int)G, thr, (long)L.part_len, fire_row, cnt, err);
-    hipLaunchKernelGGL(ex_parts_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, cnt, (int)L.parts, (int)S, tot);
-    hipLaunchKernelGGL(ex_scan_kernel, dim3(1), dim3(EX_SCAN_THREADS), 0, s, tot, (int)S, starts);
-    if (nnz > 0) {
-        const unsigned used = (unsigned)((nnz + L.part_len - 1) / L.part_len);
-        hipLaunchKernelGGL(ex_place_kernel, dim3(used), dim3(64), 0, s, row_ptr, indices, data, fire_row, (long)nnz, (int)S, (long)L.part_len, starts,
-                           cnt, row, val);
-    }
-    ExWalk a{starts, row, val, group_i32, rank, members, gstart, (int)S, (int)G, (int)k, (int)T, (int)n_images,
+    hipLaunchKernelGGL(ex_members_kernel, dim3((unsigned)G), dim3(64), 0, s, group_i32, (int)n_images, (int)G,
+                       reinterpret_cast<const unsigned long long*>(o.n_group_images), gstart, rank, members);
+    ExWalk a{ev.starts, ev.row, ev.val, group_i32, rank, members, gstart, (int)S, (int)G, (int)k, (int)T, (int)n_images,
              o.n_fire, o.top_val, o.top_img, o.top_patch, o.bot_val, o.bot_img, o.bot_patch, o.silent_img};
     // the lists of a wave take G * k * 24 bytes of LDS: as many waves a workgroup (at most 4) as 64 KiB hold
     const int64_t wave_bytes = G * k * 24;

@@ -895,7 +895,6 @@ int free_refuse(int code, const char* msg);
 // ---- Per-latent logistic probes (probe1d.hip: kernels and their C entries; include/saev_amd.h: PROBE1D) ------------------------
 // events per work item of the hot kernel: a latent firing on every one of 5 M rows is ~10 000 waves' worth, not one wave's
 constexpr int P1_CHUNK = 512;
-constexpr int P1_PARTS = 1024;  // at most this many contiguous parts of the CSR entries in the stable counting sort of prepare
 
 // ---- Latent AP (latentap.hip: kernels and their C entries; include/saev_amd.h: LATENT AP) -----------------------------------------
 // tie groups of at most this many rows are summed term by term, larger ones through the closed form (saev_latent_ap_layout.direct_max)

@@ -37,41 +37,10 @@ constexpr int LH_FILL = 3584;                 // a step that could push the tabl
 constexpr uint32_t LH_EMPTY = 0xffffffffu;    // no counter has this index: the tables stay below 2^32 - 1 counters
 constexpr uint32_t LH_NO_PREFIX = 0xffffffffu;  // a resolved target: no key carries it
 
-struct LhCodes {  // one batch in either form (padded: idx != nullptr; CSR: row_ptr != nullptr)
-    const int32_t* idx;
-    const float* val;
-    const int32_t* row_nnz;
-    int cap;
-    const int64_t* row_ptr;
-    const int32_t* indices;
-    const float* data;
-    const uint8_t* keep;
-    long total;  // code slots n cap, or stored entries
-    int n, S;
-};
-
-// entry e of the batch: false when it is no entry (padding, masked row, zero, latent out of range)
-__device__ __forceinline__ bool lh_entry(const LhCodes& c, long e, int* lat, uint32_t* key) {
-    int i;
+// entry e of the batch, its value as the key: false when it is no entry (batch_entry; no row is asked for)
+__device__ __forceinline__ bool lh_entry(const BatchCodes& c, long e, int* lat, uint32_t* key) {
     float x;
-    if (c.idx != nullptr) {
-        const long rr = e / c.cap;
-        const int slot = (int)(e - rr * c.cap);
-        const int r = (int)rr;
-        if (c.keep != nullptr && c.keep[r] == 0) return false;
-        if (c.row_nnz != nullptr && slot >= c.row_nnz[r]) return false;  // (a count above cap reads as cap: slot < cap always)
-        i = c.idx[e];
-        x = c.val[e];
-    } else {
-        const int64_t p = c.row_ptr[0] + e;
-        if (p >= c.row_ptr[c.n]) return false;
-        if (c.keep != nullptr && c.keep[csr_row_of(c.row_ptr, c.n, p)] == 0) return false;
-        i = c.indices[p];
-        x = c.data[p];
-    }
-    if (i < 0 || i >= c.S) return false;
-    if (x == 0.f) return false;  // zeros of both signs are not entries
-    *lat = i;
+    if (!batch_entry<false>(c, e, lat, &x, nullptr)) return false;
     *key = f2ukey(x);
     return true;
 }
@@ -105,7 +74,7 @@ __device__ __forceinline__ void lh_flush(uint32_t* keys, uint32_t* cnts, uint32_
 // LEVEL 0, 1 or 2.  counts: S x 4096 at level 0, S x T x 1024 above; prefix: S x 16 (levels 1, 2).  batch_rows: the kept rows of
 // this batch, summed into the workspace's first word
 template <int LEVEL>
-__global__ __launch_bounds__(LH_THREADS) void lh_update_kernel(LhCodes c, int T, uint32_t* __restrict__ counts,
+__global__ __launch_bounds__(LH_THREADS) void lh_update_kernel(BatchCodes c, int T, uint32_t* __restrict__ counts,
                                                                const uint32_t* __restrict__ prefix,
                                                                unsigned long long* __restrict__ batch_rows) {
     __shared__ uint32_t keys[LH_SLOTS];
@@ -355,7 +324,7 @@ int saev_latent_hist_update(const int32_t* idx, const float* val, const int32_t*
 
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* batch_rows = static_cast<unsigned long long*>(workspace);
-    LhCodes c{idx, val, row_nnz, (int)cap, row_ptr, indices, data, keep, (long)total, (int)n, (int)S};
+    BatchCodes c{idx, val, row_nnz, (int)cap, row_ptr, indices, data, keep, (long)total, (int)n, (int)S};
     if (hipMemsetAsync(batch_rows, 0, 8, s) != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "hipMemsetAsync failed");
     const int64_t work = std::max<int64_t>(total, n);
     const int grid = (int)std::min<int64_t>((work + LH_THREADS - 1) / LH_THREADS, LH_GRID_CAP);

@@ -29,56 +29,19 @@ namespace {
 constexpr int LT_MAX_K = 64;
 constexpr int LT_SCAN_THREADS = 1024;
 
-struct LtCodes {  // one batch in either form (padded: idx != nullptr; CSR: row_ptr != nullptr)
-    const int32_t* idx;
-    const float* val;
-    const int32_t* row_nnz;
-    int cap;
-    const int64_t* row_ptr;
-    const int32_t* indices;
-    const float* data;
-    const uint8_t* keep;
-    long total;  // code slots n cap, or stored entries
-    int n, S, k;
-};
-
-// entry e of the batch: false when it is no entry (padding, masked row, zero, latent out of range) or no candidate
-__device__ __forceinline__ bool lt_candidate(const LtCodes& c, long e, const float* __restrict__ top_val, const int32_t* __restrict__ top_cnt,
-                                             int* lat, float* v, int* row) {
-    int r, i;
-    float x;
-    if (c.idx != nullptr) {
-        const long rr = e / c.cap;
-        const int slot = (int)(e - rr * c.cap);
-        r = (int)rr;
-        if (c.keep != nullptr && c.keep[r] == 0) return false;
-        if (c.row_nnz != nullptr && slot >= c.row_nnz[r]) return false;  // (a count above cap reads as cap: slot < cap always)
-        i = c.idx[e];
-        x = c.val[e];
-    } else {
-        const int64_t p = c.row_ptr[0] + e;
-        if (p >= c.row_ptr[c.n]) return false;
-        r = csr_row_of(c.row_ptr, c.n, p);
-        if (c.keep != nullptr && c.keep[r] == 0) return false;
-        i = c.indices[p];
-        x = c.data[p];
-    }
-    if (i < 0 || i >= c.S) return false;
-    if (x == 0.f) return false;  // zeros of both signs are not entries
-    const int have = top_cnt[i];
-    if (have >= c.k && !(x >= top_val[(size_t)i * c.k + c.k - 1])) return false;
-    *lat = i;
-    *v = x;
-    *row = r;
-    return true;
+// entry e of the batch: false when it is no entry (batch_entry) or no candidate
+__device__ __forceinline__ bool lt_candidate(const BatchCodes& c, int k, long e, const float* __restrict__ top_val,
+                                             const int32_t* __restrict__ top_cnt, int* lat, float* v, int* row) {
+    if (!batch_entry<true>(c, e, lat, v, row)) return false;
+    return top_cnt[*lat] < k || *v >= top_val[(size_t)*lat * k + k - 1];
 }
 
-__global__ __launch_bounds__(256) void lt_count_kernel(LtCodes c, const float* __restrict__ top_val, const int32_t* __restrict__ top_cnt,
+__global__ __launch_bounds__(256) void lt_count_kernel(BatchCodes c, int k, const float* __restrict__ top_val, const int32_t* __restrict__ top_cnt,
                                                        int32_t* __restrict__ cnt) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < c.total; e += (long)gridDim.x * 256) {
         int lat, row;
         float v;
-        if (lt_candidate(c, e, top_val, top_cnt, &lat, &v, &row)) atomicAdd(cnt + lat, 1);
+        if (lt_candidate(c, k, e, top_val, top_cnt, &lat, &v, &row)) atomicAdd(cnt + lat, 1);
     }
 }
 
@@ -89,12 +52,12 @@ __global__ __launch_bounds__(LT_SCAN_THREADS) void lt_scan_kernel(const int32_t*
     block_scan_rounds<LT_SCAN_THREADS, int, int>(S, [&](int l) { return cnt[l]; }, [&](int l, int start) { off[l] = start; cur[l] = start; });
 }
 
-__global__ __launch_bounds__(256) void lt_place_kernel(LtCodes c, const float* __restrict__ top_val, const int32_t* __restrict__ top_cnt,
+__global__ __launch_bounds__(256) void lt_place_kernel(BatchCodes c, int k, const float* __restrict__ top_val, const int32_t* __restrict__ top_cnt,
                                                        int32_t* __restrict__ cur, float* __restrict__ cand_val, int32_t* __restrict__ cand_row) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < c.total; e += (long)gridDim.x * 256) {
         int lat, row;
         float v;
-        if (!lt_candidate(c, e, top_val, top_cnt, &lat, &v, &row)) continue;
+        if (!lt_candidate(c, k, e, top_val, top_cnt, &lat, &v, &row)) continue;
         const int at = atomicAdd(cur + lat, 1);
         if (at < 0 || (long)at >= c.total) continue;  // (cannot happen: every segment was counted with this predicate)
         cand_val[at] = v;
@@ -203,12 +166,12 @@ int saev_latent_topk_update(const int32_t* idx, const float* val, const int32_t*
     int32_t* cur = reinterpret_cast<int32_t*>(ws + 2 * round256(4 * S));
     float* cand_val = reinterpret_cast<float*>(ws + 3 * round256(4 * S));
     int32_t* cand_row = reinterpret_cast<int32_t*>(ws + 3 * round256(4 * S) + round256(4 * total));
-    LtCodes c{idx, val, row_nnz, (int)cap, row_ptr, indices, data, keep, (long)total, (int)n, (int)S, st.k};
+    BatchCodes c{idx, val, row_nnz, (int)cap, row_ptr, indices, data, keep, (long)total, (int)n, (int)S};
     if (hipMemsetAsync(cnt, 0, (size_t)S * 4, s) != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "hipMemsetAsync failed");
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
-    hipLaunchKernelGGL(lt_count_kernel, dim3(grid), dim3(256), 0, s, c, st.top_val, st.top_cnt, cnt);
+    hipLaunchKernelGGL(lt_count_kernel, dim3(grid), dim3(256), 0, s, c, st.k, st.top_val, st.top_cnt, cnt);
     hipLaunchKernelGGL(lt_scan_kernel, dim3(1), dim3(LT_SCAN_THREADS), 0, s, cnt, (int)S, off, cur);
-    hipLaunchKernelGGL(lt_place_kernel, dim3(grid), dim3(256), 0, s, c, st.top_val, st.top_cnt, cur, cand_val, cand_row);
+    hipLaunchKernelGGL(lt_place_kernel, dim3(grid), dim3(256), 0, s, c, st.k, st.top_val, st.top_cnt, cur, cand_val, cand_row);
     hipLaunchKernelGGL(lt_merge_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, cnt, off, cand_val, cand_row, (long)total, (int)S,
                        st.k, (long long)row_base, st.top_val, reinterpret_cast<long long*>(st.top_row), st.top_cnt);
     if (hipGetLastError() != hipSuccess) return entry_refuse(SAEV_HIP_ERROR, who, "kernel launch failed");

@@ -2,8 +2,10 @@
 // pairs a two-parameter logistic regression y_c ~ sigma(b + w x_j), fitted by damped Newton (Levenberg-Marquardt) steps whose
 // sums run over the latent's stored entries only -- the rows where the latent is zero enter in closed form.
 //
-//   prepare  the events latent-major: a stable counting sort of the CSR entries by latent.  The entries are cut into up to
-//            P1_PARTS contiguous parts; integer atomics count every (part, latent); a pass per latent turns the counts into the
+//   prepare  the events latent-major: a stable counting sort of the CSR entries by latent, the regroup of DESIGN.md 3.22 in
+//            this unit's own kernels, under the rule "every entry of a latent in [0, S)"; the part rule (lm_parts, lm_part_len,
+//            LM_PARTS) is entry_util.h's, shared with latent_major.h.  The entries are cut into up to
+//            LM_PARTS contiguous parts; integer atomics count every (part, latent); a pass per latent turns the counts into the
 //            parts' offsets inside the latent's segment; a scan over the latents gives `starts` and the chunk list; then ONE WAVE
 //            PER PART walks its entries in order, 64 at a time, and places each behind the earlier ones of its latent (the rank
 //            inside the group of 64 by comparing lanes, the group's base by one integer atomic of the latent's first lane on a
@@ -35,20 +37,13 @@ constexpr int P1_SUB = 64;                      // events per sub-chunk
 constexpr int P1_NSUBCHUNK = P1_CHUNK / P1_SUB;  // 8
 constexpr int P1_SCAN_THREADS = 1024;
 
-int p1_parts(int64_t S, int64_t nnz) {
-    int64_t p = std::min<int64_t>(P1_PARTS, (nnz + 63) / 64);
-    p = std::min<int64_t>(p, std::max<int64_t>(1, ((int64_t)1 << 26) / std::max<int64_t>(S, 1)));
-    return (int)std::max<int64_t>(p, 1);
-}
-int64_t p1_part_len(int64_t nnz, int parts) { return std::max<int64_t>(64, ((nnz + parts - 1) / parts + 63) / 64 * 64); }
-
 void p1_layout(int64_t N, int64_t S, int64_t C, int64_t nnz, saev_probe1d_layout* L) {
     std::memset(L, 0, sizeof *L);
     L->struct_size = (int32_t)sizeof *L;
     L->chunk = P1_CHUNK;
     L->words = (C + 31) / 32;
     L->max_chunks = nnz / P1_CHUNK + S;
-    L->parts = p1_parts(S, nnz);
+    L->parts = lm_parts(S, nnz);
     WsCarve ws;
     const int64_t pairs = S * C;
     L->off_err = ws.take(64);
@@ -642,7 +637,7 @@ int saev_probe1d_prepare(const int64_t* row_ptr, const int32_t* indices, const f
     int32_t* err = W.at<int32_t>(L.off_err);
     int32_t* cnt = W.at<int32_t>(L.off_cnt);
     int64_t* starts = W.at<int64_t>(L.off_starts);
-    const long part_len = (long)p1_part_len(nnz, (int)L.parts);
+    const long part_len = (long)lm_part_len(nnz, (int)L.parts);
     bool ok = hipMemsetAsync(err, 0, 64, s) == hipSuccess;
     ok = ok && hipMemsetAsync(cnt, 0, (size_t)(4 * L.parts * S), s) == hipSuccess;
     ok = ok && hipMemsetAsync(W.at<uint8_t>(L.off_pos), 0, (size_t)(8 * C), s) == hipSuccess;

@@ -3,11 +3,9 @@
 // firing 4-neighbours, sum of m^2, the per-cell count map and its sum of squares -- and the activation-weighted moments and per-cell
 // sums in a fixed order of addition.
 //
-//   prepare  the FIRING events latent-major in ascending row order, as probe1d.hip's prepare leaves its entries: one pass over the
-//            stored entries finds the row of each, checks its latent and its image's group (the error word) and keeps the row of an
-//            entry that fires (value > thr, group >= 0) or -1; integer atomics count every (part, latent); a pass per latent and
-//            one scan give the segments; ONE WAVE PER PART places its entries in order (rows ascend inside a part, parts are in row
-//            order, so every segment is in ascending row order whatever the timing).
+//   prepare  the FIRING events latent-major in ascending row order: the regroup of latent_major.h: a valid
+//            latent, the image's group in [0, G), value > thr.  Its first pass finds the row of each stored entry, checks
+//            its latent and its image's group (the error word) and keeps the row of an entry that fires, or -1.
 //   walk     a wave per latent, 64 events a trip.  Lane = event first: each lane loads its event and finds, by loads bounded to the
 //            latent's own list, whether its right neighbour (the next element, row + 1, not past the grid row's end) and its lower
 //            neighbour (row + gw, a binary search among the next gw elements, not past the image's end) fire, and -- at the first
@@ -19,9 +17,8 @@
 //            trips: a cell takes its terms in ascending image order, and two lanes never update one cell at once.
 //   overlap  a wave per (latent, group) squares and adds the cells of count_map.
 //
-// No floating-point atomic.  A latent that fires on most rows is one wave's serial walk.  The parts, scan and place
-// kernels restate probe1d.hip's with the event rule in front of them; that unit is left as it is.
-#include "entry_util.h"
+// No floating-point atomic.  A latent that fires on most rows is one wave's serial walk.
+#include "latent_major.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,16 +27,6 @@ namespace {
 
 constexpr int SP_MAX_G = 64;
 constexpr int SP_MAX_T = 4096;
-constexpr int SP_PARTS = 1024;  // at most this many contiguous parts of the stored entries in prepare's stable counting sort (4 096
-                                // parts bought the place pass an eighth and cost 200 MB of count table: its stores are the floor)
-constexpr int SP_SCAN_THREADS = 1024;
-
-int sp_parts(int64_t S, int64_t nnz) {
-    int64_t p = std::min<int64_t>(SP_PARTS, (nnz + 63) / 64);
-    p = std::min<int64_t>(p, std::max<int64_t>(1, ((int64_t)1 << 26) / std::max<int64_t>(S, 1)));
-    return (int)std::max<int64_t>(p, 1);
-}
-int64_t sp_part_len(int64_t nnz, int parts) { return std::max<int64_t>(64, ((nnz + parts - 1) / parts + 63) / 64 * 64); }
 
 bool sp_shape_ok(int64_t n_images, int64_t T, int64_t S, int64_t G, int64_t nnz) {
     if (n_images < 1 || T < 1 || T > SP_MAX_T || S < 1 || S > 0x7fffffffLL || G < 1 || G > SP_MAX_G || nnz < 0 || nnz > 0x7fffffffLL) return false;
@@ -49,130 +36,16 @@ bool sp_shape_ok(int64_t n_images, int64_t T, int64_t S, int64_t G, int64_t nnz)
 
 // byte offsets into the workspace (all multiples of 256); the error word comes first
 struct SpLayout {
-    int64_t parts, part_len, total_bytes;
-    int64_t off_err, off_starts, off_tot, off_cnt, off_fire_row, off_row, off_val;
+    int64_t off_err;
+    LmLayout lm;
+    int64_t total_bytes;
 };
 
 void sp_layout(int64_t S, int64_t nnz, SpLayout* L) {
-    *L = SpLayout{};
-    L->parts = sp_parts(S, nnz);
-    L->part_len = sp_part_len(nnz, (int)L->parts);
     WsCarve ws;
     L->off_err = ws.take(64);
-    L->off_starts = ws.take(8 * (S + 1));
-    L->off_tot = ws.take(4 * S);
-    L->off_cnt = ws.take(4 * L->parts * S);
-    L->off_fire_row = ws.take(4 * nnz);
-    L->off_row = ws.take(4 * nnz);
-    L->off_val = ws.take(4 * nnz);
+    lm_carve(ws, S, nnz, &L->lm);
     L->total_bytes = ws.at;
-}
-
-// ---------------------------------------------------------------- prepare ----------------------------------------------------------------
-
-// n_group[g] = images of group g; a group id outside [-1, G) is reported
-__global__ __launch_bounds__(256) void sp_groups_kernel(const int32_t* __restrict__ group, long n_images, int G, unsigned long long* __restrict__ n_group,
-                                                        int32_t* __restrict__ err) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_images; i += (long)gridDim.x * 256) {
-        const int g = group[i];
-        if (g < -1 || g >= G) atomicMax(err, SAEV_LATENT_SPATIAL_ERR_GROUP);
-        else if (g >= 0) atomicAdd(n_group + g, 1ull);
-    }
-}
-
-// the first pass over the entries: fire_row[e] = the row of entry e when it is an event of a valid latent in an image of a group in
-// [0, G), else -1; cnt[part][latent] counts the events
-__global__ __launch_bounds__(256) void sp_count_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ indices,
-                                                       const float* __restrict__ data, const int32_t* __restrict__ group, long nnz, int N, int S,
-                                                       int T, int G, float thr, long part_len, int32_t* __restrict__ fire_row,
-                                                       int32_t* __restrict__ cnt, int32_t* __restrict__ err) {
-    const int64_t p0 = row_ptr[0];
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (long)gridDim.x * 256) {
-        const int col = indices[p0 + e];
-        const int row = csr_row_of(row_ptr, N, p0 + e);
-        const int g = group[row / T];
-        int keep = -1;
-        if (col < 0 || col >= S) atomicMax(err, SAEV_LATENT_SPATIAL_ERR_LATENT);
-        else if (g < -1 || g >= G) atomicMax(err, SAEV_LATENT_SPATIAL_ERR_GROUP);
-        else if (g >= 0 && data[p0 + e] > thr) {  // NaN compares false
-            keep = row;
-            atomicAdd(cnt + (e / part_len) * S + col, 1);
-        }
-        fire_row[e] = keep;
-    }
-}
-
-// cnt[p][l] -> the events of latent l in parts before p; tot[l] = all of them
-__global__ __launch_bounds__(256) void sp_parts_kernel(int32_t* __restrict__ cnt, int parts, int S, int32_t* __restrict__ tot) {
-    const long l = (long)blockIdx.x * 256 + threadIdx.x;
-    if (l >= S) return;
-    int run = 0;
-    for (int p = 0; p < parts; p += 8) {  // eight loads in flight: a store to cnt would otherwise hold back the next load
-        int t[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t[q] = p + q < parts ? cnt[(size_t)(p + q) * S + l] : 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            if (p + q < parts) cnt[(size_t)(p + q) * S + l] = run;
-            run += t[q];
-        }
-    }
-    tot[l] = run;
-}
-
-__global__ __launch_bounds__(SP_SCAN_THREADS) void sp_scan_kernel(const int32_t* __restrict__ tot, int S, int64_t* __restrict__ starts) {
-    const long long end = block_scan_rounds<SP_SCAN_THREADS, long long, long>(
-        S, [&](long l) { return (long long)tot[l]; }, [&](long l, long long start) { starts[l] = start; });
-    if (threadIdx.x == 0) starts[S] = end;
-}
-
-// one wave per part (see the head of probe1d.hip): the rank of an event among the 64 of its trip by comparing lanes, the trip's base
-// by one integer atomic on a cursor only this wave touches
-__global__ __launch_bounds__(64) void sp_place_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ indices, const float* __restrict__ data,
-                                                      const int32_t* __restrict__ fire_row, long nnz, int S, long part_len,
-                                                      const int64_t* __restrict__ starts, int32_t* __restrict__ cnt,
-                                                      int32_t* __restrict__ row_out, float* __restrict__ val_out) {
-    const int lane = threadIdx.x;
-    const long part = blockIdx.x;
-    const long first = part * part_len, last = min(first + part_len, nnz);
-    const int64_t p0 = row_ptr[0];
-    int32_t* cur = cnt + (size_t)part * S;
-    // a trip's loads are issued one trip ahead: the atomic below returns a value, and nothing else hides its latency in a wave
-    // that works alone
-    int col_next = -1, row_next = -1;
-    float v_next = 0.f;
-    auto load = [&](long e) {
-        col_next = row_next = -1;
-        v_next = 0.f;
-        if (e < last) {
-            row_next = fire_row[e];
-            col_next = indices[p0 + e];
-            v_next = data[p0 + e];
-            if (row_next < 0 || col_next < 0 || col_next >= S) col_next = -1;  // (a kept row has its latent inside [0, S))
-        }
-    };
-    load(first + lane);
-    for (long g = first; g < last; g += 64) {
-        const int col = col_next, row = row_next;
-        const float v = v_next;
-        load(g + 64 + lane);
-        const int64_t start = col >= 0 ? starts[col] : 0;
-        int rank = 0, same = 0, leader = 64;
-#pragma unroll 16
-        for (int i = 0; i < 64; ++i) {
-            const bool match = col >= 0 && __builtin_amdgcn_readlane(col, i) == col;
-            same += match;
-            rank += match && i < lane;
-            leader = match && leader == 64 ? i : leader;
-        }
-        int base = 0;
-        if (col >= 0 && leader == lane) base = atomicAdd(cur + col, same);
-        base = __shfl(base, leader & 63, 64);
-        if (col >= 0) {
-            const int64_t at = start + base + rank;
-            if (at >= 0 && at < nnz) { row_out[at] = row; val_out[at] = v; }  // (always: the segments partition the events)
-        }
-    }
 }
 
 // ---------------------------------------------------------------- walk -------------------------------------------------------------------
@@ -340,33 +213,15 @@ int saev_latent_spatial(const int64_t* row_ptr, const int32_t* indices, const fl
 
     hipStream_t s = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
-    int32_t* err = reinterpret_cast<int32_t*>(ws + L.off_err);
-    int64_t* starts = reinterpret_cast<int64_t*>(ws + L.off_starts);
-    int32_t* tot = reinterpret_cast<int32_t*>(ws + L.off_tot);
-    int32_t* cnt = reinterpret_cast<int32_t*>(ws + L.off_cnt);
-    int32_t* fire_row = reinterpret_cast<int32_t*>(ws + L.off_fire_row);
-    int32_t* row = reinterpret_cast<int32_t*>(ws + L.off_row);
-    float* val = reinterpret_cast<float*>(ws + L.off_val);
+    const LmLists ev = lm_lists(ws, L.lm);
     const size_t cells = (size_t)(S * G * T);
-    bool ok = hipMemsetAsync(err, 0, 64, s) == hipSuccess;
-    ok = ok && hipMemsetAsync(cnt, 0, (size_t)(4 * L.parts * S), s) == hipSuccess;
-    ok = ok && hipMemsetAsync(n_group_images, 0, (size_t)(8 * G), s) == hipSuccess;
+    bool ok = hipMemsetAsync(n_group_images, 0, (size_t)(8 * G), s) == hipSuccess;
     ok = ok && hipMemsetAsync(count_map, 0, 4 * cells, s) == hipSuccess;
     if (sum_map) ok = ok && hipMemsetAsync(sum_map, 0, 8 * cells, s) == hipSuccess;
+    ok = ok && lm_regroup<SAEV_LATENT_SPATIAL_ERR_LATENT, SAEV_LATENT_SPATIAL_ERR_GROUP>(
+                    row_ptr, indices, data, nnz, N, S, group_i32, n_images, T, G, thr, n_group_images, ev, reinterpret_cast<int32_t*>(ws + L.off_err), s);
     if (!ok) return entry_refuse(SAEV_HIP_ERROR, who, "hipMemsetAsync failed");
-    hipLaunchKernelGGL(sp_groups_kernel, dim3((unsigned)std::min<int64_t>((n_images + 255) / 256, 1024)), dim3(256), 0, s, group_i32, (long)n_images,
-                       (int)G, reinterpret_cast<unsigned long long*>(n_group_images), err);
-    if (nnz > 0)
-        hipLaunchKernelGGL(sp_count_kernel, dim3((unsigned)std::min<int64_t>((nnz + 255) / 256, 8192)), dim3(256), 0, s, row_ptr, indices, data, group_i32,
-                           (long)nnz, (int)N, (int)S, (int)T, (int)G, thr, (long)L.part_len, fire_row, cnt, err);
-    hipLaunchKernelGGL(sp_parts_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, cnt, (int)L.parts, (int)S, tot);
-    hipLaunchKernelGGL(sp_scan_kernel, dim3(1), dim3(SP_SCAN_THREADS), 0, s, tot, (int)S, starts);
-    if (nnz > 0) {
-        const unsigned used = (unsigned)((nnz + L.part_len - 1) / L.part_len);
-        hipLaunchKernelGGL(sp_place_kernel, dim3(used), dim3(64), 0, s, row_ptr, indices, data, fire_row, (long)nnz, (int)S, (long)L.part_len, starts,
-                           cnt, row, val);
-    }
-    SpWalk a{starts, row, val, group_i32, (int)S, (int)G, (int)gh, (int)gw, (int)T,
+    SpWalk a{ev.starts, ev.row, ev.val, group_i32, (int)S, (int)G, (int)gh, (int)gw, (int)T,
              reinterpret_cast<long long*>(n_events), reinterpret_cast<long long*>(n_images_fire), reinterpret_cast<long long*>(pairs_h),
              reinterpret_cast<long long*>(pairs_v), reinterpret_cast<long long*>(sum_m2), moments, count_map, sum_map};
     hipLaunchKernelGGL(sp_walk_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, a);

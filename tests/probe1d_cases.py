@@ -10,12 +10,12 @@ import numpy as np
 import probe1d_restatement as R
 
 CHUNK = 512
-P1_PARTS = 1024          # kernels.h
-P1_CNT_ENTRIES = 1 << 26  # probe1d.hip, p1_parts: parts x S counters at the most
+P1_PARTS = 1024          # entry_util.h: LM_PARTS
+P1_CNT_ENTRIES = 1 << 26  # entry_util.h, lm_parts: parts x S counters at the most
 
 
 def parts_of(s, nnz):
-    """(parts, part_len) of prepare's counting sort, restated from probe1d.hip (p1_parts, p1_part_len)."""
+    """(parts, part_len) of prepare's counting sort, restated from entry_util.h (lm_parts, lm_part_len)."""
     parts = max(1, min(P1_PARTS, -(-nnz // 64), max(1, P1_CNT_ENTRIES // max(s, 1))))
     return parts, max(64, -(-(-(-nnz // parts)) // 64) * 64)
 

@@ -405,7 +405,7 @@ def test_both_label_forms_restate_to_the_same_bits():
 
 @pytest.mark.parametrize("name", list(K.PLACEMENT))
 def test_placement_designs_have_the_groups_per_part_they_are_named_for(name):
-    """From the library's own part count and p1_part_len restated here: a change of P1_PARTS or of the rule cannot quietly turn these
+    """From the library's own part count and lm_part_len restated here: a change of LM_PARTS or of the rule cannot quietly turn these
     designs into ones with a single group of 64 per part."""
     lib_mod, lib = _lib()
     fn, groups, parts, ragged = K.PLACEMENT[name]
@@ -413,7 +413,7 @@ def test_placement_designs_have_the_groups_per_part_they_are_named_for(name):
     L = lib_mod.SaevProbe1DLayout()
     assert lib.saev_probe1d_layout_of(d.n, d.s, d.c, d.nnz, C.byref(L)) == 0
     per_part = -(-d.nnz // L.parts)
-    part_len = max(64, -(-per_part // 64) * 64)  # p1_part_len
+    part_len = max(64, -(-per_part // 64) * 64)  # lm_part_len
     assert L.parts == parts and part_len == 64 * groups and (L.parts, part_len) == K.parts_of(d.s, d.nnz)
     assert -(-d.nnz // part_len) >= 2 and (not ragged or d.nnz % part_len != 0)
     assert d.indptr[0] == 0 and d.indptr[-1] == d.nnz == d.indices.size and d.indptr.size == d.n + 1 and (d.data < 0).any()

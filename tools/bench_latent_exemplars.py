@@ -40,9 +40,9 @@ N_IMAGES = N // T
 K = 8
 CHUNK = 256
 HBM_COPY = 6.29e12
-PREPARE = ("groups", "members", "count", "parts", "scan", "place")
-STAGES = {**{f"ex_{k}_kernel": "prepare" for k in PREPARE}, "ex_walk_kernel": "walk"}
-SPATIAL_STAGES = {**{f"sp_{k}_kernel": "prepare" for k in ("groups", "count", "parts", "scan", "place")}, "sp_walk_kernel": "walk", "sp_overlap_kernel": "overlap"}
+REGROUP = ("groups", "count", "parts", "scan", "place")  # latent_major.h; the names are prefixes: template arguments follow
+STAGES = {**{f"lm_{k}_kernel": "prepare" for k in REGROUP}, "ex_members_kernel": "prepare", "ex_walk_kernel": "walk"}
+SPATIAL_STAGES = {**{f"lm_{k}_kernel": "prepare" for k in REGROUP}, "sp_walk_kernel": "walk", "sp_overlap_kernel": "overlap"}
 
 
 def spread(ts):

@@ -35,7 +35,7 @@ N_IMAGES = N // T
 CHUNK = 256
 HBM_COPY = 6.29e12
 PREPARE = ("groups", "count", "parts", "scan", "place")
-STAGES = {**{f"sp_{k}": k for k in PREPARE}, "sp_walk": "walk", "sp_overlap": "overlap"}
+STAGES = {**{f"lm_{k}_kernel": k for k in PREPARE}, "sp_walk": "walk", "sp_overlap": "overlap"}  # (prefixes: template arguments follow)
 
 
 def stage_ms(fn):
