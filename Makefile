@@ -2,7 +2,7 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := saev_amd/csrc
-SRCS  := $(CSRC)/ctx.hip $(CSRC)/ctx_forward.hip $(CSRC)/ctx_auxk.hip $(CSRC)/ctx_backward.hip $(CSRC)/ctx_tail.hip $(CSRC)/ctx_dp.hip $(CSRC)/ctx_relu_train.hip $(CSRC)/gemm_encode.hip $(CSRC)/gemm_encode_f16x3.hip $(CSRC)/split.hip $(CSRC)/select.hip $(CSRC)/sparse.hip $(CSRC)/tail.hip $(CSRC)/auxk.hip $(CSRC)/relu.hip $(CSRC)/relu_train.hip $(CSRC)/muon.hip $(CSRC)/coherence.hip $(CSRC)/dictmatch.hip $(CSRC)/kmeans.hip $(CSRC)/batchstats.hip $(CSRC)/batchtopk.hip $(CSRC)/latenttopk.hip $(CSRC)/probe1d.hip $(CSRC)/latentap.hip $(CSRC)/sparselinear.hip $(CSRC)/intervene.hip $(CSRC)/coactivation.hip $(CSRC)/latenthist.hip $(CSRC)/spatial.hip $(CSRC)/exemplars.hip
+SRCS  := $(CSRC)/ctx.hip $(CSRC)/ctx_forward.hip $(CSRC)/ctx_auxk.hip $(CSRC)/ctx_backward.hip $(CSRC)/ctx_tail.hip $(CSRC)/ctx_dp.hip $(CSRC)/ctx_relu_train.hip $(CSRC)/gemm_encode.hip $(CSRC)/gemm_encode_f16x3.hip $(CSRC)/split.hip $(CSRC)/select.hip $(CSRC)/sparse.hip $(CSRC)/tail.hip $(CSRC)/auxk.hip $(CSRC)/relu.hip $(CSRC)/relu_train.hip $(CSRC)/muon.hip $(CSRC)/coherence.hip $(CSRC)/dictmatch.hip $(CSRC)/kmeans.hip $(CSRC)/batchstats.hip $(CSRC)/batchtopk.hip $(CSRC)/latenttopk.hip $(CSRC)/probe1d.hip $(CSRC)/latentap.hip $(CSRC)/sparselinear.hip $(CSRC)/intervene.hip $(CSRC)/coactivation.hip $(CSRC)/latenthist.hip $(CSRC)/spatial.hip $(CSRC)/exemplars.hip $(CSRC)/poolcsr.hip
 OBJS  := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
 FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wno-pass-failed -Wno-unused-value -Iinclude
 

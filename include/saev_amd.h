@@ -1357,6 +1357,48 @@ int saev_l1_logistic_iterate(const float* X, const int32_t* y, int64_t n, int64_
                              void* workspace, int64_t workspace_bytes, void* stream);
 int saev_l1_logistic_result(const float* X, const int32_t* y, int64_t n, int64_t S, int64_t K, double C, double kkt_tol, double* coef,
                             double* intercept, double* scalars, void* workspace, int64_t workspace_bytes, void* stream);
+/* POOL CSR (token codes pooled to an image-level CSR, never through an n_images x n_latents matrix: what the image-level forms of
+ * LATENT AUROC, LATENT OPERATING, LATENT HIST and COACTIVATION read), context-free; DESIGN.md 3.30.
+ *
+ * INPUT.  A token CSR as saev_pool_images takes it: indptr (n_images * tokens_per_image + 1 int64 absolute positions with
+ * indptr[last] <= nnz), indices int32 in [0, n_latents), data fp32; row i * tokens_per_image + p is patch p of image i.  Columns
+ * inside a row need not be sorted and a column may occur twice in a row.  The threshold of latent l is thr_vec[l] when thr_vec (n_latents
+ * fp32 on the device) is not NULL, and the scalar thr otherwise.
+ * CONTRACT.  Entry (i, l) of the output exists iff some patch of image i stores a value a of latent l with a > thr_l (strict: a NaN
+ * threshold passes nothing, +Inf silences the latent).  out_indptr (n_images + 1 int64, out_indptr[0] = 0), out_indices (int32,
+ * ascending inside every row), out_data (fp32: the maximum of the qualifying stored values, on the bits), and, unless NULL,
+ * out_patch (int32: the LOWEST patch index that attains the maximum, as LATENT EXEMPLARS) and out_count (int32: the stored entries
+ * of that image and latent that pass, a repeated column counting every time).  With thr = 0 the output is the non-zero pattern and
+ * the values of max(saev_pool_images(SAEV_POOL_MAX), 0).  A scalar thr must be finite and >= 0 (a negative one would admit the
+ * implicit zeros: SAEV_INVALID_ARG); a negative entry of thr_vec is SAEV_POOL_CSR_ERR_THRESHOLD.
+ * TWO CALLS, for the output's length is data.  saev_pool_csr_count writes ALL of out_indptr (the scan over images runs on the
+ * device); the caller reads out_indptr[n_images], provides arrays of that length, and saev_pool_csr_fill -- with the same input,
+ * thresholds and workspace, which carries every unit's first position from the one call to the other -- writes every element of
+ * them below out_indptr[n_images] exactly once: no memset of the outputs is needed and nothing at or past that length is touched.
+ * A fill that does not follow such a count writes nothing where the lengths differ and reports SAEV_POOL_CSR_ERR_INDPTR.  Neither
+ * call allocates, reads back or synchronises; no floating-point atomics: two calls give the same bits.
+ * err (one int32 on the device, zeroed by either call): 0, or the largest SAEV_POOL_CSR_ERR_* met -- the outputs are void then;
+ * out-of-range columns and a bad indptr read and write nothing out of bounds.
+ * A workgroup owns one image and saev_pool_csr_range() consecutive latents (a bit set, and in the fill pass the keys and counts of
+ * the set's members, in LDS), and walks the image's span of stored entries however long it is.  workspace:
+ * saev_pool_csr_workspace_bytes(n_images, tokens_per_image, n_latents, nnz) bytes of device memory, 256-byte aligned -- with units =
+ * n_images * ceil(n_latents / range): units + 1 int64 and ceil(units / 4096) int64, each rounded up to 256 bytes (-1 for a shape
+ * the entries refuse).  LIMITS: 1 <= n_images * tokens_per_image < 2^31, 1 <= n_latents < 2^31, and n_images * ceil(n_latents /
+ * saev_pool_csr_range()) < 2^31 (else SAEV_UNSUPPORTED).  Arguments are checked before the device is touched, in the order: sizes,
+ * the scalar threshold, input pointers, output pointers, workspace; a refused call leaves its message with saev_last_error(NULL). */
+#define SAEV_POOL_CSR_ERR_COLUMN 1     /* a column index outside [0, n_latents) */
+#define SAEV_POOL_CSR_ERR_VALUE 2      /* a stored value that is not finite */
+#define SAEV_POOL_CSR_ERR_INDPTR 3     /* indptr is not a non-decreasing sequence of positions into indices */
+#define SAEV_POOL_CSR_ERR_THRESHOLD 4  /* a negative entry of thr_vec */
+int64_t saev_pool_csr_range(void);
+int64_t saev_pool_csr_workspace_bytes(int64_t n_images, int64_t tokens_per_image, int64_t n_latents, int64_t nnz);
+int saev_pool_csr_count(const int64_t* indptr, const int32_t* indices, const float* data, int64_t nnz, int64_t n_images,
+                        int64_t tokens_per_image, int64_t n_latents, float thr, const float* thr_vec, int64_t* out_indptr, void* workspace,
+                        int64_t workspace_bytes, int32_t* err, void* stream);
+int saev_pool_csr_fill(const int64_t* indptr, const int32_t* indices, const float* data, int64_t nnz, int64_t n_images,
+                       int64_t tokens_per_image, int64_t n_latents, float thr, const float* thr_vec, const int64_t* out_indptr,
+                       int32_t* out_indices, float* out_data, int32_t* out_patch, int32_t* out_count, void* workspace,
+                       int64_t workspace_bytes, int32_t* err, void* stream);
 /* COACTIVATION (latents matched by what they fire on: idea 8, "cross-run feature alignment", of the reference's
  * contrib/mimics/README.md, which the reference never built), context-free; DESIGN.md 3.25.
  *

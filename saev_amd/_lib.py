@@ -266,6 +266,10 @@ _SIGNATURES = {
     "saev_latent_patch_rows": (C.c_int, [P, P, P] + [C.c_int64] * 4 + [P, P, C.c_int64, P, P, P]),
     "saev_pool_images_range": (C.c_int64, []),
     "saev_pool_images": (C.c_int, [P, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, P, P, P]),
+    "saev_pool_csr_range": (C.c_int64, []),
+    "saev_pool_csr_workspace_bytes": (C.c_int64, [C.c_int64] * 4),
+    "saev_pool_csr_count": (C.c_int, [P, P, P] + [C.c_int64] * 4 + [C.c_float, P, P, P, C.c_int64, P, P]),
+    "saev_pool_csr_fill": (C.c_int, [P, P, P] + [C.c_int64] * 4 + [C.c_float, P] + [P] * 5 + [P, C.c_int64, P, P]),
     "saev_l1_logistic_workspace_bytes": (C.c_int64, [C.c_int64] * 3),
     "saev_l1_logistic_layout_of": (C.c_int, [C.c_int64] * 3 + [C.POINTER(SaevL1LogisticLayout)]),
     "saev_l1_logistic_init": (C.c_int, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, P, C.c_int64, P]),

@@ -107,12 +107,8 @@ def worker_fn(cfg: Config) -> pathlib.Path:
         if tpi < 1 or n_rows % tpi:
             raise ValueError(f"{n_rows} token rows are no whole number of images of {tpi} tokens")
         n_rows //= tpi
-        pooled = torch.clamp_min(engine.pool_images(indptr, indices, data, n_rows, tpi, d_sae, "max").pooled, 0.0)
-        at = pooled != 0
-        indptr = torch.zeros(n_rows + 1, device=dev, dtype=torch.int64)
-        indptr[1:] = torch.cumsum(at.sum(dim=1), dim=0)
-        indices, data = at.nonzero()[:, 1].to(torch.int32), pooled[at]
-        del pooled, at
+        # the positive pooled maxima, in sparse form (what the non-zero entries of the clamped dense pooling were)
+        indptr, indices, data = engine.pool_csr(indptr, indices, data, n_rows, tpi, d_sae).triple()
     hist = engine.LatentHist(d_sae, dev)
     got = engine.latent_quantiles(indptr, indices, data, n_rows, d_sae, cfg.q, over=cfg.over, chunk_rows=cfg.chunk_rows, device=dev, hist=hist)
     counts, n_neg, edges = hist.histogram(cfg.lo_exp, cfg.hi_exp)

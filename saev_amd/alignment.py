@@ -19,7 +19,6 @@ import pathlib
 
 import numpy as np
 import scipy.sparse
-import torch
 
 from . import classification, engine, helpers
 
@@ -71,14 +70,6 @@ def load_token_acts(cfg: Config) -> tuple[scipy.sparse.csr_matrix, scipy.sparse.
     return ta_a, ta_b
 
 
-def _dense_to_csr(dense: torch.Tensor):
-    """The non-zero entries of a dense device matrix as a CSR triple on the device (ascending columns inside ascending rows)."""
-    at = dense != 0
-    indptr = torch.zeros(dense.shape[0] + 1, device=dense.device, dtype=torch.int64)
-    indptr[1:] = torch.cumsum(at.sum(dim=1), dim=0)
-    return indptr, at.nonzero()[:, 1].to(torch.int32), dense[at]
-
-
 def _top_k_sets(csr: scipy.sparse.csr_matrix, top_k: int, threshold: float) -> scipy.sparse.csr_matrix:
     """Per latent its ``top_k`` highest rows among those > threshold, back as a row-major CSR matrix (``helpers.csr_topk`` selects on
     the device; a latent with fewer such rows keeps them all)."""
@@ -96,11 +87,12 @@ def _sets_on_device(ta: scipy.sparse.csr_matrix, cfg: Config, dev):
         if tpi < 1 or n_rows % tpi:
             raise ValueError(f"{n_rows} rows are not a whole number of images of {tpi} tokens")
         n_rows //= tpi
-        # clamped at 0 as mimics._pool_on_device: the reference's pooling starts from zeros
-        pooled = torch.clamp_min(engine.pool_images(*classification._csr_on(ta, dev), n_rows, tpi, ta.shape[1], "max").pooled, 0.0)
+        # the positive maxima only, as mimics.max_pool_csr: the reference's pooling starts from zeros
+        pooled = engine.pool_csr(*classification._csr_on(ta, dev), n_rows, tpi, ta.shape[1]).triple()
         if cfg.top_k is None:
-            return _dense_to_csr(pooled), n_rows
-        ta = scipy.sparse.csr_matrix(pooled.cpu().numpy())
+            return pooled, n_rows
+        indptr, indices, data = (t.cpu().numpy() for t in pooled)
+        ta = scipy.sparse.csr_matrix((data, indices, indptr), shape=(n_rows, ta.shape[1]))
     elif cfg.level != "token":
         raise ValueError(f"level must be 'token' or 'image', got {cfg.level!r}")
     if cfg.top_k is not None:

@@ -903,3 +903,8 @@ constexpr int LA_DIRECT_MAX = 8;
 // ---- Sparse linear (sparselinear.hip: kernels and their C entries; include/saev_amd.h: SPARSE LINEAR) ------------------------------
 // latents of one pooling workgroup: an fp32 accumulator and an int32 patch count each, 64 KB of LDS (saev_pool_images_range)
 constexpr int SL_POOL_RANGE = 8192;
+
+// ---- Pool CSR (poolcsr.hip: kernels and their C entries; include/saev_amd.h: POOL CSR) ---------------------------------------------
+// latents of one sparse-pooling workgroup: a bit of the LDS set each (64 words of 64 bits, one wave's scan) and, in the fill pass, at
+// most as many 64-bit keys and int32 counts, 48 KB of LDS (saev_pool_csr_range); wider dictionaries are walked in ranges
+constexpr int POOL_CSR_RANGE = 4096;

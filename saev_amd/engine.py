@@ -13,6 +13,7 @@ import dataclasses
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1594,6 +1595,85 @@ def pool_images(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor,
     _lib.check(lib, None, rc, "saev_pool_images")
     range_len = int(lib.saev_pool_images_range())
     return PoolResult(out, err, -(-n_latents // range_len), range_len)
+
+
+class PoolCsrResult(_Checked):
+    """What ``pool_csr`` leaves on the device: the image-level CSR ``indptr`` (n_images + 1) int64, ``indices`` (nnz) int32 ascending
+    inside every row, ``data`` (nnz) float32; with ``details=True`` also ``patch`` and ``count`` (nnz) int32, else None.  ``nnz`` is a
+    host int.  The first read of an array -- or ``check()`` -- reads the device's error word (one synchronisation) and raises
+    ValueError if it is not 0."""
+
+    _ERRORS = {1: "a column index lies outside [0, n_latents)", 2: "a stored value is not finite",
+               3: "indptr is not a non-decreasing sequence of positions into indices", 4: "an entry of the threshold vector is negative"}
+
+    def __init__(self, out, err, nnz, ws):
+        super().__init__(out, err, self._ERRORS, "pool_csr")
+        self.nnz, self._ws = nnz, ws
+
+    indptr = property(lambda self: self._read("indptr"))
+    indices = property(lambda self: self._read("indices"))
+    data = property(lambda self: self._read("data"))
+    patch = property(lambda self: self._read("patch"))
+    count = property(lambda self: self._read("count"))
+
+    def triple(self):
+        """(indptr, indices, data), as ``latent_auroc``, ``latent_operating``, ``latent_quantiles``, ``coactivation_match`` and
+        ``latent_ap`` take them."""
+        return self.indptr, self.indices, self.data
+
+
+def pool_csr(indptr: torch.Tensor, indices: torch.Tensor, data: torch.Tensor, n_images: int, tokens_per_image: int, n_latents: int,
+             threshold=0.0, details: bool = False) -> PoolCsrResult:
+    """Pool a token CSR on the device (as ``pool_images`` takes it; unsorted rows and repeated columns are allowed) to the image-level
+    CSR, without the (n_images, n_latents) matrix (include/saev_amd.h: POOL CSR).  Entry (i, l) exists iff some patch
+    of image i stores a value of latent l ABOVE the latent's threshold (strict); its value is the maximum of those values.
+    ``threshold`` is one finite float >= 0 or a (n_latents,) float32 vector (a device tensor, or a numpy array that is copied over)
+    in the strict form ``operating.thresholds`` and ``activation_stats.thresholds`` hand out: NaN passes nothing, +Inf silences the
+    latent, a negative entry raises on first read.  With threshold 0 the result is the non-zero pattern and the values of
+    ``clamp_min(pool_images(..., "max").pooled, 0)``.  ``details=True`` adds ``patch`` (the lowest patch that attains the maximum)
+    and ``count`` (the stored entries that pass).  The call runs the count pass, reads ``out_indptr[-1]`` once -- an 8-byte read-back,
+    its only synchronisation --, allocates the arrays exactly and runs the fill pass.  Memory is that of the output and of
+    ``saev_pool_csr_workspace_bytes``.  There is no CPU path."""
+    who = "pool_csr"
+    for name, v in (("n_images", n_images), ("tokens_per_image", tokens_per_image), ("n_latents", n_latents)):
+        if not 1 <= v < 2**31:
+            raise ValueError(f"{who}: unsupported {name} {v} (1 <= {name} < 2^31)")
+    if n_images * tokens_per_image >= 2**31:
+        raise ValueError(f"{who}: unsupported n_images * tokens_per_image {n_images * tokens_per_image} (below 2^31)")
+    vector = isinstance(threshold, (torch.Tensor, np.ndarray))
+    if not vector:
+        threshold = float(threshold)
+        if not (0.0 <= threshold < float("inf")):
+            raise ValueError(f"{who}: a scalar threshold must be finite and at least 0, got {threshold}")
+    elif tuple(threshold.shape) != (n_latents,) or threshold.dtype not in (torch.float32, np.float32):
+        raise ValueError(f"{who}: a threshold vector must be float32 of shape ({n_latents},), got {threshold.dtype} {tuple(threshold.shape)}")
+    device = _hip_device(who, indptr.device)
+    nnz_in = indices.numel()
+    indptr, indices, data = _csr_on(indptr, indices, data, n_images * tokens_per_image, nnz_in, device)
+    thr_vec = None
+    if vector:
+        thr_vec = _on(torch.from_numpy(threshold).to(device) if isinstance(threshold, np.ndarray) else threshold, torch.float32, (n_latents,),
+                      "threshold", device)
+    lib = _lib.load()
+    need = int(lib.saev_pool_csr_workspace_bytes(n_images, tokens_per_image, n_latents, nnz_in))
+    if need < 0:
+        raise ValueError(f"{who}: {n_images} images of {n_latents} latents are more than 2^31 (image, latent range) units: pool in slices of images")
+    ws = torch.empty(need, device=device, dtype=torch.uint8)
+    out_indptr = torch.empty(n_images + 1, device=device, dtype=torch.int64)
+    err = torch.empty(1, device=device, dtype=torch.int32)
+    shared = (_ptr(indptr), _ptr(indices), _ptr(data), nnz_in, n_images, tokens_per_image, n_latents, 0.0 if vector else threshold, _ptr(thr_vec))
+    with torch.cuda.device(device):
+        rc = lib.saev_pool_csr_count(*shared, _ptr(out_indptr), _ptr(ws), need, _ptr(err), _stream())
+        _lib.check(lib, None, rc, "saev_pool_csr_count")
+        nnz = int(out_indptr[-1].item())  # the call's one read-back
+        i32 = dict(device=device, dtype=torch.int32)
+        out = dict(indptr=out_indptr, indices=torch.empty(nnz, **i32), data=torch.empty(nnz, device=device, dtype=torch.float32),
+                   patch=torch.empty(nnz, **i32) if details else None, count=torch.empty(nnz, **i32) if details else None)
+        if nnz > 0:
+            rc = lib.saev_pool_csr_fill(*shared, _ptr(out_indptr), _ptr(out["indices"]), _ptr(out["data"]), _ptr(out["patch"]), _ptr(out["count"]),
+                                        _ptr(ws), need, _ptr(err), _stream())
+            _lib.check(lib, None, rc, "saev_pool_csr_fill")
+    return PoolCsrResult(out, err, nnz, ws)
 
 
 class CoactResult(_Checked):

@@ -1,5 +1,5 @@
 """Latent-level scoring for mimic-pair feature triage: the reference's ``contrib/mimics`` ``mimics.tasks`` and ``mimics.scoring`` over
-``engine.pool_images`` and ``engine.latent_auroc`` (include/saev_amd.h: LATENT AUROC), without polars.
+``engine.pool_csr`` and ``engine.latent_auroc`` (include/saev_amd.h: POOL CSR, LATENT AUROC), without polars.
 
 Every SAE latent is scored on every mimic-pair task -- one subspecies of H. erato against its co-mimic of H. melpomene, in one view
 -- by AUROC, the share of each class's images on which it fires, and its mean activation per class.  The token codes of
@@ -197,6 +197,19 @@ def max_pool_csr(ta_csr, n_images: int, tpi: int, device=None) -> np.ndarray:
     return _pool_on_device(ta_csr, n_images, tpi, classification._device(device)).cpu().numpy()
 
 
+def _pool_sparse_on_device(ta_csr, n_images: int, tpi: int, dev):
+    """The image-level CSR triple of ``max_pool_csr``'s non-zero entries on the device, pooled in sparse form (``engine.pool_csr`` at
+    threshold 0: the positive maxima, for the reference's pooling starts from zeros); never an (n_images, d_sae) matrix."""
+    return engine.pool_csr(*classification._csr_on(ta_csr, dev), n_images, tpi, ta_csr.shape[1]).triple()
+
+
+def max_pool_sparse(ta_csr, n_images: int, tpi: int, device=None) -> scipy.sparse.csr_matrix:
+    """``scipy.sparse.csr_matrix(max_pool_csr(...))`` without the dense matrix: (n_images, d_sae) float32 CSR with sorted columns."""
+    assert ta_csr.shape[0] == n_images * tpi, f"{ta_csr.shape[0]} != {n_images} * {tpi}"
+    indptr, indices, data = _pool_sparse_on_device(ta_csr, n_images, tpi, classification._device(device))
+    return scipy.sparse.csr_matrix((data.cpu().numpy(), indices.cpu().numpy(), indptr.cpu().numpy()), shape=(n_images, ta_csr.shape[1]))
+
+
 def get_scores_fpath(run_root_dpath: pathlib.Path, *, run_id: str, shard_id: str) -> pathlib.Path:
     return pathlib.Path(run_root_dpath) / run_id / "inference" / shard_id / PARQUET_FNAME
 
@@ -254,15 +267,9 @@ def score_run(run_id: str, *, run_root_dpath: pathlib.Path, shard_id: str, task_
     dev = classification._device(device)
 
     logger.info("Max-pooling %s (shape %s, tpi=%d).", run_id, ta.shape, tpi)
-    pooled = _pool_on_device(ta, n_images, tpi, dev)
+    # the non-zero pooled entries as CSR, on the device (ascending columns inside ascending rows)
+    indptr, indices, data = _pool_sparse_on_device(ta, n_images, tpi, dev)
     del ta
-    # the non-zero pooled entries as CSR, on the device (row-major order: ascending columns inside ascending rows)
-    at = pooled != 0
-    indptr = torch.zeros(n_images + 1, device=dev, dtype=torch.int64)
-    indptr[1:] = torch.cumsum(at.sum(dim=1), dim=0)
-    indices = at.nonzero()[:, 1].to(torch.int32)
-    data = pooled[at]
-    del pooled, at
 
     cls, roles = task_classes(task_specs, n_images)
     assert roles.shape[1] <= 4096, f"{roles.shape[1]} classes of images; at most 4096 are supported"

@@ -118,7 +118,7 @@ def score_run(run_id: str, cfg: Config) -> dict[str, np.ndarray] | None:
     if cfg.level == "image":
         n_images, names, cls, roles = _image_tasks(cfg, shards_dpath)
         tpi = ta.shape[0] // n_images
-        x = scipy.sparse.csr_matrix(mimics.max_pool_csr(ta, n_images, tpi))
+        x = mimics.max_pool_sparse(ta, n_images, tpi)
     else:
         names, cls, roles = _token_tasks(cfg, shards_dpath, ta)
         x = ta
